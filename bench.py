@@ -9,22 +9,32 @@ One step = one pass of the whole hot path over one batch of synthetic input that
 masked MSE -> hand-written backward -> (bucketed RCCL all-reduce overlapped with backward) -> fused Adam.  Numeric mode (--precision):
 'hybrid' by default since round 6 - fp16 CNN stem, f32 residual stream through the Conformer blocks / decoder with f32 activations and
 weights contracted as fp16 pairs on the matrix cores, bf16 backward - the mode that meets the 1e-3 per-bin tolerance against the
-reference; 'fp16' (fp16 forward / bf16 backward) is timed next to it in the same line (`fast_mode`).  f32 accumulation; dropout active
-(training mode), nothing cached or skipped.
+reference; with --full, 'fp16' (fp16 forward / bf16 backward) is timed next to it in the same line (`fast_mode`).  f32 accumulation;
+dropout active (training mode), nothing cached or skipped.
 
-Rank 0 prints ONE JSON line.  Besides the contract's fields it carries
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times `--steps` steps, writes the last timed step's outputs when
+`--dump-outputs DIR` is given, and prints the line: the contract's fields (`ms_per_step` = wall time of the timed region / steps),
+the run's configuration, first / final loss of the timed region, host time and C-ABI calls per step, and
+  * `knobs`: the resolved state of every environment switch that selects a compute path (a line is only comparable with another one
+    under the same knobs; ablation switches that skip work do not exist in the product and any SARSSL_ABLATE* variable is refused);
+  * `parity_class`: what the timed numeric mode is pinned to against the reference (tests/, DESIGN.md section 2);
+  * `dist` (data parallel): backend, RCCL version, ranks, bytes per gradient bucket.
+`--full` adds what the headline does not need, each measured after the timed region:
   * `roofline`: measured live with events on the launch stream around every BN-prologue launch of the dominant kernel
     (conv3x3_fwd_pp_kernel<false>, the forward 3x3 convolution with a stored 64-channel input), the effective shader clock of those
     launches (in-kernel s_memtime / s_memrealtime probe), and the sibling launches under their own labels;
   * `cpu_baseline`: the CPU oracle (oracle/sarssl_oracle.py, the validated restatement of the reference) timed on this host;
-  * `knobs`: the resolved state of every environment switch that selects a compute path (a line is only comparable with another one
-    under the same knobs; ablation switches that skip work do not exist in the product and any SARSSL_ABLATE* variable is refused);
-  * `parity_class`: what the timed numeric mode is pinned to against the reference (tests/, DESIGN.md section 2);
   * `product_loop` (N = 1): the same step driven the way run_pretrain.py drives it - PCM-16 WAV files -> dataset.PcmSegmentLoader
     (native reader thread + pinned upload) -> STFTLearner.pretrain_epoch (captured step, STFT inside the replay);
-  * `dist` (N > 1): backend, RCCL version, ranks, bytes per gradient bucket, the event-timed all-reduce of each bucket and `overlap_check`
-    (the CNN-stem backward window the exchange hides under against the sum of the buckets issued in front of it);
-  * `fast_mode` / `tolerance_mode` (N = 1): a short timed run of the other 16-bit mode on the same box and batches.
+  * `dist` (data parallel): the event-timed all-reduce of each bucket and `overlap_check` (the CNN-stem backward window the exchange
+    hides under against the sum of the buckets issued in front of it);
+  * `fast_mode` / `tolerance_mode` (N = 1): a short timed run of the other 16-bit mode on the same box and batches;
+  * `host_enqueue_ms_per_step`: host time to issue one step into an idle queue.
+`--no-cpu-baseline`, `--no-product-loop` and `--no-other-mode` leave single blocks out of a `--full` line.
+`--dump-outputs DIR` writes what the timed step hands its caller after the last timed step, as DIR/<name>.npy: `loss.npy` and
+`diff.npy` (float32, shape (1,)) and `params.npy`, the parameter vector Adam wrote (float32; a fixed sample of DUMP_PARAMS entries,
+drawn with seed 0, when it holds more).  Inputs, weights, masks and dropout are seeded, so two builds run with the same arguments can
+be compared output for output.
 `--via-learner` makes the product loop the line's primary value; `--workload config5` times BASELINE config 5 (4-microphone 10 s
 segments: 3 microphone pairs per segment, T = 624 frames).
 """
@@ -54,6 +64,18 @@ WORKLOADS = {
     "config2": (65792, 2, 256, 1),
     "config5": (160000, 4, 624, 3),
 }
+DUMP_PARAMS = 1 << 22              # --dump-outputs: parameters written at most (16 MB of float32; the model has 17.5 M)
+
+
+def dump_outputs(d, loss, diff, params):
+    """--dump-outputs: the step's loss and diff and the parameter vector (a seeded sample of DUMP_PARAMS entries if longer) as .npy."""
+    os.makedirs(d, exist_ok=True)
+    p = params.detach().reshape(-1)
+    if p.numel() > DUMP_PARAMS:
+        idx = np.sort(np.random.default_rng(0).choice(p.numel(), DUMP_PARAMS, replace=False))
+        p = p[torch.from_numpy(idx).to(p.device)]
+    for name, v in (("loss", loss), ("diff", diff), ("params", p)):
+        np.save(os.path.join(d, name + ".npy"), v.detach().float().reshape(-1).cpu().numpy())
 
 
 def flop_per_segment(workload):
@@ -362,7 +384,14 @@ def main():
     ap.add_argument("--launch-probe", action="store_true",
                     help="launcher self-test: start the ranks, form the process group, agree on a value, print the line's launch fields "
                          "and exit without running the step (no GPU needed; tests/test_launch_cpu.py)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline / kernel families / clock and power telemetry, host enqueue "
+                         "time, the other 16-bit mode, the product loop, the CPU-oracle baseline, per-bucket all-reduce timing (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's loss, diff and parameters (seeded sample) to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.dump_outputs and args.via_learner:
+        ap.error("--dump-outputs writes the resident-batch step's outputs; it does not combine with --via-learner")
     # `python bench.py --gpus N` starts its own N ranks (one process per GPU over RCCL) - the reference's multi-GPU form is one command
     # too (code/run_pretrain.py:204-205).  This happens BEFORE anything touches the GPU: the parent only waits, forwards rank 0's single
     # line (rank 0 inherits stdout) and exits with the worst rank's code.  Under torchrun (WORLD_SIZE set) nothing is spawned.
@@ -422,6 +451,8 @@ def main():
         pcm.copy_(pcms[step_no[0] % NRES])
         step_no[0] += 1
 
+    eager_out = {}
+
     def step_eager():
         next_batch()
         x = hip.stft_frontend(pcm)
@@ -430,6 +461,7 @@ def main():
         g = reducer.finish()
         opt.step(grad_scale=g)
         opt.zero_grad()
+        eager_out["diff"] = diff.detach()
         return loss
 
     # the training step of the product path (learner.pretrain_epoch): STFT front-end + masks + forward + backward + (all-reduce) + Adam
@@ -474,7 +506,7 @@ def main():
     graph = state["graph"]
     state_graph = graph
     clk = torch.zeros(20, dtype=torch.int64, device=dev)       # clock probe of the convolution launches (csrc/conv3x3.hip)
-    if graph is None:
+    if graph is None and args.full:
         hip.profile_start()
     n0 = _lib.ncalls
     t0 = time.perf_counter()
@@ -487,60 +519,62 @@ def main():
     torch.cuda.synchronize(); barrier(); torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     calls_per_step = (_lib.ncalls - n0) / max(args.steps, 1)
-    # host work per step: the time the host needs to ENQUEUE one step into an idle GPU queue (no waiting behind earlier work: the
-    # per-step uploads of masks / the batch copy block only as long as the device is busy).  The loop time above contains that waiting.
-    enq = []
-    for _ in range(5):
-        torch.cuda.synchronize()
-        te = time.perf_counter()
-        step()
-        enq.append(time.perf_counter() - te)
-    torch.cuda.synchronize()
-    host_enqueue_ms = 1e3 * sorted(enq)[len(enq) // 2]
-    tele = None
-    if not os.environ.get("SARSSL_BENCH_NO_TELEMETRY"):
-        tele = telemetry(lambda k: [step() for _ in range(k)], sample=(rank == 0))
-    prof2 = {}
-    hip.conv_clock_probe(clk)
-    if graph is None:
-        prof = hip.profile_stop()
-        step_eager()                                           # (one more step with the clock probe attached)
-        torch.cuda.synchronize()
-    else:
-        # per-kernel durations: a graph replay offers no host-side events around single launches, so the event-bracketed launches
-        # are taken from eager steps of the SAME training run right after the timed region (same shapes, same kernels, the two
-        # encoder streams still overlapping); profiles/ holds the rocprofv3 kernel trace of the graph replays themselves
-        opt.m, opt.v, opt.step_count = graph.m, graph.v, graph.nsteps
-        for _ in range(2):
-            step_eager()
-        torch.cuda.synchronize()
-        hip.profile_start()
-        for _ in range(6):
-            step_eager()
-        prof2 = hip.profile_stop()                         # two encoder streams: durations stretched by the co-running stream
-        os.environ["SARSSL_TWO_STREAMS"] = "0"             # one stream: each launch has the GPU to itself, as in rocprof's
-        step_eager()                                       # per-kernel statistics of a single-stream run
-        torch.cuda.synchronize()
-        import gc
-        gc.collect()
-        gc.disable()                                       # (a collection pause inside an event interval reads as a slow launch)
-        hip.profile_start(all_calls=True)                  # + every C-ABI call under its entry point's name: the step's time by family
-        for _ in range(6):
-            hip.gpu_runway(40.0)                           # the profiled step is host-bound: keep the GPU queue fed (hip.gpu_runway)
-            step_eager()
+    loss_val = float(last.detach())                   # (read here: the replays of --full's measurements reuse the step's result buffer)
+    first_loss_val = float(first.reshape(-1)[0]) if first is not None else None
+    assert np.isfinite(loss_val), "non-finite loss"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last, graph.out[1] if graph is not None else eager_out["diff"], flat.flat)
+    host_enqueue_ms, tele, prof, prof2, wall_khz, clk_step = None, None, {}, {}, 0, np.zeros((5, 4), dtype=np.int64)
+    if args.full:
+        # host work per step: the time the host needs to ENQUEUE one step into an idle GPU queue (no waiting behind earlier work: the
+        # per-step uploads of masks / the batch copy block only as long as the device is busy).  The loop time above contains that waiting.
+        enq = []
+        for _ in range(5):
             torch.cuda.synchronize()
-        prof = hip.profile_stop()
-        gc.enable()
-        os.environ["SARSSL_TWO_STREAMS"] = "1"
-    wall_khz = _lib.lib().sarssl_wall_clock_khz()
-    clk_step = clk.cpu().numpy().reshape(5, 4).copy()
+            te = time.perf_counter()
+            step()
+            enq.append(time.perf_counter() - te)
+        torch.cuda.synchronize()
+        host_enqueue_ms = 1e3 * sorted(enq)[len(enq) // 2]
+        if not os.environ.get("SARSSL_BENCH_NO_TELEMETRY"):
+            tele = telemetry(lambda k: [step() for _ in range(k)], sample=(rank == 0))
+        hip.conv_clock_probe(clk)
+        if graph is None:
+            prof = hip.profile_stop()
+            step_eager()                                           # (one more step with the clock probe attached)
+            torch.cuda.synchronize()
+        else:
+            # per-kernel durations: a graph replay offers no host-side events around single launches, so the event-bracketed launches
+            # are taken from eager steps of the SAME training run right after the timed region (same shapes, same kernels, the two
+            # encoder streams still overlapping); profiles/ holds the rocprofv3 kernel trace of the graph replays themselves
+            opt.m, opt.v, opt.step_count = graph.m, graph.v, graph.nsteps
+            for _ in range(2):
+                step_eager()
+            torch.cuda.synchronize()
+            hip.profile_start()
+            for _ in range(6):
+                step_eager()
+            prof2 = hip.profile_stop()                         # two encoder streams: durations stretched by the co-running stream
+            os.environ["SARSSL_TWO_STREAMS"] = "0"             # one stream: each launch has the GPU to itself, as in rocprof's
+            step_eager()                                       # per-kernel statistics of a single-stream run
+            torch.cuda.synchronize()
+            import gc
+            gc.collect()
+            gc.disable()                                       # (a collection pause inside an event interval reads as a slow launch)
+            hip.profile_start(all_calls=True)                  # + every C-ABI call under its entry point's name: the step's time by family
+            for _ in range(6):
+                hip.gpu_runway(40.0)                           # the profiled step is host-bound: keep the GPU queue fed (hip.gpu_runway)
+                step_eager()
+                torch.cuda.synchronize()
+            prof = hip.profile_stop()
+            gc.enable()
+            os.environ["SARSSL_TWO_STREAMS"] = "1"
+        wall_khz = _lib.lib().sarssl_wall_clock_khz()
+        clk_step = clk.cpu().numpy().reshape(5, 4).copy()
     el = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     if dp:
         torch.distributed.all_reduce(el, op=torch.distributed.ReduceOp.MAX)
     elapsed = float(el[0])
-    loss_val = float(last.detach())
-    first_loss_val = float(first.reshape(-1)[0]) if first is not None else None
-    assert np.isfinite(loss_val), "non-finite loss"
 
     def eff_ghz(slot):
         """effective shader clock of the last probed launch of a variant: shader-clock ticks / constant-rate ticks x that rate"""
@@ -554,42 +588,43 @@ def main():
         dist_info = reducer.describe()
         if world == 1:
             dist_info["note"] = "SARSSL_DIST_FORCE=1: one rank - every all-reduce is a copy; this run exercises the RCCL code path, it is not a scaling point"
-        ms = reducer.time_buckets(iters=5)
-        t = torch.tensor([ms.get(b["name"], 0.0) for b in dist_info["buckets"]], dtype=torch.float64, device=dev)
-        torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
-        for b, v in zip(dist_info["buckets"], t.cpu().tolist()):
-            b["allreduce_ms_alone"] = round(v, 4)
-            b["bus_GBps_alone"] = round(2.0 * (world - 1) / world * b["bytes"] / (v * 1e-3) / 1e9, 1) if v > 0 else None
-        # overlap check (round-5 verdict: the first multi-GPU run has to document itself): the window the exchange is meant to hide under -
-        # the CNN-stem backward, event-timed between the "stem_bwd_begin" and "stems" stage hooks of launch-by-launch steps - against the
-        # sum of the three buckets issued in front of it, each timed alone above.  hidden_if_alone_times_hold: the buckets fit the window.
-        marks = {}
+        if args.full:
+            ms = reducer.time_buckets(iters=5)
+            t = torch.tensor([ms.get(b["name"], 0.0) for b in dist_info["buckets"]], dtype=torch.float64, device=dev)
+            torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
+            for b, v in zip(dist_info["buckets"], t.cpu().tolist()):
+                b["allreduce_ms_alone"] = round(v, 4)
+                b["bus_GBps_alone"] = round(2.0 * (world - 1) / world * b["bytes"] / (v * 1e-3) / 1e9, 1) if v > 0 else None
+            # overlap check (round-5 verdict: the first multi-GPU run has to document itself): the window the exchange is meant to hide under -
+            # the CNN-stem backward, event-timed between the "stem_bwd_begin" and "stems" stage hooks of launch-by-launch steps - against the
+            # sum of the three buckets issued in front of it, each timed alone above.  hidden_if_alone_times_hold: the buckets fit the window.
+            marks = {}
 
-        def timed_hook(name):
-            if name in ("stem_bwd_begin", "stems"):
-                ev = torch.cuda.Event(enable_timing=True)
-                ev.record()
-                marks.setdefault(name, []).append(ev)
-            reducer._on_stage(name)
-        try:
-            net.set_backward_stage_hook(timed_hook)
-            opt.m, opt.v, opt.step_count = (state_graph.m, state_graph.v, state_graph.nsteps) if state_graph is not None else (opt.m, opt.v, opt.step_count)
-            for _ in range(4):
-                step_eager()
-            torch.cuda.synchronize()
-            wins = [a.elapsed_time(b) for a, b in zip(marks.get("stem_bwd_begin", []), marks.get("stems", []))][1:]
-            win = torch.tensor([sorted(wins)[len(wins) // 2] if wins else 0.0], dtype=torch.float64, device=dev)
-            torch.distributed.all_reduce(win, op=torch.distributed.ReduceOp.MIN)
-            early = sum(b["allreduce_ms_alone"] for b in dist_info["buckets"] if b["name"] != "stems")
-            dist_info["overlap_check"] = {"stem_backward_window_ms_min_over_ranks": round(float(win[0]), 3),
-                                          "allreduce_ms_alone_of_the_buckets_issued_before_it": round(early, 3),
-                                          "hidden_if_alone_times_hold": bool(early <= float(win[0])),
-                                          "note": "eager launch-by-launch steps, events on the origin stream at the stage hooks; the buckets share "
-                                                  "the node's xGMI links with nothing else but each other"}
-        except Exception as e:                             # (diagnostics only)
-            dist_info["overlap_check"] = {"error": repr(e)}
-        finally:
-            net.set_backward_stage_hook(reducer._on_stage)
+            def timed_hook(name):
+                if name in ("stem_bwd_begin", "stems"):
+                    ev = torch.cuda.Event(enable_timing=True)
+                    ev.record()
+                    marks.setdefault(name, []).append(ev)
+                reducer._on_stage(name)
+            try:
+                net.set_backward_stage_hook(timed_hook)
+                opt.m, opt.v, opt.step_count = (state_graph.m, state_graph.v, state_graph.nsteps) if state_graph is not None else (opt.m, opt.v, opt.step_count)
+                for _ in range(4):
+                    step_eager()
+                torch.cuda.synchronize()
+                wins = [a.elapsed_time(b) for a, b in zip(marks.get("stem_bwd_begin", []), marks.get("stems", []))][1:]
+                win = torch.tensor([sorted(wins)[len(wins) // 2] if wins else 0.0], dtype=torch.float64, device=dev)
+                torch.distributed.all_reduce(win, op=torch.distributed.ReduceOp.MIN)
+                early = sum(b["allreduce_ms_alone"] for b in dist_info["buckets"] if b["name"] != "stems")
+                dist_info["overlap_check"] = {"stem_backward_window_ms_min_over_ranks": round(float(win[0]), 3),
+                                              "allreduce_ms_alone_of_the_buckets_issued_before_it": round(early, 3),
+                                              "hidden_if_alone_times_hold": bool(early <= float(win[0])),
+                                              "note": "eager launch-by-launch steps, events on the origin stream at the stage hooks; the buckets share "
+                                                      "the node's xGMI links with nothing else but each other"}
+            except Exception as e:                             # (diagnostics only)
+                dist_info["overlap_check"] = {"error": repr(e)}
+            finally:
+                net.set_backward_stage_hook(reducer._on_stage)
         dist_info["steps_seen_by_reducer"] = reducer.nsteps
         dist_info["overlap"] = "buckets issued from backward-stage hooks (decoder -> spat -> spec before the CNN-stem backward, stems after it)"
 
@@ -600,33 +635,6 @@ def main():
     if rank == 0:
         segs_total = batch * world * args.steps
         value = segs_total / elapsed
-        n, ms = prof.get("conv3x3_fwd:bn_prologue", (0, 0.0))          # forward 3x3 convolutions with a stored input (BN+ReLU prologue): 2 per step
-        nc1, msc1 = prof.get("conv3x3_fwd_c1", (0, 0.0))               # the other 2: input formed from the stem's 4-channel input while staging
-        nr1, msr1 = prof.get("conv3x3_dgrad_c1red", (0, 0.0))          # data gradient consumed in its epilogue (nothing stored)
-        nd, msd = prof.get("conv3x3_fwd:identity", (0, 0.0))           # plain data-gradient launches of the same kernel
-        nb, msb = prof.get("conv3x3_dgrad_bnred", (0, 0.0))            # <true> variant: data gradient + BatchNorm-backward sums
-        flop_per_launch = 2.0 * npix_b * 256 * T * 64 * 576              # one 3x3 64->64 conv over B' x 256 x T pixels
-        achieved = (flop_per_launch / (ms / n * 1e-3)) / 1e12 if n else 0.0
-        nw, msw = prof.get("conv3x3_wgrad_kernel", (0, 0.0))
-        if os.environ.get("SARSSL_BENCH_DEBUG"):
-            for k in sorted(prof):
-                if "conv" in k:
-                    print("prof", k, prof[k][0], round(prof[k][1] / max(prof[k][0], 1), 4), file=sys.stderr)
-        # HBM traffic / MFMA-busy per launch from the committed PMC passes (same kernels, same shape; tools/prof_counters.py: separate
-        # rocprofv3 --pmc runs, FETCH_SIZE x 2 on gfx950).  tag -> variant of the 3x3 family
-        PMC_TAGS = {20: "fwd_bn_prologue", 24: "fwd_from_4ch_input", 22: "dgrad_bnred", 26: "dgrad_consumed_in_epilogue", 23: "wgrad", 25: "wgrad_from_4ch_input"}
-        traffic, mfma_busy, pmc_file, pmc_var = None, None, None, {}
-        for name in ("r06_kernel_counters.json", "r05_kernel_counters.json", "r04_kernel_counters.json", "r03_kernel_counters.json", "r02_kernel_counters.json"):
-            pmc = os.path.join(ROOT, "profiles", name)
-            if traffic is None and args.workload == "config2" and batch == 64 and os.path.exists(pmc):
-                for e in json.load(open(pmc)).get("kernels", []):
-                    if e.get("tag") in PMC_TAGS and e.get("kernel", "").startswith("conv3x3_") and "hbm_read_mb" in e and "hbm_write_mb" in e:
-                        pmc_var[PMC_TAGS[e["tag"]]] = {"traffic": (e["hbm_read_mb"] + e["hbm_write_mb"]) * 1e6, "mfma_busy": e.get("mfma_busy"),
-                                                       "pmc_pass_avg_us": e.get("avg_us")}
-                if "fwd_bn_prologue" in pmc_var:
-                    traffic, mfma_busy, pmc_file = pmc_var["fwd_bn_prologue"]["traffic"], pmc_var["fwd_bn_prologue"]["mfma_busy"], name
-        fps = flop_per_segment(args.workload)
-        fexec = flop_executed_per_segment(args.workload, compact=bool(engine._DEC_MASKED and engine._TAIL_MASKED), hybrid=args.precision == "hybrid")
         seg_desc = "%dch %.3fs@16kHz segments (%d microphone pair%s, T = %d frames)" % (nmic, nsample / 16000.0, pairs, "" if pairs == 1 else "s", T)
         out = {
             "metric": "pretrain_segments_per_sec", "value": round(value, 2), "unit": "segments/s",
@@ -640,102 +648,133 @@ def main():
             "config": {"workload": "SAR-SSL MC-Conformer cross-channel-reconstruction pretrain step (STFT+mask+fwd+bwd+Adam), "
                                    "%s, batch %d per GPU, dropout on" % (seg_desc, batch),
                        "baseline_config": args.workload, "global_batch": batch * world, "segment_samples": nsample, "parallelism": "dp%d" % world},
-            "roofline": {"bound": None,
-                         "kernel": "conv3x3_fwd_pp_kernel<false>, BN+ReLU-prologue launches (the forward 3x3 convolutions; events around "
-                                   "exactly these launches inside training steps" +
-                                   (", the other encoder's stream running concurrently" if graph is None else
-                                    "; a graph replay has no per-launch host events, so: 6 eager single-stream steps of the same run "
-                                    "right after the timed replays - two_stream_avg_ms = the same with both encoder streams") + ")",
-                         "achieved": round(achieved, 1),
-                         "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s", "frac": round(achieved / PEAK_BF16_TFLOPS, 4),
-                         "traffic": traffic, "traffic_source": pmc_file, "mfma_busy": mfma_busy, "launches": n,
-                         "avg_ms": round(ms / n, 4) if n else None, "effective_clock_ghz": eff_ghz(clk_step[0]),
-                         "flop_per_launch": flop_per_launch,
-                         "fwd_from_4ch_input_avg_ms": round(msc1 / nc1, 4) if nc1 else None, "fwd_from_4ch_input_clock_ghz": eff_ghz(clk_step[3]),
-                         "dgrad_consumed_in_epilogue_avg_ms": round(msr1 / nr1, 4) if nr1 else None,
-                         "dgrad_consumed_in_epilogue_clock_ghz": eff_ghz(clk_step[4]),
-                         "dgrad_identity_avg_ms": round(msd / nd, 4) if nd else None, "dgrad_identity_clock_ghz": eff_ghz(clk_step[1]),
-                         "dgrad_bnred_avg_ms": round(msb / nb, 4) if nb else None, "dgrad_bnred_clock_ghz": eff_ghz(clk_step[2]),
-                         "wgrad_avg_ms": round(msw / nw, 4) if nw else None,
-                         "two_stream_avg_ms": (round(prof2["conv3x3_fwd:bn_prologue"][1] / prof2["conv3x3_fwd:bn_prologue"][0], 4)
-                                               if prof2.get("conv3x3_fwd:bn_prologue", (0, 0))[0] else None),
-                         "nominal_clock_ghz": 2.4,
-                         "flop_per_segment_step": fps,
-                         # whole-step fraction of the dense 16-bit matrix-core peak: with the REFERENCE's op count (what a user of the
-                         # reference would compute), with the FLOPs the step executes (decoder / last-block tails on the masked frames
-                         # only) and - hybrid mode - with the matrix-core FLOPs it issues (fp16-pair products)
-                         "end_to_end_frac": round(value / world * fps / (PEAK_BF16_TFLOPS * 1e12), 4),
-                         "end_to_end_frac_reference_flops": round(value / world * fps / (PEAK_BF16_TFLOPS * 1e12), 4),
-                         "flop_per_segment_step_executed": fexec[0],
-                         "end_to_end_frac_executed_flops": round(value / world * fexec[0] / (PEAK_BF16_TFLOPS * 1e12), 4),
-                         "mfma_flop_per_segment_step_issued": fexec[1],
-                         "end_to_end_frac_issued_mfma_flops": round(value / world * fexec[1] / (PEAK_BF16_TFLOPS * 1e12), 4),
-                         "families": families(prof, 6, npix_b, T, batch, pairs, fps)},
+        }
+        if args.full:
+            n, ms = prof.get("conv3x3_fwd:bn_prologue", (0, 0.0))          # forward 3x3 convolutions with a stored input (BN+ReLU prologue): 2 per step
+            nc1, msc1 = prof.get("conv3x3_fwd_c1", (0, 0.0))               # the other 2: input formed from the stem's 4-channel input while staging
+            nr1, msr1 = prof.get("conv3x3_dgrad_c1red", (0, 0.0))          # data gradient consumed in its epilogue (nothing stored)
+            nd, msd = prof.get("conv3x3_fwd:identity", (0, 0.0))           # plain data-gradient launches of the same kernel
+            nb, msb = prof.get("conv3x3_dgrad_bnred", (0, 0.0))            # <true> variant: data gradient + BatchNorm-backward sums
+            flop_per_launch = 2.0 * npix_b * 256 * T * 64 * 576              # one 3x3 64->64 conv over B' x 256 x T pixels
+            achieved = (flop_per_launch / (ms / n * 1e-3)) / 1e12 if n else 0.0
+            nw, msw = prof.get("conv3x3_wgrad_kernel", (0, 0.0))
+            if os.environ.get("SARSSL_BENCH_DEBUG"):
+                for k in sorted(prof):
+                    if "conv" in k:
+                        print("prof", k, prof[k][0], round(prof[k][1] / max(prof[k][0], 1), 4), file=sys.stderr)
+            # HBM traffic / MFMA-busy per launch from the committed PMC passes (same kernels, same shape; tools/prof_counters.py: separate
+            # rocprofv3 --pmc runs, FETCH_SIZE x 2 on gfx950).  tag -> variant of the 3x3 family
+            PMC_TAGS = {20: "fwd_bn_prologue", 24: "fwd_from_4ch_input", 22: "dgrad_bnred", 26: "dgrad_consumed_in_epilogue", 23: "wgrad", 25: "wgrad_from_4ch_input"}
+            traffic, mfma_busy, pmc_file, pmc_var = None, None, None, {}
+            for name in ("r06_kernel_counters.json", "r05_kernel_counters.json", "r04_kernel_counters.json", "r03_kernel_counters.json", "r02_kernel_counters.json"):
+                pmc = os.path.join(ROOT, "profiles", name)
+                if traffic is None and args.workload == "config2" and batch == 64 and os.path.exists(pmc):
+                    for e in json.load(open(pmc)).get("kernels", []):
+                        if e.get("tag") in PMC_TAGS and e.get("kernel", "").startswith("conv3x3_") and "hbm_read_mb" in e and "hbm_write_mb" in e:
+                            pmc_var[PMC_TAGS[e["tag"]]] = {"traffic": (e["hbm_read_mb"] + e["hbm_write_mb"]) * 1e6, "mfma_busy": e.get("mfma_busy"),
+                                                           "pmc_pass_avg_us": e.get("avg_us")}
+                    if "fwd_bn_prologue" in pmc_var:
+                        traffic, mfma_busy, pmc_file = pmc_var["fwd_bn_prologue"]["traffic"], pmc_var["fwd_bn_prologue"]["mfma_busy"], name
+            fps = flop_per_segment(args.workload)
+            fexec = flop_executed_per_segment(args.workload, compact=bool(engine._DEC_MASKED and engine._TAIL_MASKED), hybrid=args.precision == "hybrid")
+            out["roofline"] = {"bound": None,
+                               "kernel": "conv3x3_fwd_pp_kernel<false>, BN+ReLU-prologue launches (the forward 3x3 convolutions; events around "
+                                         "exactly these launches inside training steps" +
+                                         (", the other encoder's stream running concurrently" if graph is None else
+                                          "; a graph replay has no per-launch host events, so: 6 eager single-stream steps of the same run "
+                                          "right after the timed replays - two_stream_avg_ms = the same with both encoder streams") + ")",
+                               "achieved": round(achieved, 1),
+                               "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s", "frac": round(achieved / PEAK_BF16_TFLOPS, 4),
+                               "traffic": traffic, "traffic_source": pmc_file, "mfma_busy": mfma_busy, "launches": n,
+                               "avg_ms": round(ms / n, 4) if n else None, "effective_clock_ghz": eff_ghz(clk_step[0]),
+                               "flop_per_launch": flop_per_launch,
+                               "fwd_from_4ch_input_avg_ms": round(msc1 / nc1, 4) if nc1 else None, "fwd_from_4ch_input_clock_ghz": eff_ghz(clk_step[3]),
+                               "dgrad_consumed_in_epilogue_avg_ms": round(msr1 / nr1, 4) if nr1 else None,
+                               "dgrad_consumed_in_epilogue_clock_ghz": eff_ghz(clk_step[4]),
+                               "dgrad_identity_avg_ms": round(msd / nd, 4) if nd else None, "dgrad_identity_clock_ghz": eff_ghz(clk_step[1]),
+                               "dgrad_bnred_avg_ms": round(msb / nb, 4) if nb else None, "dgrad_bnred_clock_ghz": eff_ghz(clk_step[2]),
+                               "wgrad_avg_ms": round(msw / nw, 4) if nw else None,
+                               "two_stream_avg_ms": (round(prof2["conv3x3_fwd:bn_prologue"][1] / prof2["conv3x3_fwd:bn_prologue"][0], 4)
+                                                     if prof2.get("conv3x3_fwd:bn_prologue", (0, 0))[0] else None),
+                               "nominal_clock_ghz": 2.4,
+                               "flop_per_segment_step": fps,
+                               # whole-step fraction of the dense 16-bit matrix-core peak: with the REFERENCE's op count (what a user of the
+                               # reference would compute), with the FLOPs the step executes (decoder / last-block tails on the masked frames
+                               # only) and - hybrid mode - with the matrix-core FLOPs it issues (fp16-pair products)
+                               "end_to_end_frac": round(value / world * fps / (PEAK_BF16_TFLOPS * 1e12), 4),
+                               "end_to_end_frac_reference_flops": round(value / world * fps / (PEAK_BF16_TFLOPS * 1e12), 4),
+                               "flop_per_segment_step_executed": fexec[0],
+                               "end_to_end_frac_executed_flops": round(value / world * fexec[0] / (PEAK_BF16_TFLOPS * 1e12), 4),
+                               "mfma_flop_per_segment_step_issued": fexec[1],
+                               "end_to_end_frac_issued_mfma_flops": round(value / world * fexec[1] / (PEAK_BF16_TFLOPS * 1e12), 4),
+                               "families": families(prof, 6, npix_b, T, batch, pairs, fps)}
+            # ---- both axes of the roofline (round-4 verdict): arithmetic intensity of the named kernel = algorithmic FLOPs / measured HBM
+            # bytes against the ridge 2500 TFLOP/s / 8 TB/s = 312.5 FLOP/B decides `bound`; `frac` is the fraction of THAT bound's peak,
+            # mfma_frac / hbm_frac carry both; `variants` does the same for every launch variant of the 3x3 family
+            rf = out["roofline"]
+            RIDGE = PEAK_BF16_TFLOPS * 1e12 / 8.0e12
+            avg_s = (ms / n * 1e-3) if n else None
+            rf["mfma_achieved_tflops"], rf["mfma_frac"] = rf["achieved"], rf["frac"]
+            rf["ridge_flop_per_byte"] = RIDGE
+            if traffic and avg_s:
+                ai = flop_per_launch / traffic
+                rf["arithmetic_intensity_flop_per_byte"] = round(ai, 1)
+                rf["hbm_achieved_gbps"] = round(traffic / avg_s / 1e9, 1)
+                rf["hbm_frac"] = round(traffic / avg_s / 8.0e12, 4)
+                rf["bound"] = "hbm" if ai < RIDGE else "mfma"
+                if rf["bound"] == "hbm":
+                    rf["achieved"], rf["peak"], rf["unit"], rf["frac"] = rf["hbm_achieved_gbps"], 8000.0, "GB/s", rf["hbm_frac"]
+                rf["bound_note"] = ("arithmetic intensity %.0f FLOP/B vs ridge %.1f: %s side of the ridge (both fractions are within 10 %% of each "
+                                    "other: the launch sits at the ridge, limited by neither peak but by its per-tile schedule)" %
+                                    (ai, RIDGE, "bandwidth" if ai < RIDGE else "compute"))
+            else:
+                rf["bound"] = "mfma"
+                rf["bound_note"] = "no PMC traffic for this workload / batch: arithmetic intensity not measured, MFMA fraction reported"
+            live = {"fwd_bn_prologue": (n, ms), "fwd_from_4ch_input": (nc1, msc1), "dgrad_bnred": (nb, msb), "dgrad_consumed_in_epilogue": (nr1, msr1),
+                    "wgrad": (nw, msw), "wgrad_from_4ch_input": (nw, msw)}
+            variants = {}
+            for vname, (cnt, tot) in live.items():
+                if not cnt:
+                    continue
+                a_s = tot / cnt * 1e-3
+                v = {"avg_ms": round(tot / cnt, 4), "mfma_tflops": round(flop_per_launch / a_s / 1e12, 1),
+                     "mfma_frac": round(flop_per_launch / a_s / 1e12 / PEAK_BF16_TFLOPS, 4)}
+                pv = pmc_var.get(vname)
+                if pv:
+                    v.update({"traffic": pv["traffic"], "hbm_gbps": round(pv["traffic"] / a_s / 1e9, 1), "hbm_frac": round(pv["traffic"] / a_s / 8.0e12, 4),
+                              "flop_per_byte": round(flop_per_launch / pv["traffic"], 1), "bound": "hbm" if flop_per_launch / pv["traffic"] < RIDGE else "mfma",
+                              "mfma_busy_pmc": pv["mfma_busy"], "pmc_pass_avg_us": pv["pmc_pass_avg_us"]})
+                variants[vname] = v
+            if "wgrad" in variants and "wgrad_from_4ch_input" in variants:
+                variants["wgrad"]["note"] = variants["wgrad_from_4ch_input"]["note"] = "live average over BOTH weight-gradient variants (one label)"
+            rf["variants"] = variants
+            # clock: in-kernel probe (effective_clock_ghz) next to the power / sclk telemetry of the running step - the part clocks to its power
+            # budget (DVFS): matrix-heavy launches run below the 2.4 GHz the peak is quoted at
+            rf["telemetry_during_step"] = tele
+            if rf.get("effective_clock_ghz"):
+                rf["peak_at_effective_clock_tflops"] = round(PEAK_BF16_TFLOPS * rf["effective_clock_ghz"] / 2.4, 1)
+                rf["mfma_frac_at_effective_clock"] = round(rf["mfma_achieved_tflops"] / rf["peak_at_effective_clock_tflops"], 4)
+        out.update({
             # loss of the first and the last step of the timed region (lr 1e-3, dropout on, four resident batches round-robin, set-up and warm-up
             # steps in front): tests/test_gpu_train.py::test_bench_batches_loss_goes_down pins the direction at this batch size
             "first_loss": round(first_loss_val, 5) if first_loss_val is not None else None,
             "final_loss": round(loss_val, 5),
             "step_mode": "eager launches" if graph is None else "hipGraph replay (%d graph(s) per step)" % sum(1 for k, _ in graph._plan if k == "graph"),
-            # host_enqueue: host time to issue one step into an idle queue (what must stay below the step time for the host not to be the
-            # critical path); host_ms_per_step: wall time of the issue loop per step (includes waiting behind the device in blocking uploads)
-            "host_enqueue_ms_per_step": round(host_enqueue_ms, 3),
+            # host_ms_per_step: wall time of the issue loop per step (includes waiting behind the device in blocking uploads)
             "host_ms_per_step": round(1e3 * t_host / args.steps, 3),
             "host_calls_per_step": round(calls_per_step, 1),
             # (SARSSL_STEM_LAST_ALL_CUS only takes effect on one GPU: under data parallelism both stems keep the 7/8 rule, model.py - the N = 1
             #  point of a scaling curve is therefore this build with the knob on, the N > 1 points are with it off: +1.2 % at N = 1)
             "knobs": dict(engine.knobs(), STEM_LAST_ALL_CUS_effective=int(engine._STEM_LAST_ALL_CUS and not dp)),
             "parity_class": parity.parity_class(args.precision),
-        }
-        # ---- both axes of the roofline (round-4 verdict): arithmetic intensity of the named kernel = algorithmic FLOPs / measured HBM
-        # bytes against the ridge 2500 TFLOP/s / 8 TB/s = 312.5 FLOP/B decides `bound`; `frac` is the fraction of THAT bound's peak,
-        # mfma_frac / hbm_frac carry both; `variants` does the same for every launch variant of the 3x3 family
-        rf = out["roofline"]
-        RIDGE = PEAK_BF16_TFLOPS * 1e12 / 8.0e12
-        avg_s = (ms / n * 1e-3) if n else None
-        rf["mfma_achieved_tflops"], rf["mfma_frac"] = rf["achieved"], rf["frac"]
-        rf["ridge_flop_per_byte"] = RIDGE
-        if traffic and avg_s:
-            ai = flop_per_launch / traffic
-            rf["arithmetic_intensity_flop_per_byte"] = round(ai, 1)
-            rf["hbm_achieved_gbps"] = round(traffic / avg_s / 1e9, 1)
-            rf["hbm_frac"] = round(traffic / avg_s / 8.0e12, 4)
-            rf["bound"] = "hbm" if ai < RIDGE else "mfma"
-            if rf["bound"] == "hbm":
-                rf["achieved"], rf["peak"], rf["unit"], rf["frac"] = rf["hbm_achieved_gbps"], 8000.0, "GB/s", rf["hbm_frac"]
-            rf["bound_note"] = ("arithmetic intensity %.0f FLOP/B vs ridge %.1f: %s side of the ridge (both fractions are within 10 %% of each "
-                                "other: the launch sits at the ridge, limited by neither peak but by its per-tile schedule)" %
-                                (ai, RIDGE, "bandwidth" if ai < RIDGE else "compute"))
-        else:
-            rf["bound"] = "mfma"
-            rf["bound_note"] = "no PMC traffic for this workload / batch: arithmetic intensity not measured, MFMA fraction reported"
-        live = {"fwd_bn_prologue": (n, ms), "fwd_from_4ch_input": (nc1, msc1), "dgrad_bnred": (nb, msb), "dgrad_consumed_in_epilogue": (nr1, msr1),
-                "wgrad": (nw, msw), "wgrad_from_4ch_input": (nw, msw)}
-        variants = {}
-        for vname, (cnt, tot) in live.items():
-            if not cnt:
-                continue
-            a_s = tot / cnt * 1e-3
-            v = {"avg_ms": round(tot / cnt, 4), "mfma_tflops": round(flop_per_launch / a_s / 1e12, 1),
-                 "mfma_frac": round(flop_per_launch / a_s / 1e12 / PEAK_BF16_TFLOPS, 4)}
-            pv = pmc_var.get(vname)
-            if pv:
-                v.update({"traffic": pv["traffic"], "hbm_gbps": round(pv["traffic"] / a_s / 1e9, 1), "hbm_frac": round(pv["traffic"] / a_s / 8.0e12, 4),
-                          "flop_per_byte": round(flop_per_launch / pv["traffic"], 1), "bound": "hbm" if flop_per_launch / pv["traffic"] < RIDGE else "mfma",
-                          "mfma_busy_pmc": pv["mfma_busy"], "pmc_pass_avg_us": pv["pmc_pass_avg_us"]})
-            variants[vname] = v
-        if "wgrad" in variants and "wgrad_from_4ch_input" in variants:
-            variants["wgrad"]["note"] = variants["wgrad_from_4ch_input"]["note"] = "live average over BOTH weight-gradient variants (one label)"
-        rf["variants"] = variants
-        # clock: in-kernel probe (effective_clock_ghz) next to the power / sclk telemetry of the running step - the part clocks to its power
-        # budget (MI355X_MICROARCH.md "DVFS give-back"): matrix-heavy launches run below the 2.4 GHz the peak is quoted at
-        rf["telemetry_during_step"] = tele
-        if rf.get("effective_clock_ghz"):
-            rf["peak_at_effective_clock_tflops"] = round(PEAK_BF16_TFLOPS * rf["effective_clock_ghz"] / 2.4, 1)
-            rf["mfma_frac_at_effective_clock"] = round(rf["mfma_achieved_tflops"] / rf["peak_at_effective_clock_tflops"], 4)
+        })
+        if args.full:
+            # host time to issue one step into an idle queue (what must stay below the step time for the host not to be the critical path)
+            out["host_enqueue_ms_per_step"] = round(host_enqueue_ms, 3)
         if dist_info is not None:
             out["dist"] = dist_info
     del graph, state
-    if world == 1 and rank == 0 and args.precision in ("hybrid", "fp16") and not args.no_other_mode and not args.eager and from_pcm_in_graph:
+    if args.full and world == 1 and rank == 0 and args.precision in ("hybrid", "fp16") and not args.no_other_mode and not args.eager and from_pcm_in_graph:
         # the other 16-bit mode on the same box, same batches, same captured step: `fast_mode` (fp16 forward / bf16 backward) next to a
         # hybrid headline, `tolerance_mode` (hybrid) next to an fp16 one - so that one line carries the price of the per-bin tolerance
         other = "fp16" if args.precision == "hybrid" else "hybrid"
@@ -745,7 +784,7 @@ def main():
             out["fast_mode" if other == "fp16" else "tolerance_mode"] = {"error": repr(e)}
         runtime.set_precision(args.precision)
     if world == 1:
-        want_loop = (not args.no_product_loop or args.via_learner) and args.workload == "config2" and not dp
+        want_loop = ((args.full and not args.no_product_loop) or args.via_learner) and args.workload == "config2" and not dp
         if want_loop:
             opt = None
             net._stage_hook = None
@@ -758,8 +797,9 @@ def main():
                 out["value"], out["ms_per_step"], out["steps"] = loop["value"], loop["ms_per_step"], loop["steps"]
                 out["step_mode"] = loop["step_mode"]
                 out["config"]["workload"] += "; driven through " + loop["path"]
-                out["roofline"]["end_to_end_frac"] = round(loop["value"] * flop_per_segment(args.workload) / (PEAK_BF16_TFLOPS * 1e12), 4)
-        if not args.no_cpu_baseline:
+                if "roofline" in out:
+                    out["roofline"]["end_to_end_frac"] = round(loop["value"] * flop_per_segment(args.workload) / (PEAK_BF16_TFLOPS * 1e12), 4)
+        if args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
     if rank == 0:
         os.write(json_fd, (json.dumps(out) + "\n").encode())

@@ -583,6 +583,36 @@ def f15_edge_cases(ref_model, ref_learner):
     np.savez_compressed(os.path.join(GOLD, "f15_edge_cases.npz"), **store)
 
 
+def f16_small_step(ref_model, ref_learner, B=3, T=8, nsample=48):
+    """One small pretraining step of the reference (train mode, dropout 0, recipe weights seed 3, signal seed 9, Python's RNG seeded 11
+    in front of the forward): front-end output, loss, diff and, per parameter, the gradient's largest magnitude, its norm and `nsample`
+    sampled entries (all of them for smaller tensors).  Weight shapes: the pretrain manifest (the same at T = 8 as at T = 256).
+    tests/test_oracle_vs_reference.py."""
+    net = ref_model.SARSSL(sig_shape=(256, T, 2, 2), pretrain=True, device="cpu")
+    man = load_recipe(net, 3)
+    assert man == json.load(open(os.path.join(GOLD, "state_dict_manifest.json")))["pretrain"]
+    set_dropout(net, 0.0)
+    net.train()
+    lrn = ref_learner.STFTLearner(net, win_len=512, win_shift_ratio=0.5, nfft=512, fre_used_ratio=1, fs=16000, task=None, ch_mode="M")
+    lrn.cpu()
+    sig = recipes.recipe_signal(B, 512 + 256 * (T - 1), 2, seed=9)
+    x, = lrn.data_preprocess(sig, None)
+    random.seed(11)
+    loss, diff, _ = net(x)
+    loss.backward()
+    names, offs, sidx, svals, gmax, gn = [], [0], [], [], [], []
+    for k, p in net.named_parameters():
+        g = p.grad.reshape(-1)
+        si = sample_idx(g.numel(), nsample, 29)
+        names.append(k); sidx.append(si.astype(np.int32)); svals.append(g[si].numpy().copy()); offs.append(offs[-1] + len(si))
+        gmax.append(float(g.abs().max())); gn.append(float(g.double().norm()))
+    store = {"B": B, "T": T, "weight_seed": 3, "sig_seed": 9, "mask_seed": 11, "x": x.numpy(), "loss": np.float64(loss.item()),
+             "diff": np.float64(diff.item()), "names_json": np.array(json.dumps(names)), "sample_offsets": np.array(offs),
+             "sample_idx": np.concatenate(sidx), "sample_vals": np.concatenate(svals), "grad_absmax": np.array(gmax), "grad_norm": np.array(gn)}
+    print("f16 loss", loss.item(), "diff", diff.item(), flush=True)
+    np.savez_compressed(os.path.join(GOLD, "f16_small_step.npz"), **store)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--curve", action="store_true")
@@ -593,7 +623,7 @@ if __name__ == "__main__":
     torch.set_num_threads(8)
     os.makedirs(GOLD, exist_ok=True)
     ref_model, ref_learner, ref_um = ref_shim.load()
-    todo = a.only.split(",") if a.only else ["manifest", "f1", "f2", "f3", "f4", "f6", "f7", "f8", "f9", "f10", "f11", "f12", "f13", "f14", "f15"]
+    todo = a.only.split(",") if a.only else ["manifest", "f1", "f2", "f3", "f4", "f6", "f7", "f8", "f9", "f10", "f11", "f12", "f13", "f14", "f15", "f16"]
     if "manifest" in todo: f_manifest(ref_model)
     if "f1" in todo: f1_frontend(ref_learner, ref_model)
     if "f2" in todo: f2_blocks(ref_model)
@@ -609,6 +639,7 @@ if __name__ == "__main__":
     if "f13" in todo: f13_full_batch(ref_model, ref_learner)
     if "f14" in todo: f14_full_batch_gradient(ref_model, ref_learner)
     if "f15" in todo: f15_edge_cases(ref_model, ref_learner)
+    if "f16" in todo: f16_small_step(ref_model, ref_learner)
     if a.curve: f5_curve(ref_model, ref_learner)
     if a.curve_dropout: f5_curve_dropout(ref_model, ref_learner)
     print("golden vectors written to", GOLD)

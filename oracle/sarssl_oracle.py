@@ -10,8 +10,8 @@ anything from ``oracle/`` and has no CPU fallback.
 Parity pinning: ``oracle/make_golden.py`` (run in the build container, where
 ``/root/reference`` exists) executes the REAL reference modules on seeded inputs and stores
 inputs/outputs under ``tests/golden/``; ``tests/test_oracle_golden.py`` checks this file
-against those vectors, ``tests/test_oracle_vs_reference.py`` checks it live against the
-reference when the tree is present.  The reference itself ships no tests or golden vectors
+against those vectors, ``tests/test_oracle_vs_reference.py`` against the reference's gradients
+of one small step (fixture F16).  The reference itself ships no tests or golden vectors
 (SURVEY.md section 4), so those fixtures are the pin.
 
 Every function cites the reference lines it restates (paths relative to /root/reference).

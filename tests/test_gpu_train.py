@@ -304,7 +304,7 @@ def test_two_rank_bench_path_over_gloo(launcher):
     import socket
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     env = dict(os.environ, SARSSL_DIST_BACKEND="gloo")
-    tail = [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "4"]
+    tail = [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "4", "--full"]
     if launcher == "torchrun":
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                "--master-port", str(port)] + tail
@@ -340,7 +340,7 @@ def test_data_parallel_step_over_rccl_with_a_one_rank_process_group(mode):
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     env = dict(os.environ, SARSSL_DIST_FORCE="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     env.pop("SARSSL_DIST_BACKEND", None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--batch", "8", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--batch", "8", "--full", "--no-cpu-baseline"]
     if mode == "eager":
         cmd.append("--eager")
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env)
@@ -354,6 +354,30 @@ def test_data_parallel_step_over_rccl_with_a_one_rank_process_group(mode):
     assert np.isfinite(out["final_loss"]) and out["value"] > 0 and "product_loop" not in out
     assert out["step_mode"] == ("eager launches" if mode == "eager" else "hipGraph replay (4 graph(s) per step)")
     assert out["knobs"]["STEM_LAST_ALL_CUS_effective"] == 0             # the data-parallel knob set
+
+
+def test_plain_bench_line_and_dumped_outputs_repeat(tmp_path):
+    """`bench.py` without --full: the headline fields over exactly --steps timed steps and none of --full's blocks; --dump-outputs
+    writes the last timed step's loss, diff and parameter sample as float32 .npy - the same bits in a second run with the same arguments."""
+    dumps = []
+    for i in range(2):
+        d = tmp_path / ("out%d" % i)
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "4", "--dump-outputs", str(d)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, lines
+        out = json.loads(lines[0])
+        assert out["metric"] == "pretrain_segments_per_sec" and out["unit"] == "segments/s" and out["higher_is_better"] is True
+        assert out["steps"] == 3 and out["ms_per_step"] > 0 and abs(out["value"] * out["ms_per_step"] / 4e3 - 1) < 1e-2
+        assert not {"roofline", "fast_mode", "product_loop", "cpu_baseline", "host_enqueue_ms_per_step"} & set(out)
+        z = {n: np.load(str(d / (n + ".npy"))) for n in ("loss", "diff", "params")}
+        assert all(v.dtype == np.float32 for v in z.values()) and z["loss"].shape == z["diff"].shape == (1,)
+        assert z["params"].shape == (1 << 22,) and np.isfinite(z["params"]).all()
+        assert abs(float(z["loss"][0]) - out["final_loss"]) < 1e-5
+        dumps.append(z)
+    for n in dumps[0]:
+        assert np.array_equal(dumps[0][n], dumps[1][n]), n
 
 
 @pytest.mark.parametrize("two_streams", ["0", "1"])

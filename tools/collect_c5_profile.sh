@@ -6,7 +6,7 @@ TAG=${1:-r06}
 ROOT=$(pwd); OUT=$ROOT/gpurun_out; mkdir -p $OUT
 export TMPDIR=/tmp
 cd /tmp
-SARSSL_TWO_STREAMS=0 rocprofv3 --kernel-trace --stats -f csv -d $OUT/prof_${TAG}_c5 -o c5 -- python3 $ROOT/bench.py --workload config5 --steps 12 --warmup 3 --no-cpu-baseline --no-product-loop --no-other-mode > $OUT/${TAG}_c5_1stream_line.json 2> $OUT/${TAG}_c5.err
+SARSSL_TWO_STREAMS=0 rocprofv3 --kernel-trace --stats -f csv -d $OUT/prof_${TAG}_c5 -o c5 -- python3 $ROOT/bench.py --full --workload config5 --steps 12 --warmup 3 --no-cpu-baseline --no-product-loop --no-other-mode > $OUT/${TAG}_c5_1stream_line.json 2> $OUT/${TAG}_c5.err
 cd $ROOT
 TRACE=$(find $OUT/prof_${TAG}_c5 -name "*kernel_trace.csv" | head -1)
 [ -n "$TRACE" ] && python3 tools/prof_step.py $TRACE > $OUT/${TAG}_c5_1stream_step_breakdown.txt 2>&1

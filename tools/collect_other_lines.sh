@@ -10,7 +10,7 @@ ROOT=$(pwd); OUT=$ROOT/gpurun_out; mkdir -p $OUT
 export TMPDIR=/tmp
 L=$OUT/${TAG}_other_bench_lines.jsonl
 : > $L
-B="--no-cpu-baseline --no-product-loop --no-other-mode"
+B="--full --no-cpu-baseline --no-product-loop --no-other-mode"
 python3 bench.py --precision fp16 --steps 100 --warmup 5 $B >> $L 2>$OUT/ol_fp16.err
 python3 bench.py --precision fp32 --steps 30 --warmup 3 $B >> $L 2>$OUT/ol_fp32.err
 python3 bench.py --precision bf16 --steps 100 --warmup 5 $B >> $L 2>$OUT/ol_bf16.err
