@@ -94,7 +94,8 @@ int sarssl_gemm(const void* A, const void* B, void* C, int dtA, int dtB, int dtC
 
 /* ---- downstream heads (round 6): SARSSL.forward's downstream branch (code/model.py:667-719: mean over the frames, then
  *      nn.Sequential(LayerNorm, Linear) or (LayerNorm, Linear, ReLU, Linear)) and SARSSL_MultiCH.head_mch (code/model.py:793-821).  f32 tensors
- *      of a few hundred rows at most; LayerNorm = sarssl_layernorm_fwd / _bwd.  sarssl_mean_rows: x (B, Tn, d) of `dtype` -> out f32 (B, d);
+ *      of a few hundred rows at most; LayerNorm = sarssl_layernorm_fwd / _bwd, any d % 4 == 0 (head_mch is LayerNorm(256 * nmic_pair): d > 1024
+ *      from 5 pairs on runs their one-workgroup-per-row path).  sarssl_mean_rows: x (B, Tn, d) of `dtype` -> out f32 (B, d);
  *      _bwd: dx (B, Tn, d) of `dtype` (f32 | bf16) = dy / Tn.  sarssl_small_linear_fwd: y [M][N] = act(x [M][K] W[N][K]^T + bias), act 0 | 1 (relu),
  *      any N >= 1.  _bwd: dx (may be NULL) = dz W, dW += dz^T x, db (may be NULL) += column sums of dz, dz = dy (act 0) or dy * [y > 0] (act 1,
  *      written to dz_ws [M][N]). */
@@ -400,6 +401,9 @@ int sarssl_dwglu_wgrad(const void* dc, const void* h, int nb, int Tn, int d, int
 /* ---- Conformer row / elementwise kernels: LayerNorm (feed_forward.py:48, attention.py:139, convolution.py:137,
  *      Conformer.py:87), GLU (activation.py:31-42), depthwise conv k=31 (convolution.py:140), relative-shift softmax
  *      (attention.py:87-113), u/v bias add (attention.py:87-88) */
+/*      sarssl_layernorm_fwd / _bwd: any d % 4 == 0.  d <= 1024: a wave per row, the row in registers (the encoder's 256 / 512);
+ *      d > 1024: a 256-thread workgroup per row, re-read per pass (the multi-pair head); same f32 statistics, same partials layout and
+ *      workspace.  Every other LayerNorm entry point (_fwd2, _fwd_pair, _fwd2_pair, _bwd_drop, _bwd_stream) takes d <= 1024. */
 int sarssl_layernorm_fwd(const void* x, long ldx, long M, int d, const float* gamma, const float* beta, float eps, void* y,
                          long ldy, float* mean, float* rstd, int dtype, void* stream);
 /* a Conformer block's closing LayerNorm followed by the first LayerNorm of the next block's feed-forward module (Conformer.py:88-90,

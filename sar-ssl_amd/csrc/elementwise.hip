@@ -319,6 +319,99 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const T* __restrict_
         }
     }
 }
+// ---- rows wider than 1024 (sarssl_layernorm_fwd / _bwd only: the multi-pair head's LayerNorm(256 * nmic_pair), a few hundred rows
+// at most - not a hot path).  One 256-thread workgroup per row; thread t owns the float4 columns c4 = t + 256 i, so any d % 4 == 0
+// fits without a register bound.  The row is re-read from global memory (L2) once per pass instead of being held in registers.
+// Sum over the workgroup, the same value in every thread; `red` is 4 floats of LDS, free again when the function returns.
+__device__ __forceinline__ float ln_block_sum(float v, float* red) {
+    v = wave_sum(v);
+    __syncthreads();                                        // earlier readers of red are done
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (red[0] + red[1]) + (red[2] + red[3]);
+}
+// Same formula as layernorm_fwd_kernel: the mean, then the centred sum of squares, then rsqrtf(var + eps), all in f32.
+template <typename T>
+__global__ __launch_bounds__(256) void layernorm_fwd_wide_kernel(const T* __restrict__ x, long ldx, long M, int d,
+                                                                 const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                                 float eps, T* __restrict__ y, long ldy, float* __restrict__ mean,
+                                                                 float* __restrict__ rstd) {
+    __shared__ float red[4];
+    const int nv = d >> 2;
+    for (long row = blockIdx.x; row < M; row += gridDim.x) {
+        const T* xr = x + row * ldx;
+        float s = 0.f;
+        for (int c4 = threadIdx.x; c4 < nv; c4 += 256) { const float4 v = ld4(xr + c4 * 4); s += v.x + v.y + v.z + v.w; }
+        const float mu = ln_block_sum(s, red) / (float)d;
+        float q = 0.f;
+        for (int c4 = threadIdx.x; c4 < nv; c4 += 256) {
+            const float4 v = ld4(xr + c4 * 4);
+            const float a = v.x - mu, b = v.y - mu, c = v.z - mu, e = v.w - mu;
+            q += a * a + b * b + c * c + e * e;
+        }
+        const float rs = rsqrtf(ln_block_sum(q, red) / (float)d + eps);
+        for (int c4 = threadIdx.x; c4 < nv; c4 += 256) {
+            const float4 v = ld4(xr + c4 * 4);
+            const float4 g = *(const float4*)(gamma + c4 * 4), bb = *(const float4*)(beta + c4 * 4);
+            st4(y + row * ldy + c4 * 4, make_float4((v.x - mu) * rs * g.x + bb.x, (v.y - mu) * rs * g.y + bb.y,
+                                                    (v.z - mu) * rs * g.z + bb.z, (v.w - mu) * rs * g.w + bb.w));
+        }
+        if (threadIdx.x == 0 && mean) { mean[row] = mu; rstd[row] = rs; }
+    }
+}
+// dx = rstd * (dy*g - mean(dy*g) - xhat * mean(dy*g*xhat)) (+ resid).  Workgroup b takes rows b, b + gridDim.x, ... and accumulates
+// sum dy*xhat / sum dy of its rows in place in its partial row partial[b][2][d] (its own columns only: no atomics, no barrier); every
+// one of the gridDim.x partial rows is written, zeros included, because the fold reads all of them.
+template <typename T, typename TA>
+__global__ __launch_bounds__(256) void layernorm_bwd_wide_kernel(const T* __restrict__ dy, long lddy, const TA* __restrict__ x, long ldx,
+                                                                 long M, int d, const float* __restrict__ gamma,
+                                                                 const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                                 const T* __restrict__ resid, long ldr, T* __restrict__ dx, long lddx,
+                                                                 float* __restrict__ partial /* [gridDim.x][2][d] or null */) {
+    __shared__ float red[4];
+    const int nv = d >> 2;
+    float* P = partial ? partial + (long)blockIdx.x * 2 * d : nullptr;
+    if (P)
+        for (int c4 = threadIdx.x; c4 < nv; c4 += 256) {
+            *(float4*)(P + c4 * 4) = make_float4(0, 0, 0, 0);
+            *(float4*)(P + d + c4 * 4) = make_float4(0, 0, 0, 0);
+        }
+    for (long row = blockIdx.x; row < M; row += gridDim.x) {
+        const T* dyr = dy + row * lddy;
+        const TA* xr = x + row * ldx;
+        const float mu = mean[row], rs = rstd[row];
+        float s1 = 0.f, s2 = 0.f;
+        for (int c4 = threadIdx.x; c4 < nv; c4 += 256) {
+            const float4 a = ld4(dyr + c4 * 4), xx = ld4(xr + c4 * 4), gm = *(const float4*)(gamma + c4 * 4);
+            const float4 xh = make_float4((xx.x - mu) * rs, (xx.y - mu) * rs, (xx.z - mu) * rs, (xx.w - mu) * rs);
+            const float4 g = make_float4(a.x * gm.x, a.y * gm.y, a.z * gm.z, a.w * gm.w);
+            s1 += g.x + g.y + g.z + g.w;
+            s2 += g.x * xh.x + g.y * xh.y + g.z * xh.z + g.w * xh.w;
+            if (P) {
+                float4 pg = *(const float4*)(P + c4 * 4), pb = *(const float4*)(P + d + c4 * 4);
+                pg.x += a.x * xh.x; pg.y += a.y * xh.y; pg.z += a.z * xh.z; pg.w += a.w * xh.w;
+                pb.x += a.x; pb.y += a.y; pb.z += a.z; pb.w += a.w;
+                *(float4*)(P + c4 * 4) = pg;
+                *(float4*)(P + d + c4 * 4) = pb;
+            }
+        }
+        s1 = ln_block_sum(s1, red) / (float)d;
+        s2 = ln_block_sum(s2, red) / (float)d;
+        for (int c4 = threadIdx.x; c4 < nv; c4 += 256) {
+            const float4 a = ld4(dyr + c4 * 4), xx = ld4(xr + c4 * 4), gm = *(const float4*)(gamma + c4 * 4);
+            const float4 xh = make_float4((xx.x - mu) * rs, (xx.y - mu) * rs, (xx.z - mu) * rs, (xx.w - mu) * rs);
+            const float4 g = make_float4(a.x * gm.x, a.y * gm.y, a.z * gm.z, a.w * gm.w);
+            float4 o = make_float4(rs * (g.x - s1 - xh.x * s2), rs * (g.y - s1 - xh.y * s2),
+                                   rs * (g.z - s1 - xh.z * s2), rs * (g.w - s1 - xh.w * s2));
+            if (resid) {
+                const float4 r = ld4(resid + row * ldr + c4 * 4);
+                o.x += r.x; o.y += r.y; o.z += r.z; o.w += r.w;
+            }
+            st4(dx + row * lddx + c4 * 4, o);
+        }
+    }
+}
+
 // out[i] += sum_p partial[p][i], i < n.  Workgroup = 64 columns x 4 part-slots (4-way unrolled loads), LDS combine.
 __global__ __launch_bounds__(256) void partial_reduce_kernel(const float* __restrict__ partial, int nparts, long n,
                                                              float* __restrict__ out) {
@@ -969,7 +1062,13 @@ __global__ void adam_dev_kernel(float* __restrict__ p, float* __restrict__ g, fl
 // ================================================================================================ C ABI
 extern "C" int sarssl_layernorm_fwd(const void* x, long ldx, long M, int d, const float* gamma, const float* beta, float eps,
                                     void* y, long ldy, float* mean, float* rstd, int dtype, void* stream) {
-    SARSSL_REQUIRE(M > 0 && d > 0 && (d & 3) == 0 && d <= 1024 && (ldx & 3) == 0 && (ldy & 3) == 0, "sarssl_layernorm_fwd");
+    SARSSL_REQUIRE(M > 0 && d > 0 && (d & 3) == 0 && (ldx & 3) == 0 && (ldy & 3) == 0, "sarssl_layernorm_fwd");
+    if (d > 1024) {                 // wider than a wave's registers hold (LN_MAXV): one workgroup per row
+        DISPATCH_T(dtype, (layernorm_fwd_wide_kernel<T><<<nblocks_for(M, 1, 4096), 256, 0, ST>>>((const T*)x, ldx, M, d, gamma, beta, eps,
+                                                                                                 (T*)y, ldy, mean, rstd)));
+        SARSSL_CHECK_LAUNCH("layernorm_fwd_wide_kernel");
+        return 0;
+    }
     static const int rows_kernel = [] { const char* e = getenv("SARSSL_LN_ROWS"); return (e && atoi(e) == 0) ? 0 : 1; }();   // 0: one row per wave (A/B runs)
     if (rows_kernel && (d == 256 || d == 512) && M >= 4096) {
         const int nblk = nblocks_for(M, d == 256 ? 16 : 8, 4096);
@@ -1003,13 +1102,18 @@ extern "C" long sarssl_layernorm_bwd_workspace_bytes(long M, int d) {
 extern "C" int sarssl_layernorm_bwd(const void* dy, long lddy, const void* x, long ldx, long M, int d, const float* gamma,
                                     const float* mean, const float* rstd, const void* resid, long ldr, void* dx, long lddx,
                                     float* dgamma, float* dbeta, float* partial, int dtype, void* stream) {
-    SARSSL_REQUIRE(M > 0 && d > 0 && (d & 3) == 0 && d <= 1024 && (!dgamma || partial), "sarssl_layernorm_bwd");
+    SARSSL_REQUIRE(M > 0 && d > 0 && (d & 3) == 0 && (!dgamma || partial), "sarssl_layernorm_bwd");
     const int nblk = ln_bwd_blocks(M);
     float* part = partial;          // dgamma == null && partial != null: partials only, folded later (sarssl_ln_param_reduce_multi)
+    if (d > 1024) {                 // one workgroup per partial row (layernorm_bwd_wide_kernel), same partials layout and workspace
+        DISPATCH_GA(dtype, (layernorm_bwd_wide_kernel<T, TA><<<nblk, 256, 0, ST>>>((const T*)dy, lddy, (const TA*)x, ldx, M, d, gamma, mean,
+                                                                                   rstd, (const T*)resid, ldr, (T*)dx, lddx, part)));
+    } else {
 #define LN_BWD_LAUNCH(NVv) layernorm_bwd_kernel<T, TA, NVv><<<nblk, 256, 0, ST>>>((const T*)dy, lddy, (const TA*)x, ldx, M, d, gamma, mean, rstd, \
                                                                            (const T*)resid, ldr, (T*)dx, lddx, part)
-    DISPATCH_GA(dtype, (d <= 256 ? LN_BWD_LAUNCH(1) : (d <= 512 ? LN_BWD_LAUNCH(2) : LN_BWD_LAUNCH(4))));
+        DISPATCH_GA(dtype, (d <= 256 ? LN_BWD_LAUNCH(1) : (d <= 512 ? LN_BWD_LAUNCH(2) : LN_BWD_LAUNCH(4))));
 #undef LN_BWD_LAUNCH
+    }
     if (dgamma) {       // partial is [nblk][2][d]: viewed as nblk rows of 2d, column halves go to dgamma / dbeta
         ln_param_reduce_kernel<<<(2 * d + 63) / 64, 1024, 0, ST>>>(part, nblk, d, dgamma, dbeta);
     }
