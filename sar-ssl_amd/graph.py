@@ -55,6 +55,7 @@ class PretrainStepGraph:
         self._plan = None         # the first captured plan (kept under this name for tests / tools)
         self._plans = {}          # full_pred (bool) -> (plan, pred, xin, vis_masks, ecat): the compact step and, captured on first use, the
                                   # step with the decoder / block tails on EVERY frame (the batch whose vis an epoch returns)
+        self._plan_lo = {}        # full_pred (bool) -> the lo shadow the plan's Adam launch rewrites (None: captured before it existed)
         self._key = None
         self._pool = None
         self._stage = []          # ring of (pinned staging buffer, event) for the masks
@@ -163,10 +164,13 @@ class PretrainStepGraph:
         # stricter than the reference in the modes without a GradScaler counterpart (fp32 / bf16, where the reference would let a NaN
         # propagate into the parameters): the captured step never applies an update computed from a non-finite loss, in any mode; the
         # launch-by-launch learner path guards under --use-amp only, like the reference (advisor, round 5: documented, not aligned)
+        lo = self.flat.wl16
         hip.adam_step_dev(self.flat.flat, self.flat.grad, self.m, self.v, self.flat.w16, self.state, gscale=1.0 / world, eps=self.eps,
                           zero_grad=self.zero_grad_in_adam, ph16=self.flat.wh16, guard=guard,
-                          pl16=self.flat.wl16)      # hybrid mode: the weights' fp16 lo shadow is rewritten by the same pass (None otherwise)
-        self.flat._lo_synced = self.flat._synced
+                          pl16=lo)                  # hybrid mode: the weights' fp16 lo shadow is rewritten by the same pass (None otherwise)
+        if lo is not None:
+            self.flat._lo_synced = self.flat._synced
+        self._adam_lo = lo                          # (captured: the lo shadow every replay of this step rewrites - see step())
 
     def _exchange_in_graph(self):
         """True when the bucket all-reduces are captured INSIDE the step graph: the library's own exchange (sarssl_allreduce_bucket,
@@ -273,6 +277,7 @@ class PretrainStepGraph:
         cur.wait_stream(cap)
         torch.cuda.synchronize()
         self._plans[bool(full)] = (seg.plan, self.pred, self.xin, self.vis_masks, self.ecat)
+        self._plan_lo[bool(full)] = self._adam_lo
         if self._plan is None:
             self._plan = seg.plan
             self._key = (tuple(src.shape), src.dtype, RT.dtype, RT.fp8, RT.hybrid, net.training)
@@ -308,6 +313,8 @@ class PretrainStepGraph:
                 self.reducer._on_stage(item)
             else:                                           # "finish": wait for the buckets (stream-side for RCCL) + the collective guard
                 self.reducer.finish(guard=self.guard if self.reducer.world > 1 else None)
+        if self.flat.wl16 is not None and self._plan_lo.get(full_pred) is not self.flat.wl16:
+            self.flat.refresh_lo()                         # captured before the hybrid mode allocated the lo shadow: rewrite it behind the step
         runtime.bump_version()                             # weights moved: eager users of the re-laid-out caches must rebuild
         self.nsteps += 1
         return self.out

@@ -271,6 +271,7 @@ class FlatParams:
             self.wl16 = torch.zeros(self.numel, dtype=torch.float16, device=self.flat.device)
             for p, o in zip(self.params, self.offsets):
                 p._wl16 = self.wl16[o:o + p.numel()].view(p.shape)
+            self._lo_synced = None             # just allocated: holds nothing yet, whatever the optimiser steps before recorded
         if self._lo_synced != self._synced:
             self.refresh_lo()
 
@@ -357,5 +358,6 @@ class FusedAdam:
                       gscale=grad_scale, betas=self.betas, eps=self.eps, ph16=self.flat.wh16,
                       guard=guard.detach().reshape(-1) if guard is not None else None, nskipped=self.nskipped if guard is not None else None,
                       pl16=self.flat.wl16)     # (hybrid mode: the lo shadow is rewritten by the same pass; None otherwise)
-        self.flat._lo_synced = self.flat._synced
+        if self.flat.wl16 is not None:         # (a pass without the lo shadow leaves nothing in sync: ensure_lo refreshes it on first use)
+            self.flat._lo_synced = self.flat._synced
         bump_version()

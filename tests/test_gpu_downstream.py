@@ -15,8 +15,8 @@ pytestmark = pytest.mark.gpu
 
 TOL = {"fp32": dict(loss=1e-3, pred=2e-3, grad=2e-3, epoch=2e-3),        # north_star tolerance on the f32 (split-bf16) path
        "bf16": dict(loss=2.5e-2, pred=5e-2, grad=1.2e-1, epoch=5e-2),    # bf16 storage: 2.5-5x measured (5.1e-3, 1.4e-2, 4.5e-2)
-       "fp16": dict(loss=1e-2, pred=2e-2, grad=6e-2, epoch=2e-2),
-       "hybrid": dict(loss=1e-2, pred=2e-2, grad=6e-2, epoch=2e-2)}        # fp16 forward / bf16 backward: 4-5x measured (2.1e-3, 4.9e-3, 1.5e-2)
+       "fp16": dict(loss=1e-2, pred=2e-2, grad=6e-2, epoch=2e-2),        # fp16 forward / bf16 backward: 4-5x measured (2.1e-3, 4.9e-3, 1.5e-2)
+       "hybrid": dict(loss=9.4e-4, pred=5.9e-3, grad=3.1e-2, epoch=2e-2)}  # 2.5x measured (3.8e-4, 2.4e-3, 1.25e-2); epoch: fp32 runs only
 
 
 def _set_dropout(m, p):

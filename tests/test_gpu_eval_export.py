@@ -60,7 +60,8 @@ def test_stft_istft_round_trip_full_size():
 def test_pretest_epoch_with_eval_vs_reference(prec):
     from sar_ssl_amd import learner, model, runtime
     z = _z()
-    tol = {"fp32": (1e-3, 1e-3), "bf16": (1e-3, 2e-2), "fp16": (1e-3, 3e-3), "hybrid": (1e-3, 3e-3)}[prec]                    # bf16: 3-5x measured (2.1e-4, 6.3e-3)
+    tol = {"fp32": (1e-3, 1e-3), "bf16": (1e-3, 2e-2), "fp16": (1e-3, 3e-3),                    # bf16: 3-5x measured (2.1e-4, 6.3e-3)
+           "hybrid": (1.4e-5, 8.5e-4)}[prec]                                             # hybrid: 2.5x measured (5.8e-6, 3.4e-4)
     try:
         man = json.load(open(os.path.join(GOLD, "state_dict_manifest.json")))["pretrain"]
         net = model.SARSSL(sig_shape=(256, 256, 2, 2), pretrain=True, device="cuda:0")

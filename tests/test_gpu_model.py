@@ -258,10 +258,7 @@ def test_downstream_forward():
         runtime.set_precision("bf16")
 
 
-@pytest.mark.parametrize("prec", ["fp32", "bf16", "fp16"])
-def test_reloaded_weights_are_picked_up_without_flat_params(prec):
-    """Re-laid-out weight caches (3x3 taps, patch-GEMM weight, bf16 shadows) must follow ``load_state_dict`` / in-place updates on a
-    model that is NOT flattened: forward -> load_state_dict -> forward equals a fresh model carrying the second weights."""
+def _reload_check(prec, flatten):
     from sar_ssl_amd import model, runtime
     runtime.set_precision(prec)
     try:
@@ -272,6 +269,8 @@ def test_reloaded_weights_are_picked_up_without_flat_params(prec):
                                         device="cuda")
         x = torch.from_numpy(z["embed_encoder.x"]).to(dev)
         a = mk(); a.load_state_dict(recipes.recipe_state_dict(meta, 27)); a.to(dev).eval()
+        if flatten:
+            runtime.FlatParams(a)
         with torch.no_grad():
             y_first = a(x).float().clone()
             a.load_state_dict(recipes.recipe_state_dict(meta, 31))
@@ -280,6 +279,8 @@ def test_reloaded_weights_are_picked_up_without_flat_params(prec):
                 p.mul_(1.25)
             y_third = a(x).float().clone()
         b = mk(); b.load_state_dict(recipes.recipe_state_dict(meta, 31)); b.to(dev).eval()
+        if flatten:
+            runtime.FlatParams(b)
         with torch.no_grad():
             want_second = b(x).float().clone()
             for p in b.parameters():
@@ -289,6 +290,20 @@ def test_reloaded_weights_are_picked_up_without_flat_params(prec):
         assert torch.equal(y_second, want_second) and torch.equal(y_third, want_third)
     finally:
         runtime.set_precision("bf16")
+
+
+@pytest.mark.parametrize("prec", ["fp32", "bf16", "fp16", "hybrid"])
+def test_reloaded_weights_are_picked_up_without_flat_params(prec):
+    """Re-laid-out weight caches (3x3 taps, patch-GEMM weight, bf16 / fp16 / lo shadows) must follow ``load_state_dict`` / in-place updates on
+    a model that is NOT flattened: forward -> load_state_dict -> forward equals a fresh model carrying the second weights."""
+    _reload_check(prec, flatten=False)
+
+
+@pytest.mark.parametrize("prec", ["fp32", "bf16", "fp16", "hybrid"])
+def test_reloaded_weights_are_picked_up_with_flat_params(prec):
+    """The same through runtime.FlatParams: the flat buffer's shadows (and, in the hybrid mode, its lo shadow) are refreshed at the next
+    forward after a load_state_dict or an in-place update."""
+    _reload_check(prec, flatten=True)
 
 
 # ---------------------------------------------------------------- inputs at the edge of the front-end's normalisation (fixture F15)

@@ -36,7 +36,8 @@ def test_config5_ten_second_four_mic_segment(prec):
     """T = 624 is not a multiple of the conv tile (64) or the GEMM tile: ragged tiles everywhere."""
     from sar_ssl_amd import hip, model, runtime
     z = _z()
-    tol = {"fp32": (1e-3, 1e-3, 5e-3), "bf16": (1e-3, 3e-2, 6e-2), "fp16": (1e-3, 4e-3, 4e-2), "hybrid": (1e-3, 4e-3, 4e-2)}[prec]       # bf16: 3-5x measured (5.3e-5, 1.0e-2, 1.9e-2)
+    tol = {"fp32": (1e-3, 1e-3, 5e-3), "bf16": (1e-3, 3e-2, 6e-2), "fp16": (1e-3, 4e-3, 4e-2),       # bf16: 3-5x measured (5.3e-5, 1.0e-2, 1.9e-2)
+           "hybrid": (1.9e-6, 1e-3, 2e-2)}[prec]          # hybrid: 2.5x measured loss / gradnorm (7.8e-7, 8.1e-3); pred: the 1e-3 class (measured 8.6e-4, fp16 1.4e-3)
     runtime.set_precision(prec)
     try:
         man = json.load(open(os.path.join(GOLD, "state_dict_manifest.json")))["pretrain"]
