@@ -1082,11 +1082,6 @@ extern "C" int sarssl_relpos_attn_fwd(const void* qu, long ldq, const void* k, c
 // The same forward with the shifted positional score formed inside the kernel (attention.py:87-89 + 105-113 fused): qv = q + v_bias
 // [B*T][ldq], pos = positional projection [T][ldp] (head h at column h*dh).  bias_out (optional, (B,H,T,T)) receives the shifted score
 // for backward kernels that read it.  T <= 256, T % 8 == 0 (sarssl_relpos_attn_pos_supported).
-static int sarssl_attn_fwd_waves() {          // SARSSL_ATTN_FWD_WAVES=4: the four-wave forward for d_head 64 as well (A/B runs)
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("SARSSL_ATTN_FWD_WAVES"); v = (e && atoi(e) == 4) ? 4 : 8; }
-    return v;
-}
 extern "C" int sarssl_relpos_attn_pos_supported(int T, int dh) { return (T > 0 && T <= 256 && T % 8 == 0 && (dh == 32 || dh == 64 || dh == 128)) ? 1 : 0; }
 // u_bias / v_bias (both or neither; f32 [H*dh]): qu and qv are then the SAME plain query projection q and the kernels form q + u / q + v
 // while loading (the values sarssl_bias2 would have stored).
@@ -1104,7 +1099,7 @@ static int attn_fwd_pos_impl(const void* qu, const void* qv, long ldq, const voi
     a.ctx = (h16*)ctx; a.ldc = ldc; a.ctx32 = ctx32; a.lse = lse; a.B = B; a.H = H; a.T = T; a.scale = scale; a.p_drop = p_drop; a.seed = seed; a.salt = sarssl_dropout_salt();
     dim3 grid((T + 127) / 128, B * H);
     hipStream_t st = (hipStream_t)stream;
-    if (dh == 64 && T > 128 && sarssl_attn_fwd_waves() == 8) {        // all 256 query rows of a (batch, head) in one eight-wave workgroup
+    if (dh == 64 && T > 128) {        // all 256 query rows of a (batch, head) in one eight-wave workgroup
         dim3 grid8(1, B * H);
         if (dtype == SARSSL_F16) relpos_attn_fwd_kernel<64, f16, true, 8><<<grid8, 512, 0, st>>>(a);
         else relpos_attn_fwd_kernel<64, bf16, true, 8><<<grid8, 512, 0, st>>>(a);

@@ -1435,194 +1435,17 @@ __global__ __launch_bounds__(512) void conv3x3_wgrad_kernel(WgradArgs a) {
     }
 }
 
-// ---- weight gradient, double-buffered variant (bf16).  In conv3x3_wgrad_kernel all eight waves stage, barrier, run their MFMAs,
-// barrier: the matrix pipe idles for the whole staging phase (one tile = ~25 k cycles of which 2 x 5.1 k are MFMA, mfma_busy 0.38 in
-// the round-2 counters) and the 150 KB of one 8 x 64-pixel tile pair leave no room for a second buffer.  Here the tile is 8 x 32 pixels
-// (z halo 43.5 KB + dy 32.8 KB), LDS holds TWO of them, the next tile is written into the other buffer right behind this tile's
-// MFMAs and there is ONE barrier per tile; the waves of a SIMD drift against each other inside a tile, so one wave's staging (VALU,
-// LDS writes) runs under the other's MFMAs.  Same wave roles / accumulators / partial-sum output as conv3x3_wgrad_kernel.
+// ---- weight gradient, double-buffered role-split kernel (bf16).  In conv3x3_wgrad_kernel all eight waves stage, barrier, run their
+// MFMAs, barrier: the matrix pipe idles for the whole staging phase (one tile = ~25 k cycles of which 2 x 5.1 k are MFMA, mfma_busy 0.38
+// in the round-2 counters) and the 150 KB of one 8 x 64-pixel tile pair leave no room for a second buffer.  Here the tile is 8 x 32 pixels
+// (z halo 43.5 KB + dy 32.8 KB) and LDS holds TWO of them.  16 waves: waves 0-7 only run the MFMA loop (the decomposition of
+// conv3x3_wgrad_kernel: co half x ci half x tap group, same accumulators / partial-sum output), waves 8-15 only stage (global loads one
+// tile ahead in registers, BatchNorm + ReLU / first-layer prologue, LDS writes).  Ablation builds of its lockstep predecessor (all waves
+// in both roles, removed) ran 254 us without its staging and 268 us without its MFMAs, 378 us with both in the same waves.
 #define WTC 32
 #define WHC (WTC + 2)
 #define WX_ELEMS (HR * WHC * 64)
 #define WY_ELEMS (TR * WTC * 64)
-template <bool C1IN = false, typename TA = bf16>      // TA: encoding of the saved forward operand (zin / a0); dy and the contraction are bf16
-__global__ __launch_bounds__(512) void conv3x3_wgrad_db_kernel(WgradArgs a) {
-    typedef bf16 T;
-    __shared__ __attribute__((aligned(16))) uint16_t sYb[2][WY_ELEMS];   // dy tiles  [8*32 px][64 co]
-    __shared__ __attribute__((aligned(16))) uint16_t sXb[2][WX_ELEMS];   // z halo tiles [340 px][64 ci]
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wi = wave & 1, wj = (wave >> 1) & 1, wt = wave >> 2;     // co half, ci half, tap group
-    const int tap0 = wt ? 5 : 0, ntap = wt ? 4 : 5;
-    const int F = a.F, Tn = a.T;
-    const int tiles_f = (F + TR - 1) / TR, tiles_t = (Tn + WTC - 1) / WTC;
-    const int ntiles = a.nb * tiles_f * tiles_t;
-    const TA* zin = (const TA*)a.zin;
-    const T* dy = (const T*)a.dy;
-    const int cch = tid & 7;
-
-    f32x16 acc[5];
-#pragma unroll
-    for (int t9 = 0; t9 < 5; ++t9)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[t9][r] = 0.f;
-
-    int baseA[2], baseB[5][2];
-    {
-        const int chA = wi * 32 + 16 * ((lane >> 4) & 1) + (lane & 3) * 4, chB = wj * 32 + 16 * ((lane >> 4) & 1) + (lane & 3) * 4;
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int loff = (lane >> 5) * 8 + h * 4 + ((lane & 15) >> 2);
-            baseA[h] = swzc(loff, loff, chA >> 3) + (chA & 7);
-#pragma unroll
-            for (int tt = 0; tt < 5; ++tt) {
-                const int tap = tap0 + (tt < ntap ? tt : 0);
-                const int kh = tap / 3, kw = tap - kh * 3;
-                baseB[tt][h] = swzc(kh * WHC + kw + loff, kw + loff, chB >> 3) + (chB & 7);
-            }
-        }
-    }
-    float sc[8], sh[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { sc[e] = a.prologue ? a.scale[cch * 8 + e] : 1.f; sh[e] = a.prologue ? a.shift[cch * 8 + e] : 0.f; }
-    C1Const kc1;
-    if (C1IN) c1_setup(kc1, a.c1_w, a.scale, a.shift, cch * 8);
-    auto load_z = [&](int b, int f, int t) {                    // clamped, unconditional (load_chunk_clamped); C1IN: the pixel's 4 input channels
-        Chunk<TA> c;
-        if (C1IN) {
-            f = min(max(f, 0), F - 1); t = min(max(t, 0), Tn - 1);
-            const uint2 q = *(const uint2*)(zin + (((long)b * F + f) * Tn + t) * 4);
-            c.u.x = q.x; c.u.y = q.y;
-        } else c = load_chunk_clamped<TA>(zin, b, f, t, F, Tn, cch * 8);
-        return c;
-    };
-    auto xform_z = [&](const Chunk<TA>& c, bool ok) { return C1IN ? c1_chunk<TA, bf16>(c.u.x, c.u.y, ok, kc1) : xform_chunk<TA, bf16>(c, ok, a.prologue, sc, sh, 0); };
-
-    // staging: thread = (row parity pr, pixel column pcol of 32, 8-channel chunk): halo rows pr, pr+2, .. pr+8 and dy rows pr, pr+2, ..
-    // pr+6 of its column; threads < 160 also one chunk of halo columns 32 / 33
-    // (round 3: ~1100 vector instructions per wave and tile, a third of them addresses - 64-bit products per load, the LDS swizzle per
-    //  store.  The row parity is wave-uniform, so row bases live on the scalar unit: one 64-bit image base per tile + 32-bit row offsets,
-    //  one vector byte offset per thread for all rows of a tensor, one lane-constant LDS base per tensor with the row step as an
-    //  immediate: 1426 -> 1019 vector issue slots per tile.  The launch time did not move (379 us alone, +0.2 % on the step): like the
-    //  operand-read and look-ahead experiments in tools/conv_ng3/, it says this kernel is bound by none of them.)
-    Chunk<TA> rz[6]; Chunk<T> ry[4];
-    const int pcol = (tid >> 3) & 31;
-    const int pr = __builtin_amdgcn_readfirstlane(tid >> 8);
-    const int lbX = swzc(pr * WHC + pcol, pcol, cch), lbY = swzc(pr * WTC + pcol, pcol, cch);     // LDS element offsets of row pr; row pr + 2k: + k * 2 * W?C * 64
-    auto coord = [&](int tile) { TileCoord c; c.t0 = (tile % tiles_t) * WTC; tile /= tiles_t; c.f0 = (tile % tiles_f) * TR; c.b = tile / tiles_f; return c; };
-    auto issue_loads = [&](const TileCoord tc) {
-        constexpr unsigned PXB = C1IN ? 8u : 128u;                               // bytes per pixel of zin
-        const char* zimg = (const char*)zin + (long)tc.b * F * (long)Tn * PXB;   // (an image is < 4 GB: 32-bit offsets inside it)
-        const char* yimg = (const char*)dy + (long)tc.b * F * (long)Tn * 128;
-        const unsigned zrow = (unsigned)Tn * PXB, yrow = (unsigned)Tn * 128u;
-        const int tz = min(max(tc.t0 - 1 + pcol, 0), Tn - 1), ty = min(tc.t0 + pcol, Tn - 1);      // clamped: unconditional loads
-        const unsigned vz = C1IN ? (unsigned)tz * 8u : (unsigned)(tz * 64 + cch * 8) * 2u, vy = (unsigned)(ty * 64 + cch * 8) * 2u;
-#pragma unroll
-        for (int k = 0; k < 5; ++k) {
-            const int f = min(max(tc.f0 - 1 + pr + 2 * k, 0), F - 1);
-            const char* prow = zimg + (unsigned)f * zrow;
-            if (C1IN) { const uint2 q = *(const uint2*)(prow + vz); rz[k].u.x = q.x; rz[k].u.y = q.y; }
-            else rz[k].u = *(const uint4*)(prow + vz);
-        }
-        {
-            const int q = tid >> 3, hr = q >> 1, te = tc.t0 + WTC - 1 + (q & 1);        // (threads >= 160: an unused, harmless extra chunk)
-            rz[5] = load_z(tc.b, tc.f0 - 1 + hr, te);
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int f = min(tc.f0 + pr + 2 * k, F - 1);
-            ry[k].u = *(const uint4*)(yimg + (unsigned)f * yrow + vy);
-        }
-    };
-    // the tile is written in three pieces (halo rows 0-2 of this thread | halo rows 3-4 + edge columns | dy rows) so that the pieces can be
-    // placed between the row iterations of the PREVIOUS tile's MFMA loop
-    auto write_piece = [&](const int piece, const TileCoord tc, uint16_t* __restrict__ sX, uint16_t* __restrict__ sY) {
-        if (piece < 2) {
-            const int t = tc.t0 - 1 + pcol;
-            const bool tv = t >= 0 && t < Tn;
-#pragma unroll
-            for (int k = 0; k < 5; ++k) {
-                if ((piece == 0) != (k < 3)) continue;
-                const int f = tc.f0 - 1 + pr + 2 * k;
-                *(uint4*)&sX[lbX + k * (2 * WHC * 64)] = xform_z(rz[k], tv && f >= 0 && f < F);
-            }
-            if (piece == 1 && tid < 160) {
-                const int q = tid >> 3, hr = q >> 1, f = tc.f0 - 1 + hr, te = tc.t0 + WTC - 1 + (q & 1);
-                *(uint4*)&sX[swzc(hr * WHC + WTC + (q & 1), WTC + (q & 1), cch)] = xform_z(rz[5], f >= 0 && f < F && te < Tn);
-            }
-        } else {
-            const int ty = tc.t0 + pcol;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                *(uint4*)&sY[lbY + k * (2 * WTC * 64)] = xform_chunk<T>(ry[k], tc.f0 + pr + 2 * k < F && ty < Tn, 0, sc, sh, 0);
-            }
-        }
-    };
-    auto write_tile = [&](const TileCoord tc, uint16_t* __restrict__ sX, uint16_t* __restrict__ sY) {
-        write_piece(0, tc, sX, sY); write_piece(1, tc, sX, sY); write_piece(2, tc, sX, sY);
-    };
-
-    const int nrounds = (ntiles + gridDim.x - 1) / gridDim.x;
-    int tile = xcd_tile(0, blockIdx.x, gridDim.x);
-    TileCoord tc = coord(tile < ntiles ? tile : 0);
-    if (tile < ntiles) {
-        issue_loads(tc);
-        write_tile(tc, sXb[0], sYb[0]);
-    }
-    __syncthreads();
-    int cur = 0;
-    for (int it = 0; it < nrounds; ++it) {
-        if (tile >= ntiles) break;
-        const int next = (it + 1 < nrounds) ? xcd_tile(it + 1, blockIdx.x, gridDim.x) : ntiles;
-        const TileCoord tcn = coord(next < ntiles ? next : 0);
-        if (next < ntiles) issue_loads(tcn);
-        const uint16_t* sX = sXb[cur];
-        const uint16_t* sY = sYb[cur];
-#pragma unroll
-        for (int r = 0; r < TR; ++r) {
-            const uint16_t* ya[2] = {sY + baseA[0] + r * (WTC * 64), sY + baseA[1] + r * (WTC * 64)};
-            const uint16_t* xb[5][2];
-#pragma unroll
-            for (int tt = 0; tt < 5; ++tt) { xb[tt][0] = sX + baseB[tt][0] + r * (WHC * 64); xb[tt][1] = sX + baseB[tt][1] + r * (WHC * 64); }
-#pragma unroll
-            for (int cb = 0; cb < WTC / 16; ++cb) {
-                const int co_ = cb * 16 * 64;                  // 16 pixels x 64 channels further on
-                const bf16x8 fa = tr_pair(ya[0] + co_, ya[1] + co_);
-                bf16x8 fb[2];
-                fb[0] = tr_pair(xb[0][0] + co_, xb[0][1] + co_);
-#pragma unroll
-                for (int tt = 0; tt < 5; ++tt) {
-                    if (tt + 1 < 5 && tt + 1 < ntap) fb[(tt + 1) & 1] = tr_pair(xb[tt + 1][0] + co_, xb[tt + 1][1] + co_);
-                    __builtin_amdgcn_sched_barrier(0);         // pin the next tap's transpose reads above this MFMA
-                    if (tt < ntap) acc[tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa, fb[tt & 1], acc[tt], 0, 0, 0);
-                }
-            }
-            // next tile -> the other buffer, in pieces behind the later rows (its loads were issued before this tile's first MFMA and
-            // have had rows 0-4 to land): this wave's VALU / LDS-write work runs under the MFMAs it has just queued and the other
-            // wave's on the same SIMD
-            if (next < ntiles && r >= 5) write_piece(r - 5, tcn, sXb[cur ^ 1], sYb[cur ^ 1]);
-        }
-        __syncthreads();
-        cur ^= 1; tile = next; tc = tcn;
-    }
-    float* P = a.partial + (long)blockIdx.x * W_ELEMS;
-#pragma unroll
-    for (int tt = 0; tt < 5; ++tt) {
-        if (tt < ntap) {
-            const int tap = tap0 + tt;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int co = wi * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                const int ci = wj * 32 + (lane & 31);
-                P[(tap * 64 + co) * 64 + ci] = acc[tt][r];
-            }
-        }
-    }
-}
-
-// Role-split variant of conv3x3_wgrad_db_kernel: 16 waves, waves 0-7 only run the MFMA loop (same decomposition: co half x ci half x tap
-// group), waves 8-15 only stage (global loads one tile ahead in registers, BatchNorm + ReLU / first-layer prologue, LDS writes).  Ablation
-// builds of the lockstep kernel ran 254 us without its staging and 268 us without its MFMAs, 378 us with both in the same waves.
 template <bool C1IN = false, typename TA = bf16>
 __global__ __launch_bounds__(1024) void conv3x3_wgrad_ws_kernel(WgradArgs a) {
     typedef bf16 T;
@@ -1835,8 +1658,8 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
     }
 }
 
-// Workgroups of the persistent convolution launches.  kind 0 = forward launches, 1 = data / weight gradients.  One per CU, or
-// SARSSL_CONV_CUS[_FWD | _BWD] of them: a convolution workgroup takes a CU's whole LDS and nearly all of its registers, so while a
+// Workgroups of the persistent convolution launches.  kind 0 = forward launches, 1 = data / weight gradients.  One per CU, or fewer:
+// a convolution workgroup takes a CU's whole LDS and nearly all of its registers, so while a
 // launch covers every CU the other encoder's stream stands still; a launch that leaves an eighth of the CUs free lets that stream's
 // short latency-bound kernels run next to it (measured on the step, see NOTES.md 4.7).  The grid is then trimmed so that the last
 // round of tiles is as full as the others (a multiple of 8 keeps the XCD-aware tile order).
@@ -1844,14 +1667,10 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
 // stem backward that runs LAST - alone on the chip, the other encoder's stream has drained - all CUs (sarssl_ctx_set_conv_cus).
 static int conv_cus_override() { const sarssl_ctx* c = sarssl_current(); return c ? c->conv_cus_bwd : 0; }     // (sarssl_ctx_set_conv_cus)
 static int conv_cus(int kind) {
-    static const int lim[2] = {
-        []() { const char* e = getenv("SARSSL_CONV_CUS_FWD"); if (!e) e = getenv("SARSSL_CONV_CUS"); return e ? atoi(e) : 0; }(),
-        []() { const char* e = getenv("SARSSL_CONV_CUS_BWD"); if (!e) e = getenv("SARSSL_CONV_CUS"); return e ? atoi(e) : 0; }()};
     const int ncu = sarssl_cu_count();
     const int ovr = conv_cus_override();
     if (kind == 1 && ovr > 0) return ovr < ncu ? ovr : ncu;
-    if (lim[kind] > 0) return lim[kind] < ncu ? lim[kind] : ncu;
-    // default: forward launches on every CU, gradient launches on 7/8 of them (same-box A/B at B = 64, three rounds: 5 510 - 5 750
+    // forward launches on every CU, gradient launches on 7/8 of them (same-box A/B at B = 64, three rounds: 5 510 - 5 750
     // segments/s with 256 of 256, 5 736 - 5 750 with 224 - the step gains ~2 % although each gradient launch alone is ~12 % slower)
     return kind == 1 && ncu >= 64 ? (ncu * 7 / 8) & ~7 : ncu;
 }
@@ -1864,16 +1683,11 @@ extern "C" long sarssl_wall_clock_khz() {
     if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, 0) != hipSuccess) return 0;
     return (long)khz;
 }
-// forward / data-gradient kernel: the ping-pong kernel, or (SARSSL_CONV_WS=1) its role-split variant
-// Which launches take it (SARSSL_CONV_WS, bit mask: 1 plain forward / data gradient, 2 forward from the 4-channel input, 4 data gradient
-// consumed in its epilogue, 8 data gradient + BatchNorm sums; default 4).  In-step launch times, ping-pong -> role-split, same box:
+// forward / data-gradient kernel: the ping-pong kernel; the data gradient consumed in its epilogue takes the role-split variant.
+// In-step launch times, ping-pong -> role-split, same box:
 // BatchNorm-prologue forward 0.298 -> 0.314 ms and 4-channel-input forward 0.351 -> 0.350 (one 4-wave staging team serves both groups:
 // with a prologue to compute it becomes the bottleneck), data gradient + BatchNorm sums 0.361 -> 0.56 (80 B of scratch at the 168-register
 // cap), data gradient consumed in its epilogue (identity prologue, no output drain) 0.345 -> **0.314**: step 10.72 -> 10.68 ms.
-static bool conv_ws(int variant_bit) {
-    static const int mask = []() { const char* e = getenv("SARSSL_CONV_WS"); return e ? atoi(e) : 4; }();
-    return (mask & variant_bit) != 0;
-}
 static int conv_persistent_grid(int nunits, int kind) {
     const int cus = conv_cus(kind);
     if (nunits <= cus) return nunits;
@@ -1931,10 +1745,7 @@ extern "C" int sarssl_conv3x3_fwd_c1(const void* a0, const float* W1, const floa
     a.in = a0; a.w = w; a.out = out; a.scale = scale; a.shift = shift; a.prologue = 1; a.c1_w = W1;
     a.nb = nb; a.F = F; a.T = T;
     const int npairs = (nb * ((F + TR - 1) / TR) * ((T + PTC - 1) / PTC) + 1) / 2;
-    if (dtype == SARSSL_F16) {
-        if (conv_ws(2)) conv3x3_fwd_ws_kernel<false, true, false, f16><<<conv_persistent_grid(npairs, 0), 768, 0, (hipStream_t)stream>>>(a);
-        else conv3x3_fwd_pp_kernel<false, true, false, f16><<<conv_persistent_grid(npairs, 0), 512, 0, (hipStream_t)stream>>>(a);
-    } else if (conv_ws(2)) conv3x3_fwd_ws_kernel<false, true><<<conv_persistent_grid(npairs, 0), 768, 0, (hipStream_t)stream>>>(a);
+    if (dtype == SARSSL_F16) conv3x3_fwd_pp_kernel<false, true, false, f16><<<conv_persistent_grid(npairs, 0), 512, 0, (hipStream_t)stream>>>(a);
     else conv3x3_fwd_pp_kernel<false, true><<<conv_persistent_grid(npairs, 0), 512, 0, (hipStream_t)stream>>>(a);
     SARSSL_CHECK_LAUNCH("conv3x3_fwd_pp_kernel<c1in>");
     return 0;
@@ -1959,12 +1770,9 @@ extern "C" int sarssl_conv3x3_dgrad_c1red(const void* dy, const void* w, const v
     a.in = dy; a.w = w; a.out = nullptr; a.scale = scale; a.shift = shift; a.prologue = 0; a.c1_w = W1; a.c1_a0 = a0; a.c1_red = red;
     a.nb = nb; a.F = F; a.T = T;
     const int npairs = (nb * ((F + TR - 1) / TR) * ((T + PTC - 1) / PTC) + 1) / 2;
-    if (a0_dtype == SARSSL_F16) {
-        if (conv_ws(4)) conv3x3_fwd_ws_kernel<false, false, true, bf16, f16><<<conv_persistent_grid(npairs, 1), 768, 0, (hipStream_t)stream>>>(a);
-        else conv3x3_fwd_pp_kernel<false, false, true, bf16, f16><<<conv_persistent_grid(npairs, 1), 512, 0, (hipStream_t)stream>>>(a);
-    } else if (conv_ws(4)) conv3x3_fwd_ws_kernel<false, false, true><<<conv_persistent_grid(npairs, 1), 768, 0, (hipStream_t)stream>>>(a);
-    else conv3x3_fwd_pp_kernel<false, false, true><<<conv_persistent_grid(npairs, 1), 512, 0, (hipStream_t)stream>>>(a);
-    SARSSL_CHECK_LAUNCH("conv3x3_fwd_pp_kernel<c1red>");
+    if (a0_dtype == SARSSL_F16) conv3x3_fwd_ws_kernel<false, false, true, bf16, f16><<<conv_persistent_grid(npairs, 1), 768, 0, (hipStream_t)stream>>>(a);
+    else conv3x3_fwd_ws_kernel<false, false, true><<<conv_persistent_grid(npairs, 1), 768, 0, (hipStream_t)stream>>>(a);
+    SARSSL_CHECK_LAUNCH("conv3x3_fwd_ws_kernel<c1red>");
     return 0;
 }
 
@@ -1990,19 +1798,14 @@ static int conv3x3_launch(const void* in, const void* w, void* out, int dtype, i
     if (dtype == SARSSL_BF16 && w_dtype == SARSSL_BF16) {
         const int npairs = (nb * ((F + TR - 1) / TR) * ((T + PTC - 1) / PTC) + 1) / 2;
         const int g = conv_persistent_grid(npairs, scale != nullptr ? 0 : 1);      // (no prologue = a data-gradient launch)
-        if (bn_y && y_dtype == SARSSL_F16) {
-            if (conv_ws(8)) conv3x3_fwd_ws_kernel<true, false, false, bf16, f16><<<g, 768, 0, st>>>(a);
-            else conv3x3_fwd_pp_kernel<true, false, false, bf16, f16><<<g, 512, 0, st>>>(a);
-        } else if (bn_y && conv_ws(8)) conv3x3_fwd_ws_kernel<true><<<g, 768, 0, st>>>(a);
-        else if (!bn_y && conv_ws(1)) conv3x3_fwd_ws_kernel<false><<<g, 768, 0, st>>>(a);
+        if (bn_y && y_dtype == SARSSL_F16) conv3x3_fwd_pp_kernel<true, false, false, bf16, f16><<<g, 512, 0, st>>>(a);
         else if (bn_y) conv3x3_fwd_pp_kernel<true><<<g, 512, 0, st>>>(a);
         else conv3x3_fwd_pp_kernel<false><<<g, 512, 0, st>>>(a);
     } else if (dtype == SARSSL_F16 && w_dtype == SARSSL_F16) {              // forward launches of the fp16-forward mode
         SARSSL_REQUIRE(bn_y == nullptr, "sarssl_conv3x3_fwd(fp16: forward launches only)");
         const int npairs = (nb * ((F + TR - 1) / TR) * ((T + PTC - 1) / PTC) + 1) / 2;
         const int g = conv_persistent_grid(npairs, scale != nullptr ? 0 : 1);
-        if (conv_ws(1)) conv3x3_fwd_ws_kernel<false, false, false, f16><<<g, 768, 0, st>>>(a);
-        else conv3x3_fwd_pp_kernel<false, false, false, f16><<<g, 512, 0, st>>>(a);
+        conv3x3_fwd_pp_kernel<false, false, false, f16><<<g, 512, 0, st>>>(a);
     } else if (dtype == SARSSL_F32 && w_dtype == SARSSL_F32) {
         if (!precise) conv3x3_fwd_kernel<float, float><<<grid, 512, 0, st>>>(a);
         else {
@@ -2019,7 +1822,7 @@ static int conv3x3_launch(const void* in, const void* w, void* out, int dtype, i
 }
 
 extern "C" long sarssl_conv3x3_wgrad_workspace_bytes(int nb, int F, int T) {
-    const int g1 = conv_grid(nb, F, T), g2 = wgrad_db_grid(nb, F, T);          // (either weight-gradient kernel may run)
+    const int g1 = conv_grid(nb, F, T), g2 = wgrad_db_grid(nb, F, T);          // (the f32 or the bf16 weight-gradient kernel may run)
     return (long)(g1 > g2 ? g1 : g2) * W_ELEMS * sizeof(float);
 }
 
@@ -2079,17 +1882,13 @@ extern "C" int sarssl_patch_wgrad_accum(const float* g, int nslice, float* grad,
     return 0;
 }
 
-// bf16 weight gradient: the role-split kernel (16 waves: 8 stage, 8 run the MFMA loop), or with SARSSL_WGRAD_WS=0 (A/B) the lockstep
-// double-buffered one.  Same box, three interleaved rounds, both weight-gradient launches of a stem: 10.87 -> 10.72 ms per step; alone
-// 361 -> 311 us (its MFMA loop alone: 254 us).
+// bf16 weight gradient: the role-split kernel (16 waves: 8 stage, 8 run the MFMA loop).  Against the lockstep double-buffered kernel it
+// replaced - same box, three interleaved rounds, both weight-gradient launches of a stem: 10.87 -> 10.72 ms per step; alone 361 -> 311 us
+// (its MFMA loop alone: 254 us).
 template <bool C1IN>
 static void wgrad_bf16_launch(const WgradArgs& a, int g2, hipStream_t st, bool z_f16) {
-    static const bool ws = []() { const char* e = getenv("SARSSL_WGRAD_WS"); return !(e && atoi(e) == 0); }();
-    if (z_f16) {
-        if (ws) conv3x3_wgrad_ws_kernel<C1IN, f16><<<g2, 1024, 0, st>>>(a);
-        else conv3x3_wgrad_db_kernel<C1IN, f16><<<g2, 512, 0, st>>>(a);
-    } else if (ws) conv3x3_wgrad_ws_kernel<C1IN><<<g2, 1024, 0, st>>>(a);
-    else conv3x3_wgrad_db_kernel<C1IN><<<g2, 512, 0, st>>>(a);
+    if (z_f16) conv3x3_wgrad_ws_kernel<C1IN, f16><<<g2, 1024, 0, st>>>(a);
+    else conv3x3_wgrad_ws_kernel<C1IN><<<g2, 1024, 0, st>>>(a);
 }
 
 extern "C" int sarssl_conv3x3_wgrad(const void* dy, const void* zin, int dtype, int nb, int F, int T,
@@ -2148,6 +1947,6 @@ extern "C" int sarssl_conv3x3_wgrad_c1_acc(const void* dy, const void* a0, const
     const int g2 = wgrad_db_grid(nb, F, T);
     wgrad_bf16_launch<true>(a, g2, st, a0_dtype == SARSSL_F16);
     wgrad_reduce_kernel<<<W_ELEMS / 64, 256, 0, st>>>(partial, g2, nullptr, 0, grad_oihw);
-    SARSSL_CHECK_LAUNCH("conv3x3_wgrad_db_kernel<c1in>");
+    SARSSL_CHECK_LAUNCH("conv3x3_wgrad_ws_kernel<c1in>");
     return 0;
 }

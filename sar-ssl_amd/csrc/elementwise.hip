@@ -1069,8 +1069,7 @@ extern "C" int sarssl_layernorm_fwd(const void* x, long ldx, long M, int d, cons
         SARSSL_CHECK_LAUNCH("layernorm_fwd_wide_kernel");
         return 0;
     }
-    static const int rows_kernel = [] { const char* e = getenv("SARSSL_LN_ROWS"); return (e && atoi(e) == 0) ? 0 : 1; }();   // 0: one row per wave (A/B runs)
-    if (rows_kernel && (d == 256 || d == 512) && M >= 4096) {
+    if ((d == 256 || d == 512) && M >= 4096) {      // four / two rows per wave (bit-identical to the one-row kernel below)
         const int nblk = nblocks_for(M, d == 256 ? 16 : 8, 4096);
         if (d == 256) { DISPATCH_T(dtype, (layernorm_fwd_rows_kernel<T, 256><<<nblk, 256, 0, ST>>>((const T*)x, ldx, M, d, gamma, beta, eps, (T*)y, ldy, mean, rstd))); }
         else { DISPATCH_T(dtype, (layernorm_fwd_rows_kernel<T, 512><<<nblk, 256, 0, ST>>>((const T*)x, ldx, M, d, gamma, beta, eps, (T*)y, ldy, mean, rstd))); }

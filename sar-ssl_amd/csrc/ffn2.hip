@@ -26,7 +26,7 @@
 #include "common.h"
 
 #ifndef FFN_ABL
-#define FFN_ABL 0          // probe builds (tools/bench_ffn2.py --ablate): 1 no activation / dropout math, 2 no tile stores, 4 no weight refills, 8 no MFMAs
+#define FFN_ABL 0          // probe builds (FFN_ABL=<mask> python tools/bench_ffn2.py), timing only, WRONG results: 1 no activation / dropout math, 2 no tile stores, 4 no weight refills, 8 no MFMAs
 #endif
 #define FFN_NT 512
 #define FFN_HC 256

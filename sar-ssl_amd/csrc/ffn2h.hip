@@ -37,11 +37,13 @@ struct Ffn2hArgs {
 
 // ALO: the LayerNorm result enters the first product as a pair (hi hi + lo hi + hi lo; the engine's default); !ALO: its hi half only
 // (hi hi + hi lo) - the first product's OUTPUT is an fp16 tensor, whose own rounding is of the size of what the lo half adds to the
-// per-bin result; the gradients of the f32-stream parameters do see it (engine.py, SARSSL_HYBRID_ALO)
-template <int D, bool ALO, int ABL = 0>
+// per-bin result; the gradients of the f32-stream parameters do see it (engine.py, _H_ALO)
+#ifndef FFN_ABL
+#define FFN_ABL 0          // probe builds (FFN_ABL=<mask> python tools/bench_ffn2.py --hybrid), timing only, WRONG results: 1 no stores of the saved tensors, 2 no MFMAs, 4 no weight refills, 8 no activation arithmetic
+#endif
+template <int D, bool ALO>
 __global__ __launch_bounds__(FFN_NT) void ffn2h_kernel(Ffn2hArgs g) {
-    // ABL (tools/bench_ffn2.py --hybrid, SARSSL_FFN_ABL): ablation builds for timing only - 1: no stores of the saved tensors, 2: no MFMAs,
-    // 4: no weight refills, 8: no activation arithmetic, 16: no LayerNorm arithmetic
+    constexpr int ABL = FFN_ABL;
     constexpr int H = 4 * D, NCH = H / FFN_HC, PA = D + 8, KS1 = D / 16, DB = D / 256;
     constexpr int SA_ELEMS = 64 * PA, ST_ELEMS = 64 * FFN_PH, PY = D + 4;
     constexpr int TILE_ELEMS = (ALO ? 2 : 1) * SA_ELEMS + 2 * ST_ELEMS, YST_ELEMS = 64 * PY * 2;
@@ -329,22 +331,6 @@ extern "C" int sarssl_ffn2h_fwd(const float* x, long ldx, const float* ln_gamma,
     g.p1 = p1; g.p2 = p2; g.s1 = s1; g.s2 = s2; g.salt = sarssl_dropout_salt(); g.out_scale = out_scale; g.M = (int)M;
     g.rot = ffn_rot();
     g.stamps = g_ffn_stamps;
-    static const int abl = [] { const char* e = getenv("SARSSL_FFN_ABL"); return e ? atoi(e) : 0; }();
-    if (abl && act_pair) {
-        const int nb = (int)(M / 64);
-        hipStream_t st = (hipStream_t)stream;
-        switch (abl) {
-            case 1: ffn2h_kernel<256, true, 1><<<nb, FFN_NT, 0, st>>>(g); break;
-            case 2: ffn2h_kernel<256, true, 2><<<nb, FFN_NT, 0, st>>>(g); break;
-            case 4: ffn2h_kernel<256, true, 4><<<nb, FFN_NT, 0, st>>>(g); break;
-            case 6: ffn2h_kernel<256, true, 6><<<nb, FFN_NT, 0, st>>>(g); break;
-            case 8: ffn2h_kernel<256, true, 8><<<nb, FFN_NT, 0, st>>>(g); break;
-            case 9: ffn2h_kernel<256, true, 9><<<nb, FFN_NT, 0, st>>>(g); break;
-            case 15: ffn2h_kernel<256, true, 15><<<nb, FFN_NT, 0, st>>>(g); break;
-            default: SARSSL_REQUIRE(false, "SARSSL_FFN_ABL");
-        }
-        return 0;
-    }
     if (act_pair) ffn2h_kernel<256, true><<<(int)(M / 64), FFN_NT, 0, (hipStream_t)stream>>>(g);
     else ffn2h_kernel<256, false><<<(int)(M / 64), FFN_NT, 0, (hipStream_t)stream>>>(g);
     SARSSL_CHECK_LAUNCH("ffn2h_kernel");

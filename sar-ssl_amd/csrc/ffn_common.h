@@ -3,10 +3,15 @@
 #include <stdlib.h>
 #include "common.h"
 
-// SARSSL_FFN_ROT=0: every workgroup of the fused feed-forward launches walks the hidden chunks from chunk 0 (the order up to round 6)
+// 1: the workgroups of the fused feed-forward launches start their walk over the hidden chunks at different chunks; 0: all from chunk 0
+// (the order up to round 6).  Probe builds (-DSARSSL_PROBE_ENV, tools/ffn_rot_ab.sh) read it from SARSSL_FFN_ROT.
 static inline int ffn_rot() {
+#ifdef SARSSL_PROBE_ENV
     static const int rot = [] { const char* e = getenv("SARSSL_FFN_ROT"); return e ? atoi(e) : 1; }();
     return rot;
+#else
+    return 1;
+#endif
 }
 
 struct FfnDrop {

@@ -7,7 +7,6 @@ push saved tensors on; the ``*_bwd`` twin consumes what was saved, accumulates p
 Reference semantics are cited per function; the math is restated in oracle/sarssl_oracle.py.
 """
 import math
-
 import os
 
 import torch
@@ -21,15 +20,13 @@ RELU, SWISH = 1, 2
 
 
 # ------------------------------------------------------------------------------------------------ GEMM helpers
-def mm_nt(x, W, fp8=False, **kw):
-    """x [M,K] @ W[N,K]^T -> [M,N]   (nn.Linear forward).  (``fp8``: accepted and ignored - the whole-step fp8 mode of rounds 2-5 was removed
-    in round 6: its just-in-time quantisation made the step 7-12 % slower than bf16; the e4m3 GEMM kernels remain library entry points,
-    hip.gemm_fp8 / tests/test_gpu_fp8.py.)"""
+def mm_nt(x, W, **kw):
+    """x [M,K] @ W[N,K]^T -> [M,N]   (nn.Linear forward)."""
     M, K = x.shape
     return hip.gemm(x, W, M=M, N=W.shape[0], K=K, lda=x.stride(0), ldb=W.stride(0), precise=RT.precise, **kw)
 
 
-def mm_nn(dy, W, fp8=False, **kw):
+def mm_nn(dy, W, **kw):
     """dy [M,N] @ W[N,K] -> [M,K]   (input gradient of nn.Linear)."""
     M, N = dy.shape
     return hip.gemm(dy, W, a_kc=True, b_kc=False, M=M, N=W.shape[1], K=N, lda=dy.stride(0), ldb=W.stride(0),
@@ -37,14 +34,12 @@ def mm_nn(dy, W, fp8=False, **kw):
 
 
 # Grouped launch: the weight-gradient products of one block (bf16) are collected while its backward runs and issued as ONE launch when
-# it ends (hip.gemm_group_tn); SARSSL_WGRAD_GROUP=0 issues them one by one where they occur (A/B runs).  (Round 2 also measured
+# it ends (hip.gemm_group_tn), their bias gradients with them.  (Round 2 also measured
 # companion-stream schedules for these products - per product and per block; neither beat keeping them on the chain, and a stream
 # forked off a forked stream crashes hipStreamEndCapture on ROCm 7.2 (tools/capture_nested_fork_repro.py).  Removed in round 3.)
-_WGRAD_GROUP = os.environ.get("SARSSL_WGRAD_GROUP", "1") != "0"
-_WGRAD_CSUM = os.environ.get("SARSSL_WGRAD_CSUM", "1") != "0"   # bias gradients from the grouped weight-gradient launch (0: separate column-sum launch)
-_STEM_LAST_ALL_CUS = os.environ.get("SARSSL_STEM_LAST_ALL_CUS", "1") != "0"   # gradient convolutions of the stem that runs last (spat) on every CU (model.py)
-_WGRAD_SPLIT_BIG = int(os.environ.get("SARSSL_WGRAD_SPLIT_BIG", "4"))            # K-slices of a grouped launch with >= .._TILES output tiles
-_WGRAD_SPLIT_BIG_TILES = int(os.environ.get("SARSSL_WGRAD_SPLIT_BIG_TILES", "128"))
+_STEM_LAST_ALL_CUS = True     # gradient convolutions of the stem that runs last (spat) on every CU (model.py)
+_WGRAD_SPLIT_BIG = 4          # K-slices of a grouped launch with >= .._TILES output tiles
+_WGRAD_SPLIT_BIG_TILES = 128
 _wg_blocks = []              # stack of pending-product lists (wgrad_block)
 
 
@@ -66,19 +61,18 @@ class wgrad_block:
         # cannot join the grouped launch (it has no ragged instantiation) - they must not keep the block's other products out of it
         ragged = [it for it in items if it[0].shape[0] % 64 != 0]
         items = [it for it in items if it[0].shape[0] % 64 == 0]
-        if _WGRAD_SPLIT_BIG != 8:
-            # a group whose products already have plenty of 256 x 128 output tiles needs fewer K-slices to fill the chip: half the
-            # partial-sum traffic of the products and of the fold launch
-            tiles = sum(((it[0].shape[1] + 255) // 256) * ((it[1].shape[1] + 127) // 128) for it in items)
-            if tiles >= _WGRAD_SPLIT_BIG_TILES:
-                items = [(dy, x, g2, _WGRAD_SPLIT_BIG if (split == 8 and dy.shape[0] >= 4096) else split, bias) for dy, x, g2, split, bias in items]
+        # a group whose products already have plenty of 256 x 128 output tiles needs fewer K-slices to fill the chip: half the
+        # partial-sum traffic of the products and of the fold launch
+        tiles = sum(((it[0].shape[1] + 255) // 256) * ((it[1].shape[1] + 127) // 128) for it in items)
+        if tiles >= _WGRAD_SPLIT_BIG_TILES:
+            items = [(dy, x, g2, _WGRAD_SPLIT_BIG if (split == 8 and dy.shape[0] >= 4096) else split, bias) for dy, x, g2, split, bias in items]
         for dy, x, g2, split, bias in ragged:
             _wgrad_gemm(dy, x, g2, split)
             if bias is not None:
                 hip.colsum(dy, bias)
         for i in range(0, len(items), 12):                 # one grouped launch per <= 12 products (csrc/gemm.hip)
             chunk = items[i:i + 12]
-            if not (_WGRAD_GROUP and len(chunk) > 1 and hip.gemm_group_tn(chunk)):
+            if not (len(chunk) > 1 and hip.gemm_group_tn(chunk)):
                 for dy, x, g2, split, bias in chunk:
                     _wgrad_gemm(dy, x, g2, split)
                     if bias is not None:
@@ -115,12 +109,9 @@ def mm_tn_acc(dy, x, gW, group=True, bias=None):
     M, N = dy.shape
     K = x.shape[1]
     g2 = gW.view(N, K)
-    grouped = bool(group and _wg_blocks and RT.replay is None and _WGRAD_GROUP and RT.dtype in _16)
+    grouped = bool(group and _wg_blocks and RT.replay is None and RT.dtype in _16)
     split = _wgrad_split(M, N, K, grouped)
     if grouped:
-        if bias is not None and not _WGRAD_CSUM:             # A/B: bias gradient by the stand-alone column-sum launch
-            hip.colsum(dy, bias)
-            bias = None
         _wg_blocks[-1].append((dy, x, g2, split, bias))      # enqueued when the block's backward ends (wgrad_block)
     else:
         _wgrad_gemm(dy, x, g2, split)
@@ -132,19 +123,16 @@ def mm_tn_acc(dy, x, gW, group=True, bias=None):
 # fp16 stem and module-internal tensors, f32 residual stream: an f32 activation is handed to a Linear layer as an fp16 pair (hip.Pair,
 # written by the LayerNorm in front of it), a weight as its (hi, lo) fp16 shadows; hip.gemm_split contracts hi hi + lo hi + hi lo.
 _F32 = torch.float32
-_H_STEM4 = os.environ.get("SARSSL_HYBRID_STEM4", "1") != "0"    # the stem's 4-channel tensors (64 -> 4 result, BatchNorm(4) + ReLU of it) as pairs (0: fp16)
-_H_CTX = os.environ.get("SARSSL_HYBRID_CTX", "1") != "0"        # the attention context enters the output projection as a pair (0: fp16)
 # Which Linear layers fed by a LayerNorm contract the ACTIVATION as a pair (three products) instead of its fp16 rounding (two).  The CPU
 # study (profiles/r06_operand_rounding_study.txt) says the pair buys no per-bin accuracy where the layer's OUTPUT is an fp16 tensor (q / k /
 # v, the feed-forward hidden layer: rms 1.02e-4 -> 1.06e-4 eval, 2.02e-4 -> 2.05e-4 train) - measured on the GPU (profiles/
 # r06_hybrid_alo_ab.txt) the per-bin figures hold (F13 train max 5.6e-4 -> 7.3e-4 on that build, inside the 1e-3 gate) but the GRADIENT deviation of the
 # f32-stream parameters grows 2.1e-3 -> 5.7e-3 / 6.9e-3 (the positional projection's weight, the convolution module's LayerNorm bias) for
-# 0.05 ms per family of an 11.1 ms step.  Not worth it: every family keeps the pair by default; "pw1,dec1" is the 0.1 ms faster setting.
-_H_ALO = set(v for v in os.environ.get("SARSSL_HYBRID_ALO", "ffn1,qkv,pw1,dec1").split(",") if v != "none" and v)
-_H_PREP = os.environ.get("SARSSL_HYBRID_PREP", "1") != "0"      # 0: the hybrid mode's positional projections / patch pair formed at their point of use
-_H_FFN2_FWD = os.environ.get("SARSSL_HYBRID_FFN2_FWD", "1") != "0"   # the feed-forward module's forward on the f32 stream in one launch (d = 256, csrc/ffn2h.hip; 0: LayerNorm + two GEMMs)
-_H_FFN2_BWD = os.environ.get("SARSSL_HYBRID_FFN2_BWD", "1") != "0"   # the feed-forward module's data gradients in the fused launch (d = 256; 0: two GEMMs)
-_H_DLN32 = os.environ.get("SARSSL_HYBRID_DLN32", "1") != "0"    # branch gradients entering the LayerNorm backward in f32 (0: bf16)
+# 0.05 ms per family of an 11.1 ms step.  Not worth it: every family keeps the pair ("pw1", "dec1" alone was the 0.1 ms faster setting).
+_H_ALO = {"ffn1", "qkv", "pw1", "dec1"}
+# The feed-forward module's forward on the f32 stream in one launch (d = 256, csrc/ffn2h.hip).  False is the LayerNorm + two-GEMM sequence that
+# replayed masks and M % 64 != 0 take anyway; tests/test_gpu_hybrid.py flips it to compare the two.
+_H_FFN2_FWD = True
 
 
 def wpair(p, view=None):
@@ -263,7 +251,7 @@ def stem_fwd(a0, pe, train, saved):
     fuse = train and RT.dtype in _16                     # BatchNorm sums come out of the producing kernel's epilogue
     W1 = pe[0].weight.data.view(64, 4)
     y1 = y2 = mom1 = None
-    if fuse and _C1IN and (B * F * T) % 64 == 0 and not RT.inference:
+    if fuse and (B * F * T) % 64 == 0 and not RT.inference:
         # the first layer's 64-channel output is never stored: its BatchNorm statistics follow from the 4 + 10 moments of the
         # 4-channel input, the first 3x3 convolution (and, in backward, its weight gradient and the layer's own backward pass) form
         # relu(bn1(W1 a0)) from a0 while staging - 4 x 537 MB less HBM traffic per encoder and step at B = 64
@@ -280,7 +268,7 @@ def stem_fwd(a0, pe, train, saved):
     y3, s3 = hip.conv3x3_fwd(y2, _taps(pe[6])[0], aff2[0], aff2[1], want_stats=True) if fuse else \
         (hip.conv3x3_fwd(y2, _taps(pe[6])[0], aff2[0], aff2[1], precise=RT.precise), None)
     aff3 = bn_affine(y3, 64, pe[7], train, sums=s3)
-    if RT.hybrid and _H_STEM4 and RT.dtype == torch.float16:
+    if RT.hybrid:
         # the f32 stream starts at the 4-channel tensors (0.5 MB per segment): the 64 -> 4 result and BatchNorm(4) + ReLU of it travel as
         # fp16 pairs into a three-segment frame-patch product; the hi halves are exactly the fp16 mode's y4 / z4 (what backward reads)
         if train:
@@ -301,41 +289,23 @@ def stem_fwd(a0, pe, train, saved):
         y4 = hip.stem_c4_fwd(y3, pe[9].weight.data.view(4, 64), aff3[0], aff3[1])
         aff4 = bn_affine(y4, 4, pe[10], train)
     z4 = hip.cl_affine_act(y4, 4, aff4, RELU).view(B * T, F * 4)
-    if RT.hybrid:          # the stream starts here: f32 result, the weight as its fp16 pair
-        e = mm_nt_h(z4, _patch_w_pair(pe[12], F), _F32)
-    else:
-        e = mm_nt(z4, _patch_w(pe[12], F), fp8=False)
+    e = mm_nt(z4, _patch_w(pe[12], F))
     saved.append((a0, (y1, mom1), aff1, y2, aff2, y3, aff3, y4, aff4, z4, train))
     return e
 
 
-# A/B switches of the round-2 work-removal passes (NOTES.md 4.1a / 4.6); bench.py prints their resolved state.  The paths measured
-# slower in round 2 (BatchNorm-backward transform inside the convolution staging, consumer-side BatchNorm finalize, one-pass 64->4
-# backward, the separate / half-fused first-layer backward) were removed from the engine in round 3.
-_DGRAD_BNRED = os.environ.get("SARSSL_DGRAD_BNRED", "1") != "0"
-_DWGLU = os.environ.get("SARSSL_DWGLU", "1") != "0"             # 0: separate glu / dwconv / cl_stats kernels (A/B runs)
-_FUSED_ATTN = os.environ.get("SARSSL_FUSED_ATTN", "1") != "0"   # 0: GEMM + softmax-kernel attention core also in bf16 mode (A/B runs)
-_ATTN_POS = os.environ.get("SARSSL_ATTN_POS", "1") != "0"       # 0: positional score by its own GEMM launch instead of inside the attention kernel (A/B runs)
-# T > 256 (config 5): the forward kernel forms the shifted score itself, one 256-key block of its slab at a time (round 6; bit-identical to
-# the score-GEMM sequence).  OFF by default: measured SLOWER on config 5 (same box, two interleaved rounds: 20.65 vs 20.33 ms fp16, 22.46 vs
-# 22.16 ms hybrid) - per (query tile, key block) the band of position tiles is re-staged through LDS behind two barriers each at one wave
-# per SIMD, which costs more than the chip-filling score GEMM it replaces plus the read of its 150 MB result
-_ATTN_POS_LONG = os.environ.get("SARSSL_ATTN_POS_LONG", "0") != "0"
-_C1IN = os.environ.get("SARSSL_C1IN", "1") != "0"             # 0: store the first layer's 64-channel output (A/B runs)
-_C1RED = os.environ.get("SARSSL_C1RED", "1") != "0"           # 0: store the gradient w.r.t. that output and reduce it in a pass of its own
-
-
 def knobs():
-    """Resolved state of every environment switch that selects a compute path (bench.py prints it; a benchmark line is only
-    comparable with another one under the same knobs)."""
+    """The compute paths this build takes (bench.py prints it; a benchmark line is only comparable with another one under the same
+    knobs).  The entries of retired A/B switches are literals - the side each one settled on - so that new benchmark lines stay comparable
+    with the recorded ones; SARSSL_TWO_STREAMS and SARSSL_GRAPH are the two that still follow the environment."""
     from . import runtime
-    return {"SARSSL_WGRAD_GROUP": int(_WGRAD_GROUP), "SARSSL_WGRAD_CSUM": int(_WGRAD_CSUM), "SARSSL_DGRAD_BNRED": int(_DGRAD_BNRED), "SARSSL_DWGLU": int(_DWGLU),
-            "SARSSL_FUSED_ATTN": int(_FUSED_ATTN), "SARSSL_ATTN_POS": int(_ATTN_POS), "SARSSL_ATTN_POS_LONG": int(_ATTN_POS_LONG), "SARSSL_C1IN": int(_C1IN), "SARSSL_C1RED": int(_C1RED),
-            "SARSSL_FUSE_DROP_BWD": int(_FUSE_DROP_BWD), "SARSSL_FFN2": int(_FFN2), "SARSSL_FFN2_FWD": sorted(_FFN2_FWD), "SARSSL_FFN2_BWD": sorted(_FFN2_BWD), "SARSSL_FFN2_LN": int(_FFN2_LN), "SARSSL_HYBRID_ALO": sorted(_H_ALO), "SARSSL_LIN256": int(_LIN256), "SARSSL_DEC_MASKED": int(_DEC_MASKED), "SARSSL_TAIL_MASKED": int(_TAIL_MASKED), "SARSSL_PREP_ASYNC": int(_PREP_ASYNC), "SARSSL_WGRAD_SPLIT_BIG": [_WGRAD_SPLIT_BIG, _WGRAD_SPLIT_BIG_TILES], "SARSSL_TWO_STREAMS": os.environ.get("SARSSL_TWO_STREAMS", "1"),
-            "SARSSL_STEM_LAST_ALL_CUS": int(_STEM_LAST_ALL_CUS), "SARSSL_WGRAD_WS": os.environ.get("SARSSL_WGRAD_WS", "1"),
-            "SARSSL_CONV_WS": os.environ.get("SARSSL_CONV_WS", "4"),
-            "SARSSL_CONV_CUS_FWD": os.environ.get("SARSSL_CONV_CUS_FWD", os.environ.get("SARSSL_CONV_CUS", "default(256)")),
-            "SARSSL_CONV_CUS_BWD": os.environ.get("SARSSL_CONV_CUS_BWD", os.environ.get("SARSSL_CONV_CUS", "default(224)")),
+    return {"SARSSL_WGRAD_GROUP": 1, "SARSSL_WGRAD_CSUM": 1, "SARSSL_DGRAD_BNRED": 1, "SARSSL_DWGLU": 1, "SARSSL_FUSED_ATTN": 1, "SARSSL_ATTN_POS": 1,
+            "SARSSL_ATTN_POS_LONG": 0, "SARSSL_C1IN": 1, "SARSSL_C1RED": 1, "SARSSL_FUSE_DROP_BWD": 1, "SARSSL_FFN2": 1,
+            "SARSSL_FFN2_FWD": sorted(_FFN2_WIDTHS), "SARSSL_FFN2_BWD": sorted(_FFN2_WIDTHS), "SARSSL_FFN2_LN": 1, "SARSSL_HYBRID_ALO": sorted(_H_ALO),
+            "SARSSL_LIN256": 0, "SARSSL_DEC_MASKED": int(_DEC_MASKED), "SARSSL_TAIL_MASKED": int(_TAIL_MASKED), "SARSSL_PREP_ASYNC": 1,
+            "SARSSL_WGRAD_SPLIT_BIG": [_WGRAD_SPLIT_BIG, _WGRAD_SPLIT_BIG_TILES], "SARSSL_TWO_STREAMS": os.environ.get("SARSSL_TWO_STREAMS", "1"),
+            "SARSSL_STEM_LAST_ALL_CUS": int(_STEM_LAST_ALL_CUS), "SARSSL_WGRAD_WS": "1", "SARSSL_CONV_WS": "4",
+            "SARSSL_CONV_CUS_FWD": "default(256)", "SARSSL_CONV_CUS_BWD": "default(224)",
             "SARSSL_GRAPH": os.environ.get("SARSSL_GRAPH", "default"),
             "precision": runtime.get_precision()}
 
@@ -356,7 +326,7 @@ def patch_bwd(de, pe, saved):
         gtmp = torch.zeros((d, F * 4), dtype=torch.float32, device=de.device)
         mm_tn_acc(de, z4, gtmp, group=False)
         hip.patch_wgrad_accum(gtmp, gbuf(pe[12].weight))
-    return mm_nn(de, _patch_w(pe[12], F, grad=True), fp8=False)                            # (B,T,F,4)
+    return mm_nn(de, _patch_w(pe[12], F, grad=True))                            # (B,T,F,4)
 
 
 def stem_bwd(dz4, pe, saved):
@@ -375,7 +345,7 @@ def stem_bwd(dz4, pe, saved):
     if dW is not None:
         gbuf(pe[6].weight).add_(dW.view(3, 3, 64, 64).permute(2, 3, 0, 1))
     red2 = None
-    if _DGRAD_BNRED and RT.dtype in _16:              # BatchNorm-backward sums accumulated in the data-gradient kernel's epilogue
+    if RT.dtype in _16:              # BatchNorm-backward sums accumulated in the data-gradient kernel's epilogue
         dz2, red2 = hip.conv3x3_dgrad_bnred(dy3, _taps(pe[6])[1], y2, aff2)
     else:
         dz2 = hip.conv3x3_fwd(dy3, _taps(pe[6])[1], precise=RT.precise)
@@ -384,8 +354,8 @@ def stem_bwd(dz4, pe, saved):
     dy2 = hip.cl_bn_bwd_apply(dz2, y2, 64, aff2, RELU, False, train, red2, out=dz2, pgrads=(gbuf(pe[4].weight), gbuf(pe[4].bias)))
     if y1 is None:                     # first layer never stored (stem_fwd): its operand is formed from a0 while staging
         hip.conv3x3_wgrad_c1(dy2, a0, W1, aff1[0], aff1[1], gbuf(pe[3].weight))
-        if _C1RED and hip.conv3x3_dgrad_c1red(dy2, _taps(pe[3])[1], a0, W1, aff1, mom1, train, gbuf(pe[0].weight),
-                                              gbuf(pe[1].weight), gbuf(pe[1].bias)):
+        if hip.conv3x3_dgrad_c1red(dy2, _taps(pe[3])[1], a0, W1, aff1, mom1, train, gbuf(pe[0].weight),
+                                     gbuf(pe[1].weight), gbuf(pe[1].bias)):
             return None     # the data gradient of the first 3x3 convolution was consumed in its epilogue: the first layer is done
     else:
         dW = hip.conv3x3_wgrad(dy2, y1, aff1[0], aff1[1], precise=RT.precise, acc_into=gbuf(pe[3].weight))
@@ -409,17 +379,13 @@ def _replaying(train):
     return train and RT.replay is not None
 
 
-_DEC_MASKED = os.environ.get("SARSSL_DEC_MASKED", "1") != "0"   # training steps run the decoder on the masked frames only (model._PretrainFn; 0: every frame)
-_PREP_ASYNC = os.environ.get("SARSSL_PREP_ASYNC", "1") != "0"    # weight-only launches of a step on the side stream, next to the front-end (model.py)
-_TAIL_MASKED = os.environ.get("SARSSL_TAIL_MASKED", "1") != "0"  # ... and the row-wise tail of each encoder's last block (second feed-forward module + closing LayerNorm)
-_FFN2 = os.environ.get("SARSSL_FFN2", "1") != "0"             # 0: the feed-forward module as two GEMM launches (A/B runs)
-# Model widths that take the fused forward / backward launch.  Default: d = 256 only (the spat encoder - the step's critical chain).  The
-# fused launch owns whole CUs (512 threads, 101-134 KB of LDS); at d = 512 (spec encoder) it runs 100-160 us during which the other
+_DEC_MASKED = True     # training steps run the decoder on the masked frames only (model._PretrainFn; False: every frame)
+_TAIL_MASKED = True    # ... and the row-wise tail of each encoder's last block (second feed-forward module + closing LayerNorm)
+# Model widths that take the fused feed-forward launches (forward and backward, the module's LayerNorm inside them): d = 256 only
+# (the spat encoder - the step's critical chain).  The fused launch owns whole CUs (512 threads, 101-134 KB of LDS); at d = 512 (spec encoder) it runs 100-160 us during which the other
 # encoder's stream gets no CU, and the step is SLOWER with it (same box, two rounds: off 10.69 / 10.70 ms, d = 256 only 10.64 / 10.59,
 # d = 512 only 10.86 / 10.83, both 10.78 / 10.71) although the launch itself beats its two GEMMs alone (101 vs 121 us forward).
-_FFN2_LN = os.environ.get("SARSSL_FFN2_LN", "1") != "0"       # the module's LayerNorm (forward / backward) inside the fused launches (0: own launches)
-_FFN2_FWD = set(int(v) for v in os.environ.get("SARSSL_FFN2_FWD", "256").split(",") if v)
-_FFN2_BWD = set(int(v) for v in os.environ.get("SARSSL_FFN2_BWD", "256").split(",") if v)
+_FFN2_WIDTHS = (256,)
 
 
 def prepare_ffn_packs(ffs, need_bwd=True):
@@ -429,7 +395,7 @@ def prepare_ffn_packs(ffs, need_bwd=True):
     jobs, fresh = [], []
     for ff in ffs:
         l1, l2 = ff.sequential[1].linear, ff.sequential[4].linear
-        if l1.weight.shape[1] not in _FFN2_FWD and l1.weight.shape[1] not in _FFN2_BWD:
+        if l1.weight.shape[1] not in _FFN2_WIDTHS:
             continue
         w1, w2 = wt(l1.weight), wt(l2.weight)
         if w1.dtype not in _16 or not w1.is_cuda:
@@ -458,70 +424,6 @@ def prepare_ffn_packs(ffs, need_bwd=True):
         ff.__dict__["_ffn2_packs"] = (key, bufs)
 
 
-# LayerNorm + q/k/v / first pointwise convolution (and their data gradient + LayerNorm backward) of the d = 256 blocks as one tile-resident
-# launch each (csrc/lin256.hip).  OFF by default: alone the launches beat the pairs they replace (LayerNorm + q/k/v 21.2 vs 27.4 us, data
-# gradient + LayerNorm backward 33.0 vs 37.7 us; tools/bench_lin256.py), inside the two-stream step they do not - same box, three interleaved
-# rounds: 10.67 / 10.67 / 10.66 ms with, 10.64 / 10.62 / 10.65 ms without.  Like the d = 512 feed-forward launch, a 512-thread / 100 KB
-# workgroup owns its CU, and what it displaces from the other encoder's stream costs what it saves (NOTES.md section 10).
-_LIN256 = os.environ.get("SARSSL_LIN256", "0") != "0"
-
-
-def _lin_pack_jobs(owner, name, w_fwd, w_bwd, need_bwd):
-    """Pack jobs (and the cache entry to commit) of one Linear weight [N, K]: forward pack of W in the forward dtype, pack of W^T in the
-    gradient dtype; persistent buffers on ``owner`` (an nn.Module), stale when the weights' version moved."""
-    key = (weights_version(), w_fwd.dtype, w_fwd.data_ptr(), bool(need_bwd))
-    c = owner.__dict__.get("_lin256_" + name)
-    if c is not None and (c[0] == key or (c[0][:3] == key[:3] and c[0][3])):
-        return [], None
-    bufs = owner.__dict__.get("_lin256_bufs_" + name)
-    if bufs is None or bufs[0].dtype != w_fwd.dtype or bufs[0].device != w_fwd.device or bufs[0].numel() != w_fwd.numel():
-        bufs = owner.__dict__["_lin256_bufs_" + name] = (torch.empty(w_fwd.numel(), dtype=w_fwd.dtype, device=w_fwd.device),
-                                                         torch.empty(w_fwd.numel(), dtype=RT.gdtype, device=w_fwd.device))
-    jobs = [(w_fwd, bufs[0])]
-    if need_bwd:
-        jobs.append((w_bwd.t(), bufs[1]))
-    return jobs, ("_lin256_" + name, key, bufs)
-
-
-def _lin256_weights(blk_mod, kind):
-    """(forward view [N, K], gradient-side view) of the layer a tile-resident launch replaces: 'qkv' of an attention module (the three
-    projections back to back in the flat buffers) or 'pw1' of a convolution module; None when the layout does not allow it."""
-    if kind == "qkv":
-        att = blk_mod.attention
-        f, gsd = _qkv_views(att), _qkv_views(att, grad=True)
-        return None if f is None or gsd is None else (f[0], gsd[0])
-    pw1 = blk_mod.sequential[2].conv
-    d = pw1.weight.shape[1]
-    return wt(pw1.weight).view(2 * d, d), wtg(pw1.weight).view(2 * d, d)
-
-
-def prepare_lin256_packs(mods, need_bwd=True):
-    """mods: [(module, kind)] - packs of every stale weight in one launch (model._PretrainFn: once per step for the whole spat encoder)."""
-    jobs, commits = [], []
-    for m, kind in mods:
-        ws = _lin256_weights(m, kind)
-        if ws is None or ws[0].dtype not in _16 or not ws[0].is_cuda or ws[0].shape[1] != 256:
-            continue
-        j, c = _lin_pack_jobs(m, kind, ws[0], ws[1], need_bwd)
-        jobs += j
-        if c is not None:
-            commits.append((m, c))
-    if jobs:
-        hip.ffn_pack(jobs)
-    for m, (name, key, bufs) in commits:
-        m.__dict__[name] = (key, bufs)
-
-
-def _lin256_pack(m, kind, need_bwd=True):
-    prepare_lin256_packs([(m, kind)], need_bwd)
-    c = m.__dict__.get("_lin256_" + kind)
-    return None if c is None else c[1]
-
-
-def block_lin256_mods(enc):
-    return [(blk.sequential[1].module, "qkv") for blk in enc.layers] + [(blk.sequential[2].module, "pw1") for blk in enc.layers]
-
-
 def _ffn_packs(ff, need_bwd=True):
     prepare_ffn_packs([ff], need_bwd)
     return ff.__dict__["_ffn2_packs"][1]
@@ -540,7 +442,7 @@ def _ffn_fwd_h(x, ff, factor, train, saved, out=None):
     p1, p2 = _p(seq[3], train), _p(seq[5], train)
     l1, l2 = seq[1].linear, seq[4].linear
     d = x.shape[1]
-    if (_FFN2 and _H_FFN2_FWD and d in _FFN2_FWD and pre is None and not _replaying(train) and x.stride(1) == 1 and hip.ffn2h_supported(x.shape[0], d)
+    if (_H_FFN2_FWD and d in _FFN2_WIDTHS and pre is None and not _replaying(train) and x.stride(1) == 1 and hip.ffn2h_supported(x.shape[0], d)
             and l1.weight.shape[0] == 4 * d and wt(l1.weight).is_cuda):
         # LayerNorm + Linear + Swish + Dropout + Linear + Dropout + scaled residual on the f32 stream in one launch (csrc/ffn2h.hip)
         packs = _ffn_packs(ff, need_bwd=not RT.inference)
@@ -585,7 +487,7 @@ def _ffn_bwd_h(dy, ff, saved, dy16=None, next_kind=None, want16=True):
         dz2 = dz2 * (s2 * factor).to(dz2.dtype)
     mm_tn_acc(dz2, a, gbuf(l2.weight), bias=gbuf(l2.bias))
     d = x.shape[1]
-    if (_FFN2 and _H_FFN2_BWD and d in _FFN2_BWD and not torch.is_tensor(s1) and dz2.stride(1) == 1 and hip.ffn2_supported(x.shape[0], d, dz2.dtype)
+    if (d in _FFN2_WIDTHS and not torch.is_tensor(s1) and dz2.stride(1) == 1 and hip.ffn2_supported(x.shape[0], d, dz2.dtype)
             and hpre.shape[1] == 4 * d and ff.__dict__.get("_ffn2_packs") is not None and ff.__dict__["_ffn2_packs"][0][5]
             and ff.__dict__["_ffn2_packs"][0][0] == weights_version()):
         # both data-gradient products in the fused launch of the fp16 mode (csrc/ffn2.hip; bf16 gradients, fp16 saved pre-activation):
@@ -599,7 +501,7 @@ def _ffn_bwd_h(dy, ff, saved, dy16=None, next_kind=None, want16=True):
     else:
         dh = mm_nn(dz2, wtg(l2.weight), aux=hpre, aux_act=SWISH, p_drop=p1, seed=s1)
     mm_tn_acc(dh, ln, gbuf(l1.weight), bias=gbuf(l1.bias))
-    dln = mm_nn(dh, wtg(l1.weight), out_dtype=_F32 if _H_DLN32 else None)
+    dln = mm_nn(dh, wtg(l1.weight), out_dtype=_F32)
     return _ln_bwd_h(dln, x, seq[0], stats, _as_stream(dy), saved, next_kind, want16)
 
 
@@ -611,11 +513,11 @@ def ffn_fwd(x, ff, factor, train, saved, out=None):
     pre = x.__dict__.pop("_pre_ln", None)            # (block_fwd of the previous block already normalised this very tensor for us)
     p1, p2 = _p(seq[3], train), _p(seq[5], train)
     d = x.shape[1]
-    fused = (_FFN2 and d in _FFN2_FWD and not _replaying(train) and hip.ffn2_supported(x.shape[0], d, x.dtype)
+    fused = (d in _FFN2_WIDTHS and not _replaying(train) and hip.ffn2_supported(x.shape[0], d, x.dtype)
              and seq[1].linear.weight.shape[0] == 4 * d)
     if pre is not None and pre[0] is seq[0]:
         ln, stats = pre[1], pre[2]
-    elif fused and _FFN2_LN and x.stride(1) == 1:
+    elif fused and x.stride(1) == 1:
         ln = stats = None                           # the fused launch normalises its rows itself (bit-identical to the stand-alone kernel)
     else:
         ln, stats = hip.layernorm_fwd(x, seq[0].weight.data, seq[0].bias.data, seq[0].eps)
@@ -652,15 +554,12 @@ def ffn_fwd(x, ff, factor, train, saved, out=None):
     return y
 
 
-_FUSE_DROP_BWD = os.environ.get("SARSSL_FUSE_DROP_BWD", "1") != "0"
-
-
 def _next_drop(kind, saved):
     """(p, seed, gscale) of the dropout backward the NEXT module of the backward chain (``kind``: 'ffn' | 'conv' | 'mhsa', its entry
     is on top of ``saved``) applies to its incoming gradient, or None when there is nothing to apply (or the masks are replayed host
     tensors).  The LayerNorm backward that produces that gradient then writes the dropped copy as a second output
     (hip.layernorm_bwd(drop=...)) instead of a separate act_bwd pass."""
-    if not _FUSE_DROP_BWD or kind is None or kind == "copy" or not saved:
+    if kind is None or kind == "copy" or not saved:
         return None
     e = saved[-1]
     if kind == "ffn":
@@ -692,12 +591,12 @@ def ffn_bwd(dy, ff, saved, dy_dropped=None, next_kind=None):
             dz2 = hip.act_bwd(dy, None, 0, p_drop=p2, seed=s2, gscale=factor) if (p2 > 0 or factor != 1.0) else dy
         mm_tn_acc(dz2, a, gbuf(seq[4].linear.weight), bias=gbuf(seq[4].linear.bias))
         d = x.shape[1]
-        if (_FFN2 and d in _FFN2_BWD and dz2.dtype in _16 and dz2.stride(1) == 1 and hip.ffn2_supported(x.shape[0], d, dz2.dtype)
+        if (d in _FFN2_WIDTHS and dz2.dtype in _16 and dz2.stride(1) == 1 and hip.ffn2_supported(x.shape[0], d, dz2.dtype)
                 and hpre.shape[1] == 4 * d and ff.__dict__.get("_ffn2_packs") is not None and ff.__dict__["_ffn2_packs"][0][5]):
             # both data-gradient products in one launch: dh = (dz2 W2) * mask * swish'(hpre) leaves the chip once (the two weight-gradient
             # products read it), dln = dh W1 is formed from the LDS-resident tile (csrc/ffn2.hip, packs of the transposed weights)
             packs = _ffn_packs(ff)
-            if _FFN2_LN and x.dtype == hpre.dtype and x.stride(1) == 1 and dy.stride(1) == 1:
+            if x.dtype == hpre.dtype and x.stride(1) == 1 and dy.stride(1) == 1:
                 # ... and the LayerNorm backward of the module's first layer in the same launch's epilogue (dln never leaves the chip)
                 dx, dh = hip.ffn2_bwd(dz2, packs[2], packs[3], hpre, d, p1=p1, s1=s1,
                                       ln_bwd=(x, seq[0].weight.data, stats, dy, gbuf(seq[0].weight), gbuf(seq[0].bias), _next_drop(next_kind, saved)))
@@ -728,7 +627,7 @@ def _pos_proj(mod, T):
     """The module's positional projection linear_pos(PE[:T]) [T, d] (attention.py:84): batch-invariant and a function of the weights only,
     so it is cached per weight version like the re-laid-out taps - prepare_step_weights forms it off the encoders' chains."""
     lin = mod.attention.pos_proj.linear
-    return _cached(lin, "pos%d" % T, lambda: mm_nt(_pe(mod, T), wt(lin.weight), fp8=False))
+    return _cached(lin, "pos%d" % T, lambda: mm_nt(_pe(mod, T), wt(lin.weight)))
 
 
 def prepare_step_weights(net, F, T, need_bwd=True):
@@ -737,15 +636,13 @@ def prepare_step_weights(net, F, T, need_bwd=True):
     masking launches run (a dozen 5-20 us launches that otherwise sit in the two encoders' chains).  The point-of-use helpers
     (_taps, _patch_w, _pos_proj, _ffn_packs) then hit their caches."""
     encs = (net.spec_encoder, net.spat_encoder)
-    if _FFN2 and RT.dtype in _16 and RT.replay is None:
+    if RT.dtype in _16 and RT.replay is None:
         # fragment-order packs of every feed-forward module's weights for the fused kernel: one launch per step
         prepare_ffn_packs(block_ffns(encs[0].embed) + block_ffns(encs[1].embed), need_bwd=need_bwd)
-        if _LIN256:
-            prepare_lin256_packs(block_lin256_mods(encs[0].embed) + block_lin256_mods(encs[1].embed), need_bwd=need_bwd)
     for enc in encs:
         pe = enc.patch_embed
         _taps(pe[3]); _taps(pe[6])
-        if RT.hybrid and _H_PREP:
+        if RT.hybrid:
             _patch_w_pair(pe[12], F)                         # (the forward's operand; the backward takes the gradient-side matrix below)
         else:
             _patch_w(pe[12], F)
@@ -754,7 +651,7 @@ def prepare_step_weights(net, F, T, need_bwd=True):
         for blk in enc.embed.layers:
             # hybrid: the pair-accurate projection is what both passes use (round 6: it used to be formed inside the blocks' chains - four
             # 12-19 us launches - while the fp16 mode's projection was still formed here, unused)
-            (_pos_proj_h if (RT.hybrid and _H_PREP) else _pos_proj)(blk.sequential[1].module, T)
+            (_pos_proj_h if RT.hybrid else _pos_proj)(blk.sequential[1].module, T)
 
 
 def _adjacent(ts):
@@ -822,8 +719,8 @@ def _mhsa_fwd_h(x, mod, B, T, train, saved):
     sa = RT.next_seed() if pa > 0 else 0
     scale = 1.0 / math.sqrt(d)
     replay = _replaying(train) and (pa > 0 or _p(mod.dropout, train) > 0)
-    fused_attn = _FUSED_ATTN and not replay and hip.relpos_attn_supported(T, dh, RT.dtype)
-    in_kernel = fused_attn and _ATTN_POS and hip.relpos_attn_pos_supported(T, dh, RT.dtype)
+    fused_attn = not replay and hip.relpos_attn_supported(T, dh, RT.dtype)
+    in_kernel = fused_attn and hip.relpos_attn_pos_supported(T, dh, RT.dtype)
     ub, vb = att.u_bias.data.view(-1), att.v_bias.data.view(-1)
     qu, qv = (q, None) if in_kernel else hip.bias2(q, ub, vb)
     po = _p(mod.dropout, train)
@@ -831,20 +728,18 @@ def _mhsa_fwd_h(x, mod, B, T, train, saved):
     if fused_attn:
         if in_kernel:
             ctx, lse, bias = hip.relpos_attn_fwd_pos(q, q, k, v, pos, B, H, T, dh, scale, pa, sa, need_bwd=not RT.inference, biases=(ub, vb),
-                                                     pair=_H_CTX)            # (the kernel writes the context's lo half itself)
-        elif _ATTN_POS_LONG and hip.relpos_attn_pos_long_supported(T, dh, RT.dtype):
-            ctx, lse, bias = hip.relpos_attn_fwd_pos_long(qu, qv, k, v, pos, B, H, T, dh, scale, pa, sa, need_bwd=not RT.inference, want_ctx32=_H_CTX)
+                                                     pair=True)              # (the kernel writes the context's lo half itself)
         else:
             bias = torch.empty((B, H, T, T), dtype=RT.dtype, device=x.device)
             hip.gemm(qv, pos, M=T, N=T, K=dh, lda=d, ldb=d, nbatch=nbh, batch_inner=H, sA=(T * d, dh), sB=(0, dh), out=bias, ldc=T,
                      sC=(H * T * T, T * T), c_row_shift=True)
-            ctx, lse = hip.relpos_attn_fwd(qu, k, v, bias, B, H, T, dh, scale, pa, sa, need_bwd=not RT.inference, want_ctx32=_H_CTX)
+            ctx, lse = hip.relpos_attn_fwd(qu, k, v, bias, B, H, T, dh, scale, pa, sa, need_bwd=not RT.inference, want_ctx32=True)
         so = RT.next_seed() if po > 0 else 0
         # the kernel's unrounded f32 context (it keeps it for the backward pass anyway) enters the output projection as a pair
         if isinstance(ctx, hip.Pair):
             cin, ctx = ctx, ctx.hi
         else:
-            cin = hip.Pair(ctx, hip.split_pair(lse[0], want_hi=False)) if (_H_CTX and lse[0] is not None) else ctx
+            cin = hip.Pair(ctx, hip.split_pair(lse[0], want_hi=False)) if lse[0] is not None else ctx
         y = mm_nt_h(cin, wo, _F32, bias=att.out_proj.linear.bias.data, p_drop=po, seed=so, resid=x, ldr=x.stride(0), res_scale=1.0)
         saved.append((x, ln.hi, stats, qu, qv, k, v, pos, pe, bias, lse, pa, sa, ctx, po, so, B, T))
         return y
@@ -888,17 +783,8 @@ def mhsa_fwd(x, mod, B, T, train, saved):
     if RT.hybrid:
         return _mhsa_fwd_h(x, mod, B, T, train, saved)
     fused = _qkv_views(att)
-    lin = (_LIN256 and fused is not None and d == 256 and not _replaying(train) and x.stride(1) == 1
-           and hip.lin256_supported(M, 3 * d, d, x.dtype))
-    pk = _lin256_pack(mod, "qkv", need_bwd=not RT.inference) if lin else None
-    if pk is not None:      # LayerNorm + the [M, 3d] projection in one tile-resident launch (csrc/lin256.hip)
-        qkv, ln, stats = hip.lin256_fwd(None, pk[0], fused[1], 3 * d, d, ln_in=(x, mod.layer_norm.weight.data, mod.layer_norm.bias.data, mod.layer_norm.eps))
-        q, k, v = qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:]
-    else:
-        ln, stats = hip.layernorm_fwd(x, mod.layer_norm.weight.data, mod.layer_norm.bias.data, mod.layer_norm.eps)
-    if pk is not None:
-        pass
-    elif fused is not None:                     # one [M, 3d] GEMM; q / k / v are column slices (row stride 3d)
+    ln, stats = hip.layernorm_fwd(x, mod.layer_norm.weight.data, mod.layer_norm.bias.data, mod.layer_norm.eps)
+    if fused is not None:                       # one [M, 3d] GEMM; q / k / v are column slices (row stride 3d)
         qkv = mm_nt(ln, fused[0], bias=fused[1])
         q, k, v = qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:]
     else:
@@ -913,8 +799,8 @@ def mhsa_fwd(x, mod, B, T, train, saved):
     sa = RT.next_seed() if pa > 0 else 0
     scale = 1.0 / math.sqrt(d)                                                               # 1/sqrt(d_model), attention.py:57
     replay = _replaying(train) and (pa > 0 or _p(mod.dropout, train) > 0)
-    fused_attn = _FUSED_ATTN and not replay and hip.relpos_attn_supported(T, dh, RT.dtype)
-    in_kernel = fused_attn and _ATTN_POS and hip.relpos_attn_pos_supported(T, dh, RT.dtype)
+    fused_attn = not replay and hip.relpos_attn_supported(T, dh, RT.dtype)
+    in_kernel = fused_attn and hip.relpos_attn_pos_supported(T, dh, RT.dtype)
     ub, vb = att.u_bias.data.view(-1), att.v_bias.data.view(-1)
     # (positional score in the kernels: they also form q + u / q + v while loading the query rows - no biased copies of q)
     qu, qv = (q, None) if in_kernel else hip.bias2(q, ub, vb)
@@ -925,10 +811,6 @@ def mhsa_fwd(x, mod, B, T, train, saved):
             # T <= 256: the kernel forms the shifted positional score itself (position tiles stream through its K buffer)
             ctx, lse, bias = hip.relpos_attn_fwd_pos(q, q, k, v, pos, B, H, T, dh, scale, pa, sa, need_bwd=not RT.inference,
                                                      biases=(ub, vb))
-        elif _ATTN_POS_LONG and hip.relpos_attn_pos_long_supported(T, dh, RT.dtype):
-            # T > 256 (config 5): the forward kernel forms the shifted score itself, one 256-key block of the slab at a time, and writes
-            # it out for the backward kernels - no positional-score GEMM launch, no read of its result
-            ctx, lse, bias = hip.relpos_attn_fwd_pos_long(qu, qv, k, v, pos, B, H, T, dh, scale, pa, sa, need_bwd=not RT.inference)
         else:
             bias = torch.empty((B, H, T, T), dtype=RT.dtype, device=x.device)
             hip.gemm(qv, pos, M=T, N=T, K=dh, lda=d, ldb=d, nbatch=nbh, batch_inner=H, sA=(T * d, dh), sB=(0, dh), out=bias, ldc=T,
@@ -1000,7 +882,7 @@ def mhsa_bwd(dy, mod, saved, dy_dropped=None, next_kind=None):
         dv = torch.empty((M, d), dtype=RT.gdtype, device=dev)
     ldg = dqu.stride(0)
     scale = 1.0 / math.sqrt(d)
-    if fused_attn and _ATTN_POS and hip.relpos_attn_pos_supported(T, dh, RT.dtype):
+    if fused_attn and hip.relpos_attn_pos_supported(T, dh, RT.dtype):
         # T <= 256: the dQ kernel also forms the positional-score gradients (no d(bias) tensor, un-shift pass or batched products)
         dqv = torch.empty((M, d), dtype=RT.gdtype, device=dev)
         plain_q = qv is None                       # forward saved the plain query projection: the kernels add u / v while loading
@@ -1069,13 +951,7 @@ def _mhsa_bwd_tail(dy, mod, att, x, ln, stats, pe, dqkv, dqu, dk, dv, dqv, dposb
     dq = dq_out if dq_done else hip.axpby2d(dqu, dqv, 1.0, 1.0, out=dq_out)      # (dq_done: the attention backward wrote dqu + dqv itself)
     if fused is not None:
         mm_tn_acc(dqkv, ln, fused[2], bias=fused[3])
-        pk = mod.__dict__.get("_lin256_qkv")
-        if (_LIN256 and pk is not None and pk[0][3] and pk[0][0] == weights_version() and d == 256 and dqkv.dtype in _16 and x.dtype == ln.dtype
-                and x.stride(1) == 1 and dy.stride(1) == 1 and hip.lin256_supported(dqkv.shape[0], d, 3 * d, dqkv.dtype)):
-            # data gradient of the projection + the LayerNorm backward in one tile-resident launch
-            return hip.lin256_bwd(dqkv, pk[1][1], d, 3 * d, ln_bwd=(x, mod.layer_norm.weight.data, stats, dy, gbuf(mod.layer_norm.weight),
-                                                                     gbuf(mod.layer_norm.bias), drop))
-        dln = mm_nn(dqkv, fused[0], out_dtype=_F32 if (RT.hybrid and _H_DLN32) else None)
+        dln = mm_nn(dqkv, fused[0], out_dtype=_F32 if RT.hybrid else None)
     else:
         for proj, g in ((att.query_proj, dq), (att.key_proj, dk), (att.value_proj, dv)):
             mm_tn_acc(g, ln, gbuf(proj.linear.weight), bias=gbuf(proj.linear.bias))
@@ -1096,19 +972,15 @@ def convmod_fwd(x, cm, B, T, train, saved):
     hyb = RT.hybrid
     if hyb:
         x = _as_stream(x)
-    lin = (_LIN256 and not hyb and d == 256 and not _replaying(train) and x.stride(1) == 1 and hip.lin256_supported(x.shape[0], 2 * d, d, x.dtype))
-    pk = _lin256_pack(cm, "pw1", need_bwd=not RT.inference) if lin else None
     if hyb:                 # f32 stream in / out; the module's inner tensors (h, c, s) are the fp16 tensors of the fp16 mode
         lnp, stats = hip.layernorm_fwd_pair(x, seq[0].weight.data, seq[0].bias.data, seq[0].eps, want_lo="pw1" in _H_ALO)
         ln = lnp.hi
         h = mm_nt_h(lnp, wpair(pw1.weight, (2 * d, d)), torch.float16, bias=pw1.bias.data)
-    elif pk is not None:      # LayerNorm + first pointwise convolution in one tile-resident launch (csrc/lin256.hip)
-        h, ln, stats = hip.lin256_fwd(None, pk[0], pw1.bias.data, 2 * d, d, ln_in=(x, seq[0].weight.data, seq[0].bias.data, seq[0].eps))
     else:
         ln, stats = hip.layernorm_fwd(x, seq[0].weight.data, seq[0].bias.data, seq[0].eps)
         h = mm_nt(ln, wt(pw1.weight).view(2 * d, d), bias=pw1.bias.data)                     # [M, 2d]
     g = None
-    if _DWGLU and d % 8 == 0:            # GLU + depthwise conv + BatchNorm batch sums in one LDS-tiled pass (csrc/dwconv.hip)
+    if d % 8 == 0:            # GLU + depthwise conv + BatchNorm batch sums in one LDS-tiled pass (csrc/dwconv.hip)
         c, sums = hip.dwglu_fwd(h, dw.weight.data.view(d, -1), B, T, want_stats=True) if train else \
             (hip.dwglu_fwd(h, dw.weight.data.view(d, -1), B, T), None)
         if train and d >= 64 and 256 % (d // 8) == 0:       # BatchNorm finalize + affine + Swish in one launch (bit-identical to the two)
@@ -1163,20 +1035,12 @@ def convmod_bwd(dy, cm, saved, dy_dropped=None, next_kind=None):
         hip.dwconv_wgrad(dc, g.view(B, T, d), gbuf(dw.weight).view(d, -1))
         dh = hip.glu_bwd(dg.view(B * T, d), h)
     mm_tn_acc(dh, ln, gbuf(pw1.weight), bias=gbuf(pw1.bias))
-    pk = cm.__dict__.get("_lin256_pw1")
-    if (_LIN256 and pk is not None and pk[0][3] and pk[0][0] == weights_version() and d == 256 and dh.dtype in _16 and x.dtype == ln.dtype
-            and x.stride(1) == 1 and dy.stride(1) == 1 and dh.stride(1) == 1 and hip.lin256_supported(dh.shape[0], d, 2 * d, dh.dtype)):
-        return hip.lin256_bwd(dh, pk[1][1], d, 2 * d, ln_bwd=(x, seq[0].weight.data, stats, dy, gbuf(seq[0].weight), gbuf(seq[0].bias),
-                                                               _next_drop(next_kind, saved)))
     if RT.hybrid:
-        dln = mm_nn(dh, wtg(pw1.weight).view(2 * d, d), out_dtype=_F32 if _H_DLN32 else None)
+        dln = mm_nn(dh, wtg(pw1.weight).view(2 * d, d), out_dtype=_F32)
         return _ln_bwd_h(dln, x, seq[0], stats, _as_stream(dy), saved, next_kind, next_kind is not None)
     dln = mm_nn(dh, wtg(pw1.weight).view(2 * d, d))
     return hip.layernorm_bwd(dln, x, seq[0].weight.data, stats, resid=dy, dgamma=gbuf(seq[0].weight), dbeta=gbuf(seq[0].bias),
                              drop=_next_drop(next_kind, saved))
-
-
-_LN_PAIR = os.environ.get("SARSSL_LN_PAIR", "1") != "0"       # 0: the two LayerNorms of a block boundary as two launches (A/B runs)
 
 
 def block_fwd(x, blk, B, T, train, saved, out=None, next_blk=None, rows=None):
@@ -1200,8 +1064,8 @@ def block_fwd(x, blk, B, T, train, saved, out=None, next_blk=None, rows=None):
         saved.append((xc, stats, (rows, B, T), x))          # (x: the full-row input of the tail, for a full prediction on request - vis)
         return y
     x = ffn_fwd(x, seq[3].module, seq[3].module_factor, train, saved)
-    if next_blk is not None and out is None and _LN_PAIR and not (RT.hybrid and _FFN2 and _H_FFN2_FWD and x.shape[1] in _FFN2_FWD and not _replaying(train)
-                                                               and hip.ffn2h_supported(x.shape[0], x.shape[1])):
+    if next_blk is not None and out is None and not (RT.hybrid and _H_FFN2_FWD and x.shape[1] in _FFN2_WIDTHS and not _replaying(train)
+                                                     and hip.ffn2h_supported(x.shape[0], x.shape[1])):
         # (hybrid, d = 256: the next block's fused feed-forward launch normalises its rows in its own prologue)
         nln = next_blk.sequential[0].module.sequential[0]
         if RT.hybrid:
@@ -1289,8 +1153,8 @@ def decoder_fwd(e, dec, saved):
         pred = mm_nt_h(h, wpair(l2.weight), _F32, bias=l2.bias.data)
         saved.append((ep.hi, h))
         return pred
-    h = mm_nt(e, wt(l1.weight), fp8=False, bias=l1.bias.data, act=RELU)
-    pred = mm_nt(h, wt(l2.weight), fp8=False, bias=l2.bias.data)
+    h = mm_nt(e, wt(l1.weight), bias=l1.bias.data, act=RELU)
+    pred = mm_nt(h, wt(l2.weight), bias=l2.bias.data)
     saved.append((e, h))
     return pred
 
@@ -1300,9 +1164,9 @@ def decoder_bwd(dpred, dec, saved):
     l1, l2 = dec.proj[0], dec.proj[2]
     with hip.colsum_batched(), hip.splitk_batched(), wgrad_block():
         mm_tn_acc(dpred, h, gbuf(l2.weight), bias=gbuf(l2.bias))
-        dh = mm_nn(dpred, wtg(l2.weight), fp8=False, aux=h, aux_act=RELU)
+        dh = mm_nn(dpred, wtg(l2.weight), aux=h, aux_act=RELU)
         mm_tn_acc(dh, e, gbuf(l1.weight), bias=gbuf(l1.bias))
-        return mm_nn(dh, wtg(l1.weight), fp8=False, out_dtype=_F32 if RT.hybrid else None)      # hybrid: the stream's gradient is f32
+        return mm_nn(dh, wtg(l1.weight), out_dtype=_F32 if RT.hybrid else None)      # hybrid: the stream's gradient is f32
 
 
 # ------------------------------------------------------------------------------------------------ downstream heads

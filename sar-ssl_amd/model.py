@@ -381,7 +381,7 @@ class SARSSL(nn.Module):
         results) or, single-stream, in place (-> True).  graph.py calls it in front of the front-end launch and leaves the event in
         ``_prep_event`` for the forward pass."""
         dev = next(self.parameters()).device
-        side = self._side_stream(dev) if (engine._PREP_ASYNC and dev.type == "cuda") else None
+        side = self._side_stream(dev) if dev.type == "cuda" else None
         if side is None:
             engine.prepare_step_weights(self, F, T, need_bwd=not RT.inference)
             return True

@@ -35,7 +35,7 @@ def run(B, H, T, dh, p_drop, iters):
     pos = (torch.randn((T, d), device=dev, generator=g) * 0.5).to(torch.bfloat16)
     quc = qu.contiguous()                       # (q + u and q + v share a row stride, as the engine's bias2 produces them)
 
-    def gemm_fwd():                             # what a layer issues with SARSSL_ATTN_POS=0: shifted positional-score GEMM, then the kernel
+    def gemm_fwd():                             # what a layer issues where T > 256: shifted positional-score GEMM, then the kernel
         hip.gemm(qv, pos, M=T, N=T, K=dh, lda=d, ldb=d, nbatch=B * H, batch_inner=H, sA=(T * d, dh), sB=(0, dh), out=bias, ldc=T,
                  sC=(H * T * T, T * T), c_row_shift=True)
         hip.relpos_attn_fwd(qu, k, v, bias, B, H, T, dh, scale, p_drop, 11)
@@ -49,7 +49,7 @@ def run(B, H, T, dh, p_drop, iters):
     ctx_p, aux_p, bias_p = hip.relpos_attn_fwd_pos(quc, qv, k, v, pos, B, H, T, dh, scale, p_drop, 11)
     dqv = torch.empty((B * T, d), dtype=torch.bfloat16, device=dev)
 
-    def bwd_unfused_all():                      # SARSSL_ATTN_POS=0: kernels + un-shift pass + the two batched products of the positional gradients
+    def bwd_unfused_all():                      # T > 256: kernels + un-shift pass + the two batched products of the positional gradients
         dbias = hip.relpos_attn_bwd(qu, k, v, bias, aux, dctx, dqkv[:, :d], dqkv[:, d:2 * d], dqkv[:, 2 * d:], B, H, T, dh, scale, p_drop, 11)
         dps = hip.relshift_bwd(dbias)
         hip.gemm(dps, pos, a_kc=True, b_kc=False, M=T, N=dh, K=T, lda=T, ldb=d, nbatch=B * H, batch_inner=H,

@@ -1,12 +1,23 @@
 #!/usr/bin/env python
 """Fused feed-forward launch (csrc/ffn2.hip) against the two GEMM launches it replaces, forward and backward, at the step's shapes
-(M = 16384; d = 256: spat encoder, d = 512: spec encoder).  Event-timed loops of 20 on rotating buffer sets (cold operands)."""
+(M = 16384; d = 256: spat encoder, d = 512: spec encoder).  Event-timed loops of 20 on rotating buffer sets (cold operands).
+
+    python tools/bench_ffn2.py [--hybrid | --hybrid-stamps]          # shipped library
+    FFN_ABL=<mask> python tools/bench_ffn2.py [--hybrid]              # probe build (tools/probe_lib.py, -DFFN_ABL=<mask> -DSARSSL_PROBE_ENV)
+
+FFN_ABL builds are timing-only ablations of csrc/ffn2.hip / ffn2h.hip (the bits are listed there; their results are wrong by construction);
+the probe build also reads SARSSL_FFN_ROT (0: no chunk rotation), which the shipped library does not."""
 import os
 import sys
 
-import torch
-
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+if os.environ.get("FFN_ABL") and "SARSSL_HIP_LIB" not in os.environ:
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    from probe_lib import probe_lib
+    os.environ["SARSSL_HIP_LIB"] = probe_lib("ffnabl%d" % int(os.environ["FFN_ABL"]), ["-DFFN_ABL=%d" % int(os.environ["FFN_ABL"]), "-DSARSSL_PROBE_ENV"])
+
+import torch  # noqa: E402
+
 import sarssl_boot  # noqa: E402,F401
 from sar_ssl_amd import hip  # noqa: E402
 
@@ -52,8 +63,8 @@ def hybrid(dev, M, NSET=6):
                                res_scale=1.0)
             tf, tu = timed(fused), timed(unfused)
             issued = 2.0 * M * d * H * ((3 if ap else 2) + 2)
-            print("hybrid d=256 act_pair=%d p=%.1f  fwd fused %.1f us (%.0f TF/s issued) | LayerNorm + two launches %.1f us   [SARSSL_FFN_ROT=%s]"
-                  % (ap, p, tf, issued / tf * 1e-6, tu, os.environ.get("SARSSL_FFN_ROT", "0")), flush=True)
+            print("hybrid d=256 act_pair=%d p=%.1f  fwd fused %.1f us (%.0f TF/s issued) | LayerNorm + two launches %.1f us   [FFN_ABL=%s]"
+                  % (ap, p, tf, issued / tf * 1e-6, tu, os.environ.get("FFN_ABL", "0")), flush=True)
 
 
 def hybrid_stamps(dev, M):
