@@ -38,9 +38,9 @@ struct ConvArgs {
     const float* scale; const float* shift; int prologue;
     int nb, F, T;
     int part_in, part_w;
-    double* stats;      // optional f64[128]: per-channel sum / sum of squares of the (bf16-rounded) output, for the next BatchNorm
-    // data-gradient mode of the ping-pong kernel: the output is dz = dL/d relu(bn(y)) of the PREVIOUS layer; with bn_y / bn_aff set,
-    // stats instead receives that BatchNorm's backward sums [sum g | sum g*xhat], g = dz * relu'(bn(y)) (the cl_bn_bwd_reduce pass)
+    double* stats;      // optional f64[128] (16-bit launches): per-channel sum / sum of squares of the rounded output, for the next BatchNorm
+    // data-gradient mode of the ping-pong kernel (BNRED): the output is dz = dL/d relu(bn(y)) of the PREVIOUS layer; with bn_y / bn_aff
+    // set, stats instead receives that BatchNorm's backward sums [sum g | sum g*xhat], g = dz * relu'(bn(y)) (the cl_bn_bwd_reduce pass)
     const void* bn_y;   // (B,F,T,64) pre-BN activations of the layer whose input gradient this launch produces
     const float* bn_aff;    // [4][64]: scale, shift, mean, rstd
     int prio;           // != 0: raise the wave's issue priority for its MFMA phase (s_setprio), see sarssl_mfma_prio()
@@ -48,11 +48,11 @@ struct ConvArgs {
     // on relu(bn1(W1 a0)) formed while staging (c1_w = W1 f32[64][4], scale / shift = bn1's affine) - the 64-channel output of the
     // first 1x1 layer is never stored or read (2 x 537 MB per encoder and pass at B = 64)
     const float* c1_w;
-    // first-layer REDUCTION mode of the ping-pong kernel (C1RED): the launch is the data gradient of the first 3x3 convolution and its
-    // result dz1 = dL/d relu(bn1(W1 a0)) is only needed for the first layer's parameter gradients, so it is never stored: the epilogue
-    // masks it with relu'(bn1(W1 a0)) (one MFMA per accumulator tile recomputes the pre-activation from c1_a0 / c1_w / scale / shift)
-    // and contracts it over the pixels against [a0 | 1] on the matrix cores: c1_red (f64[644], sarssl_stem_c1_bwd's layout) receives
-    // G[co][c] = sum_p g a0[c] and s1[co] = sum_p g
+    // first-layer reduction (conv3x3_dgrad_c1red_ws_kernel, the only kernel that reads these two): the launch is the data gradient of
+    // the first 3x3 convolution and its result dz1 = dL/d relu(bn1(W1 a0)) is only needed for the first layer's parameter gradients, so
+    // it is never stored (out = stats = null, no staging prologue): the epilogue masks it with relu'(bn1(W1 a0)) (one MFMA per accumulator
+    // tile recomputes the pre-activation from c1_a0 / c1_w / scale / shift) and contracts it over the pixels against [a0 | 1] on the
+    // matrix cores: c1_red (f64[644], sarssl_stem_c1_bwd's layout) receives G[co][c] = sum_p g a0[c] and s1[co] = sum_p g
     const void* c1_a0; double* c1_red;
     // optional clock probe (sarssl_conv_clock_probe): thread 0 of workgroup 0 stores {s_memtime, s_memrealtime} at kernel entry and
     // exit - shader-clock ticks over constant-rate ticks = the effective shader clock this launch ran at (bench.py reports it next to
@@ -164,28 +164,23 @@ __device__ __forceinline__ int xcd_tile(int it, int bid, int grid) {
     return it * grid + bid;
 }
 
-template <typename T, typename TW>
+// f32 storage only (the 16-bit launches take the ping-pong kernel below): operands are split to bf16 parts while staged
 __global__ __launch_bounds__(512) void conv3x3_fwd_kernel(ConvArgs a) {
     __shared__ __attribute__((aligned(16))) uint16_t sW[W_ELEMS];
     __shared__ __attribute__((aligned(16))) uint16_t sX[X_ELEMS];
-    __shared__ float sStats[8][128];               // per-wave partial statistics, folded in wave order at the end (deterministic)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int F = a.F, Tn = a.T;
     const int tiles_f = (F + TR - 1) / TR, tiles_t = (Tn + TCOL - 1) / TCOL;
     const int ntiles = a.nb * tiles_f * tiles_t;
-    const T* in = (const T*)a.in;
-    for (int q = tid; q < 8 * 128; q += 512) (&sStats[0][0])[q] = 0.f;
+    const float* in = (const float*)a.in;
     const int cch = tid & 7;                        // this thread's 8-channel chunk (fixed: 512 % 8 == 0)
 
     // weights -> LDS once ([tap][co][ci], ci contiguous)
     {
-        const TW* w = (const TW*)a.w;
+        const float* w = (const float*)a.w;
         for (int q = tid; q < 9 * 64 * 8; q += 512) {
             const int p = q >> 3, c = q & 7;
-            uint4 u;
-            if constexpr (sizeof(TW) == 2) u = *(const uint4*)(w + (long)p * 64 + c * 8);
-            else { f8 v = ld8(w + (long)p * 64 + c * 8); u = pack8_part(v, a.part_w); }
-            *(uint4*)&sW[swz(p, c)] = u;
+            *(uint4*)&sW[swz(p, c)] = pack8_part(ld8(w + (long)p * 64 + c * 8), a.part_w);
         }
     }
     float sc[8], sh[8];
@@ -206,16 +201,16 @@ __global__ __launch_bounds__(512) void conv3x3_fwd_kernel(ConvArgs a) {
             for (int kw = 0; kw < 3; ++kw) laneX[kw][kc] = swzx(wave * HC + l31 + kw, l31 + kw, kc * 2 + hi);
         }
     }
-    Chunk<T> regs[X_ITERS];
+    Chunk<float> regs[X_ITERS];
     const int pc = tid >> 3;
     auto issue_loads = [&](int tile) {
         const TileCoord tc = tile_coord(tile, tiles_f, tiles_t);
         const int t = tc.t0 - 1 + pc;
 #pragma unroll
-        for (int i = 0; i < HR; ++i) regs[i] = load_chunk_clamped<T>(in, tc.b, tc.f0 - 1 + i, t, F, Tn, cch * 8);
+        for (int i = 0; i < HR; ++i) regs[i] = load_chunk_clamped<float>(in, tc.b, tc.f0 - 1 + i, t, F, Tn, cch * 8);
         {
             const int hr = pc >> 1, te = tc.t0 + TCOL - 1 + (pc & 1);       // (threads >= 160: an unused, harmless extra chunk)
-            regs[HR] = load_chunk_clamped<T>(in, tc.b, tc.f0 - 1 + hr, te, F, Tn, cch * 8);
+            regs[HR] = load_chunk_clamped<float>(in, tc.b, tc.f0 - 1 + hr, te, F, Tn, cch * 8);
         }
     };
     auto write_tile = [&](int tile) {
@@ -225,11 +220,11 @@ __global__ __launch_bounds__(512) void conv3x3_fwd_kernel(ConvArgs a) {
 #pragma unroll
         for (int i = 0; i < HR; ++i) {
             const int f = tc.f0 - 1 + i;
-            *(uint4*)&sX[swzx(i * HC + pc, pc, cch)] = xform_chunk<T>(regs[i], tv && f >= 0 && f < F, a.prologue, sc, sh, a.part_in);
+            *(uint4*)&sX[swzx(i * HC + pc, pc, cch)] = xform_chunk<float>(regs[i], tv && f >= 0 && f < F, a.prologue, sc, sh, a.part_in);
         }
         if (tid < 160) {
             const int hr = pc >> 1, f = tc.f0 - 1 + hr, te = tc.t0 + TCOL - 1 + (pc & 1);
-            *(uint4*)&sX[swzx(hr * HC + TCOL + (pc & 1), TCOL + (pc & 1), cch)] = xform_chunk<T>(regs[HR], f >= 0 && f < F && te < Tn, a.prologue, sc, sh, a.part_in);
+            *(uint4*)&sX[swzx(hr * HC + TCOL + (pc & 1), TCOL + (pc & 1), cch)] = xform_chunk<float>(regs[HR], f >= 0 && f < F && te < Tn, a.prologue, sc, sh, a.part_in);
         }
     };
 
@@ -289,66 +284,8 @@ __global__ __launch_bounds__(512) void conv3x3_fwd_kernel(ConvArgs a) {
         __builtin_amdgcn_s_waitcnt(0x0F70);                    // vmcnt(0), expcnt / lgkmcnt untouched
         const TileCoord tc = tile_coord(tile, tiles_f, tiles_t);
         const int f = tc.f0 + wave;
-        if constexpr (sizeof(T) == 2) {
-            // Output path (bf16).  The accumulators (lane = pixel, 4 consecutive channels per register group) are transposed
-            // through the wave's own 8 KiB slice of the now idle input-tile LDS so that 8 consecutive lanes hold one pixel's
-            // 128-byte line: 8 fully coalesced 16-byte stores per lane (1 KiB contiguous per instruction) instead of 16
-            // scattered 8-byte stores that each touch 32 cache lines (store-issue bound: ~40 % of the kernel).
-            __syncthreads();                                   // every wave is done reading the input tile
-            uint16_t* stg = sX + wave * (64 * 64);             // [64 px][64 co], 16-byte chunk index XOR (px & 7)
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    const int px = j * 32 + (lane & 31);
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) {
-                        const int co = i * 32 + 8 * g + 4 * (lane >> 5);
-                        uint2 w2;
-                        w2.x = pack2_bf16(acc[i][j][g * 4 + 0], acc[i][j][g * 4 + 1]);
-                        w2.y = pack2_bf16(acc[i][j][g * 4 + 2], acc[i][j][g * 4 + 3]);
-                        *(uint2*)&stg[px * 64 + (((co >> 3) ^ (px & 7)) << 3) + (co & 7)] = w2;
-                    }
-                }
-            // the staging slice is private to this wave: its own LDS writes only have to land (no workgroup barrier)
-            __builtin_amdgcn_s_waitcnt(0xC07F);                // lgkmcnt(0)
-            __builtin_amdgcn_wave_barrier();
-            float ssum[8], ssq[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) { ssum[e] = 0.f; ssq[e] = 0.f; }
-            if (f < F) {
-#pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    const int px = (lane >> 3) + 8 * k;
-                    const int t = tc.t0 + px;
-                    const uint4 o = *(const uint4*)&stg[px * 64 + (((lane & 7) ^ (px & 7)) << 3)];
-                    if (t < Tn) {
-                        *(uint4*)((uint16_t*)a.out + (((long)tc.b * F + f) * Tn + t) * 64 + (lane & 7) * 8) = o;
-                        if (a.stats) {          // BatchNorm statistics of exactly what was stored (8 channels of this lane's chunk)
-                            const uint32_t w[4] = {o.x, o.y, o.z, o.w};
-#pragma unroll
-                            for (int q = 0; q < 4; ++q) {
-                                const float lo = bf16_bits_to_f32(w[q] & 0xffffu), hi = __uint_as_float(w[q] & 0xffff0000u);
-                                ssum[2 * q] += lo; ssq[2 * q] += lo * lo; ssum[2 * q + 1] += hi; ssq[2 * q + 1] += hi * hi;
-                            }
-                        }
-                    }
-                }
-            }
-            if (a.stats) {
-                // lanes that share a channel chunk are 8 apart: butterfly over lane bits 3..5, then one LDS atomic per channel
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    ssum[e] += __shfl_xor(ssum[e], 8, 64); ssum[e] += __shfl_xor(ssum[e], 16, 64); ssum[e] += __shfl_xor(ssum[e], 32, 64);
-                    ssq[e] += __shfl_xor(ssq[e], 8, 64); ssq[e] += __shfl_xor(ssq[e], 16, 64); ssq[e] += __shfl_xor(ssq[e], 32, 64);
-                }
-                if (lane < 8) {
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) { sStats[wave][lane * 8 + e] += ssum[e]; sStats[wave][64 + lane * 8 + e] += ssq[e]; }   // this wave's own slot: no race
-                }
-            }
-        } else if (f < F) {
-            // f32 storage (precise mode): lane = pixel, 4 consecutive co per register group; split-pass accumulation workspace
+        if (f < F) {
+            // lane = pixel, 4 consecutive co per register group; split-pass accumulation workspace (precise mode)
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 const int t = tc.t0 + j * 32 + (lane & 31);
@@ -365,18 +302,12 @@ __global__ __launch_bounds__(512) void conv3x3_fwd_kernel(ConvArgs a) {
                                 v.x += w4.x; v.y += w4.y; v.z += w4.z; v.w += w4.w;
                             }
                             if (a.acc_out) *(float4*)(a.acc_ws + pix + co) = v;
-                            else st4((T*)a.out + pix + co, v);
+                            else st4((float*)a.out + pix + co, v);
                         }
                 }
             }
         }
         __syncthreads();
-    }
-    if (a.stats && tid < 128) {
-        float s = 0.f;
-#pragma unroll
-        for (int w = 0; w < 8; ++w) s += sStats[w][tid];
-        atomicAdd(&a.stats[tid], (double)s);
     }
 }
 
@@ -436,17 +367,14 @@ __device__ __forceinline__ void half_barrier(unsigned* cnt, unsigned& epoch, int
 }
 
 // TM: encoding of the input / weights / LDS operands / output (bf16, or fp16 for the forward launches of the fp16-forward mode);
-// TY: encoding of the tensors SAVED BY THE FORWARD PASS that the gradient epilogues read (bn_y, c1_a0)
-template <bool BNRED, bool C1IN = false, bool C1RED = false, typename TM = bf16, typename TY = bf16>
+// TY: encoding of the tensor SAVED BY THE FORWARD PASS that the BNRED epilogue reads (bn_y)
+template <bool BNRED, bool C1IN = false, typename TM = bf16, typename TY = bf16>
 __global__ __launch_bounds__(512) void conv3x3_fwd_pp_kernel(ConvArgs a) {
     typedef TM T;
-    static_assert(!C1RED || __is_same(TM, bf16), "gradient launches contract in bf16");
+    static_assert(!BNRED || __is_same(TM, bf16), "gradient launches contract in bf16");
     __shared__ __attribute__((aligned(16))) uint16_t sW[W_ELEMS];
     __shared__ __attribute__((aligned(16))) uint16_t sXh[2][PX_ELEMS];
     __shared__ float sAff[BNRED ? 256 : 1];
-    // C1RED: MFMA "A" fragments of the scale-folded first-layer weights, [co][16 k]: k 0..3 = bf16 high parts of scale*W1[co][c], 4 = of
-    // shift, 8..12 = the low parts (the input fragment repeats [a0 | 1] in both k halves: one MFMA gives the f32-accurate pre-activation)
-    __shared__ __attribute__((aligned(16))) uint16_t sC1[C1RED ? 64 * 16 : 8];
     __shared__ unsigned sSync[2];
     const int tid = threadIdx.x, lane = tid & 63;
     // wave-uniform ids as SCALARS (hipcc cannot prove tid >> 6 uniform): the tile coordinates (two integer divisions), row bases and
@@ -462,14 +390,6 @@ __global__ __launch_bounds__(512) void conv3x3_fwd_pp_kernel(ConvArgs a) {
     if (a.clk && blockIdx.x == 0 && tid == 0) { a.clk[0] = __builtin_amdgcn_s_memtime(); a.clk[1] = __builtin_amdgcn_s_memrealtime(); }
     if (tid < 2) sSync[tid] = 0u;
     if (BNRED && tid < 256) sAff[tid] = a.bn_aff[tid];
-    if (C1RED) {
-        for (int q = tid; q < 64 * 16; q += 512) {
-            const int co = q >> 4, k = q & 15, c = k & 7;
-            const float v = c < 4 ? a.scale[co] * a.c1_w[co * 4 + c] : (c == 4 ? a.shift[co] : 0.f);
-            const uint32_t hi = f32_to_bf16_bits(v);
-            sC1[q] = (uint16_t)(k < 8 ? hi : f32_to_bf16_bits(v - bf16_bits_to_f32(hi)));
-        }
-    }
     const int cch = tid & 7;
     {
         const T* w = (const T*)a.w;
@@ -564,11 +484,6 @@ __global__ __launch_bounds__(512) void conv3x3_fwd_pp_kernel(ConvArgs a) {
             bthr[e] = thr;
         }
     }
-    float gacc[2][4];                              // C1RED: lanes < 32: G[c = r][co = nb*32 + lane]; lanes >= 32: r = 0: s1[co = nb*32 + lane - 32]
-#pragma unroll
-    for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) gacc[nb][r] = 0.f;
     const int nrounds = (npairs + gridDim.x - 1) / gridDim.x;
     int tile = tile_of(0);
     TileCoord tc = coord(tile < ntiles ? tile : 0);
@@ -635,87 +550,9 @@ __global__ __launch_bounds__(512) void conv3x3_fwd_pp_kernel(ConvArgs a) {
                 yv[k] = *(const uint4*)((const uint16_t*)a.bn_y + (((long)tc.b * F + f) * Tn + t) * 64 + (lane & 7) * 8);
             }
         }
-        uint2 av[C1RED ? 2 : 1];                               // C1RED: the 4 input channels of this lane's pixel (lane & 31) in both rows
-        bool pv[C1RED ? 2 : 1];
-        if (C1RED) {
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const int f = tc.f0 + 2 * hw + j, t = tc.t0 + (lane & 31);
-                pv[j] = f < F && t < Tn;
-                av[j] = *(const uint2*)((const uint16_t*)a.c1_a0 + (((long)tc.b * F + min(f, F - 1)) * Tn + min(t, Tn - 1)) * 4);
-            }
-        }
         half_barrier(cnt, epoch, lane);                        // the half is done reading its input tile
         STAMP(6);
         uint16_t* stg = sX + hw * (64 * 64);                   // this wave's [64 px][64 co] slice (px = row * 32 + column)
-        if (C1RED) {
-            // (1) mask: pre-activation tile of the first layer in the accumulators' own layout (co x pixel), one MFMA per tile
-            __builtin_amdgcn_s_waitcnt(0x0F70);                // av landed (the next tile's prefetch too: it had the whole MFMA loop)
-            if constexpr (!__is_same(TY, bf16)) {              // saved fp16 input -> the bf16 operand of the two first-layer contractions below
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    av[j].x = pack2_bf16(H16<TY>::lo(av[j].x), H16<TY>::hi(av[j].x));
-                    av[j].y = pack2_bf16(H16<TY>::lo(av[j].y), H16<TY>::hi(av[j].y));
-                }
-            }
-            uint16_t* a0t = sX + 4 * (64 * 64) + hw * 256;     // [4 c][64 px] of this wave, in the part of the input tile no slice uses
-            {
-                const int j = lane >> 5;                       // lanes < 32 file row 0, lanes >= 32 row 1 (both hold both rows' pixels)
-                const uint2 q = j ? av[1] : av[0];
-                uint16_t* d = a0t + j * 32 + (lane & 31);
-                d[0] = (uint16_t)(q.x & 0xffffu); d[64] = (uint16_t)(q.x >> 16); d[128] = (uint16_t)(q.y & 0xffffu); d[192] = (uint16_t)(q.y >> 16);
-            }
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const bf16x8 wfr = *(const bf16x8*)&sC1[(i * 32 + (lane & 31)) * 16 + (lane >> 5) * 8];
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    union { uint4 u; bf16x8 b; } bx;
-                    bx.u = make_uint4(av[j].x, av[j].y, 0x00003f80u, 0u);          // [a0_0..a0_3, 1, 0, 0, 0]
-                    f32x16 y;
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) y[r] = 0.f;
-                    y = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wfr, bx.b, y, 0, 0, 0);
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) acc[i][j][r] = (y[r] > 0.f && pv[j]) ? acc[i][j][r] : 0.f;
-                }
-            }
-            // (2) masked gradient tile, bf16, [64 px][64 co] in the transpose-read layout (swz)
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int g = 0; g < 4; ++g)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j) {
-                        uint2 w2;
-                        w2.x = pack2_bf16(acc[i][j][g * 4 + 0], acc[i][j][g * 4 + 1]);
-                        w2.y = pack2_bf16(acc[i][j][g * 4 + 2], acc[i][j][g * 4 + 3]);
-                        *(uint2*)(stg + swz(j * 32 + (lane & 31), i * 4 + g) + 4 * (lane >> 5)) = w2;
-                    }
-            __builtin_amdgcn_s_waitcnt(0xC07F);
-            __builtin_amdgcn_wave_barrier();
-            // (3) G[c'][co] += sum_px [a0 | 1][px][c'] * g[px][co]: 4 k-steps of 16 pixels x 2 channel halves
-            f32x16 d2[2];
-#pragma unroll
-            for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) d2[nb][r] = 0.f;
-            const int m = lane & 31;
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) {
-                union { uint4 u; bf16x8 b; } ax;
-                ax.u = *(const uint4*)(a0t + min(m, 3) * 64 + ks * 16 + (lane >> 5) * 8);
-                if (m == 4) ax.u = make_uint4(0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u);
-                else if (m > 4) ax.u = make_uint4(0u, 0u, 0u, 0u);
-#pragma unroll
-                for (int nb = 0; nb < 2; ++nb)
-                    d2[nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ax.b, tr_frag(stg, ks * 16, nb * 32, lane), d2[nb], 0, 0, 0);
-            }
-#pragma unroll
-            for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) gacc[nb][r] += d2[nb][r];
-        } else {
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -789,7 +626,6 @@ __global__ __launch_bounds__(512) void conv3x3_fwd_pp_kernel(ConvArgs a) {
                 }
             }
         }
-        }
         STAMP(8);
         STAMP(9);
         half_barrier(cnt, epoch, lane);                        // slices drained before the next tile overwrites the buffer
@@ -804,7 +640,7 @@ __global__ __launch_bounds__(512) void conv3x3_fwd_pp_kernel(ConvArgs a) {
     // channel of f32-valued terms: exact (order-free) as long as the terms' exponents span < 2^20.
     __syncthreads();                               // every wave is done with sW
     if (a.clk && blockIdx.x == 0 && tid == 0) { a.clk[2] = __builtin_amdgcn_s_memtime(); a.clk[3] = __builtin_amdgcn_s_memrealtime(); }
-    float* part = (float*)sW;                      // [8 waves][128] statistics, then [8][320] first-layer sums (C1RED)
+    float* part = (float*)sW;                      // [8 waves][128] statistics
     if (BNRED || a.stats) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
@@ -827,42 +663,26 @@ __global__ __launch_bounds__(512) void conv3x3_fwd_pp_kernel(ConvArgs a) {
             atomicAdd(&a.stats[tid], (double)s);
         }
     }
-    if (C1RED) {                                   // fold the 8 waves through LDS in wave order, then f64 atomics
-        float* fold = part + 1024;                 // [8][320]: [0,256) G[co][c], [256,320) s1[co]
-#pragma unroll
-        for (int nb = 0; nb < 2; ++nb) {
-            const int co = nb * 32 + (lane & 31);
-            if (lane < 32) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) fold[wave * 320 + co * 4 + r] = gacc[nb][r];
-            } else fold[wave * 320 + 256 + co] = gacc[nb][0];
-        }
-        __syncthreads();
-        for (int q = tid; q < 320; q += 512) {
-            float s = 0.f;
-#pragma unroll
-            for (int w = 0; w < 8; ++w) s += fold[w * 320 + q];
-            atomicAdd(&a.c1_red[q < 256 ? q : 512 + (q - 256)], (double)s);
-        }
-    }
 }
 
-// Role-split variant of conv3x3_fwd_pp_kernel (12 waves, three per SIMD, <= 168 registers): waves 0-7 are the two tile groups of the
-// ping-pong kernel WITHOUT their staging phases - wait for the tile, MFMA phase, accumulators -> LDS, drain / statistics / epilogues,
-// release the buffer; waves 8-11 only stage: for each group in turn wait until its buffer is released, write the prefetched tile
-// (BatchNorm + ReLU or the first-layer prologue), publish it, request the group's next tile.  Staging (2.6 k cycles), its barrier and
-// the prefetch issue (2.1 k) leave the MFMA waves' 16.7 k-cycle iteration.  LDS arrival counters: sReady[g] (4 staging waves per tile),
-// sFree[g] (4 MFMA waves per tile), sSync[g] (the group's own barrier between its MFMA phase and the accumulator hand-over).
-template <bool BNRED, bool C1IN = false, bool C1RED = false, typename TM = bf16, typename TY = bf16>
-__global__ __launch_bounds__(768) void conv3x3_fwd_ws_kernel(ConvArgs a) {
-    typedef TM T;
-    static_assert(!C1RED || __is_same(TM, bf16), "gradient launches contract in bf16");
+// Data gradient of the first 3x3 convolution, consumed in its epilogue (ConvArgs::c1_a0 / c1_red): the role-split variant of
+// conv3x3_fwd_pp_kernel (12 waves, three per SIMD, <= 168 registers).  Waves 0-7 are the two tile groups of the ping-pong kernel WITHOUT
+// their staging phases - wait for the tile, MFMA phase, mask, masked tile -> LDS, contraction against [a0 | 1], release the buffer;
+// waves 8-11 only stage: for each group in turn wait until its buffer is released, copy the prefetched tile (identity prologue, chunks
+// outside the image zeroed), publish it, request the group's next tile.  Staging, its barrier and the prefetch issue leave the MFMA
+// waves' iteration.  LDS arrival counters: sReady[g] (4 staging waves per tile), sFree[g] (4 MFMA waves per tile), sSync[g] (the group's
+// own barrier between its MFMA phase and the accumulator hand-over).  Nothing is stored per pixel and no statistics are formed: the
+// forward, plain data-gradient and BatchNorm-sum launches were measured slower under this role split (see conv_persistent_grid) and
+// take the ping-pong kernel.  TY: encoding of the saved input a0; gradient and taps are bf16.
+// (Formerly conv3x3_fwd_ws_kernel<false, false, true, bf16, TY>: NOTES.md 4.1 and the recorded profiles use that name.)
+template <typename TY>
+__global__ __launch_bounds__(768) void conv3x3_dgrad_c1red_ws_kernel(ConvArgs a) {
+    typedef bf16 T;
     __shared__ __attribute__((aligned(16))) uint16_t sW[W_ELEMS];
     __shared__ __attribute__((aligned(16))) uint16_t sXh[2][PX_ELEMS];
-    __shared__ float sAff[BNRED ? 256 : 1];
-    // C1RED: MFMA "A" fragments of the scale-folded first-layer weights, [co][16 k]: k 0..3 = bf16 high parts of scale*W1[co][c], 4 = of
+    // MFMA "A" fragments of the scale-folded first-layer weights, [co][16 k]: k 0..3 = bf16 high parts of scale*W1[co][c], 4 = of
     // shift, 8..12 = the low parts (the input fragment repeats [a0 | 1] in both k halves: one MFMA gives the f32-accurate pre-activation)
-    __shared__ __attribute__((aligned(16))) uint16_t sC1[C1RED ? 64 * 16 : 8];
+    __shared__ __attribute__((aligned(16))) uint16_t sC1[64 * 16];
     __shared__ unsigned sSync[2], sReady[2], sFree[2];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave_all = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -879,14 +699,11 @@ __global__ __launch_bounds__(768) void conv3x3_fwd_ws_kernel(ConvArgs a) {
     uint16_t* sX = sXh[half];                      // MFMA waves: their group's tile buffer
     if (a.clk && blockIdx.x == 0 && tid == 0) { a.clk[0] = __builtin_amdgcn_s_memtime(); a.clk[1] = __builtin_amdgcn_s_memrealtime(); }
     if (tid < 2) { sSync[tid] = 0u; sReady[tid] = 0u; sFree[tid] = 0u; }
-    if (BNRED && tid < 256) sAff[tid] = a.bn_aff[tid];
-    if (C1RED) {
-        for (int q = tid; q < 64 * 16; q += 768) {
-            const int co = q >> 4, k = q & 15, c = k & 7;
-            const float v = c < 4 ? a.scale[co] * a.c1_w[co * 4 + c] : (c == 4 ? a.shift[co] : 0.f);
-            const uint32_t hi = f32_to_bf16_bits(v);
-            sC1[q] = (uint16_t)(k < 8 ? hi : f32_to_bf16_bits(v - bf16_bits_to_f32(hi)));
-        }
+    for (int q = tid; q < 64 * 16; q += 768) {
+        const int co = q >> 4, k = q & 15, c = k & 7;
+        const float v = c < 4 ? a.scale[co] * a.c1_w[co * 4 + c] : (c == 4 ? a.shift[co] : 0.f);
+        const uint32_t hi = f32_to_bf16_bits(v);
+        sC1[q] = (uint16_t)(k < 8 ? hi : f32_to_bf16_bits(v - bf16_bits_to_f32(hi)));
     }
     const int cch = tid & 7;
     {
@@ -899,40 +716,27 @@ __global__ __launch_bounds__(768) void conv3x3_fwd_ws_kernel(ConvArgs a) {
     __syncthreads();                                // weights, counters (the only workgroup-wide barrier before the end)
     // ------------------------------------------------------------------------------------------------ staging waves
     if (producer) {
-        float sc[8], sh[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            sc[e] = a.prologue ? a.scale[cch * 8 + e] : 1.f; sh[e] = a.prologue ? a.shift[cch * 8 + e] : 0.f;
-        }
-        C1Const kc1;
-        if (C1IN) c1_setup(kc1, a.c1_w, a.scale, a.shift, cch * 8);
-
         // staging: thread of the half = (pixel column pc = htid >> 3 of 32, chunk): halo rows 0..9 + one chunk of halo columns 32 / 33
         Chunk<T> regsg[2][X_ITERS];                    // one prefetched tile per group
         const int pc = htid >> 3;
         // addresses: row bases are scalar (tile coordinates are wave-uniform), each thread adds ONE byte offset (its clamped frame and chunk)
         auto issue_loads = [&](Chunk<T> (&regs)[X_ITERS], const TileCoord tc) __attribute__((always_inline)) {
             const int tcl = min(max(tc.t0 - 1 + pc, 0), Tn - 1);
-            const unsigned voff = C1IN ? (unsigned)tcl * 8u : (unsigned)(tcl * 64 + cch * 8) * 2u;
+            const unsigned voff = (unsigned)(tcl * 64 + cch * 8) * 2u;
             // one 64-bit base per tile (the image), 32-bit row offsets inside it (an image is < 4 GB): round-3 stamps showed this phase at
             // 2.8 k cycles per half tile for 12 loads - ~14 scalar instructions of 64-bit multiply / add per row sat in front of every load
-            constexpr unsigned PXB = C1IN ? 8u : 128u;                               // bytes per pixel
+            constexpr unsigned PXB = 128u;                                           // bytes per pixel
             const char* pimg = (const char*)in + (long)tc.b * F * (long)Tn * PXB;
             const unsigned rowbytes = (unsigned)Tn * PXB;
 #pragma unroll
             for (int i = 0; i < HR; ++i) {
                 const int f = min(max(tc.f0 - 1 + i, 0), F - 1);                      // (clamped: unconditional loads, see load_chunk_clamped)
                 const char* prow = pimg + (unsigned)f * rowbytes;
-                if (C1IN) { const uint2 q = *(const uint2*)(prow + voff); regs[i].u = make_uint4(q.x, q.y, 0u, 0u); }
-                else regs[i].u = *(const uint4*)(prow + voff);
+                regs[i].u = *(const uint4*)(prow + voff);
             }
             {
                 const int hr = pc >> 1, te = tc.t0 + PTC - 1 + (pc & 1);        // (threads >= 160: an unused, harmless extra chunk)
-                if (C1IN) {
-                    const int f = min(max(tc.f0 - 1 + hr, 0), F - 1), t = min(max(te, 0), Tn - 1);
-                    const uint2 q = *(const uint2*)(in + (((long)tc.b * F + f) * Tn + t) * 4);
-                    regs[HR].u = make_uint4(q.x, q.y, 0u, 0u);
-                } else regs[HR] = load_chunk_clamped<T>(in, tc.b, tc.f0 - 1 + hr, te, F, Tn, cch * 8);
+                regs[HR] = load_chunk_clamped<T>(in, tc.b, tc.f0 - 1 + hr, te, F, Tn, cch * 8);
             }
         };
         auto write_tile = [&](const Chunk<T> (&regs)[X_ITERS], const TileCoord tc, uint16_t* __restrict__ sX) __attribute__((always_inline)) {
@@ -942,17 +746,14 @@ __global__ __launch_bounds__(768) void conv3x3_fwd_ws_kernel(ConvArgs a) {
             for (int i = 0; i < HR; ++i) {
                 const int f = tc.f0 - 1 + i;
                 const bool ok = tv && f >= 0 && f < F;
-                *(uint4*)&sX[swzx(i * PHC + pc, pc, cch)] = C1IN ? c1_chunk<T>(regs[i].u.x, regs[i].u.y, ok, kc1)
-                                                                 : xform_chunk<T>(regs[i], ok, a.prologue, sc, sh, 0);
+                *(uint4*)&sX[swzx(i * PHC + pc, pc, cch)] = ok ? regs[i].u : make_uint4(0, 0, 0, 0);
             }
             if (htid < 160) {
                 const int hr = pc >> 1, f = tc.f0 - 1 + hr, te = tc.t0 + PTC - 1 + (pc & 1);
                 const bool ok = f >= 0 && f < F && te < Tn;
-                *(uint4*)&sX[swzx(hr * PHC + PTC + (pc & 1), PTC + (pc & 1), cch)] = C1IN ? c1_chunk<T>(regs[HR].u.x, regs[HR].u.y, ok, kc1)
-                                                                                           : xform_chunk<T>(regs[HR], ok, a.prologue, sc, sh, 0);
+                *(uint4*)&sX[swzx(hr * PHC + PTC + (pc & 1), PTC + (pc & 1), cch)] = ok ? regs[HR].u : make_uint4(0, 0, 0, 0);
             }
         };
-
 
         auto coord = [&](int tile) __attribute__((always_inline)) { TileCoord c; c.t0 = (tile % tiles_t) * PTC; tile /= tiles_t; c.f0 = (tile % tiles_f) * TR; c.b = tile / tiles_f; return c; };
         auto tile_g = [&](int it, int g) __attribute__((always_inline)) { const int pr = xcd_tile(it, blockIdx.x, gridDim.x); return pr < npairs ? pr * 2 + g : ntiles; };
@@ -977,10 +778,9 @@ __global__ __launch_bounds__(768) void conv3x3_fwd_ws_kernel(ConvArgs a) {
                 if (next < ntiles) issue_loads(regsg[g], coord(next));
             }
         }
-        // the MFMA waves' final folds run behind workgroup barriers: take part in the same sequence
+        // the MFMA waves' final fold runs behind two workgroup barriers: take part in both
         __syncthreads();
-        if (BNRED || a.stats) __syncthreads();
-        if (C1RED) __syncthreads();
+        __syncthreads();
         return;
     }
     // ------------------------------------------------------------------------------------------------ MFMA waves
@@ -1000,22 +800,7 @@ __global__ __launch_bounds__(768) void conv3x3_fwd_ws_kernel(ConvArgs a) {
 
     unsigned epoch = 0;
     unsigned* cnt = &sSync[half];
-    float ssum[8], ssq[8];                         // this thread's 8 output channels ((lane & 7) * 8 + e), summed over all its tiles
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { ssum[e] = 0.f; ssq[e] = 0.f; }
-    float bthr[8];                                 // BNRED: relu'(y*sc + sh) as a threshold test on y (see cl_bn_bwd_reduce), lane-constant
-    unsigned bsgn = 0u;
-    if (BNRED) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const int c = (lane & 7) * 8 + e;
-            const float sc_ = sAff[c], sh_ = sAff[64 + c];
-            float thr = sc_ != 0.f ? -sh_ / sc_ : (sh_ > 0.f ? -INFINITY : INFINITY);
-            if (sc_ < 0.f) { thr = -thr; bsgn |= 1u << e; }
-            bthr[e] = thr;
-        }
-    }
-    float gacc[2][4];                              // C1RED: lanes < 32: G[c = r][co = nb*32 + lane]; lanes >= 32: r = 0: s1[co = nb*32 + lane - 32]
+    float gacc[2][4];                              // lanes < 32: G[c = r][co = nb*32 + lane]; lanes >= 32: r = 0: s1[co = nb*32 + lane - 32]
 #pragma unroll
     for (int nb = 0; nb < 2; ++nb)
 #pragma unroll
@@ -1046,8 +831,8 @@ __global__ __launch_bounds__(768) void conv3x3_fwd_ws_kernel(ConvArgs a) {
 #pragma unroll
                 for (int j = 0; j < 2; ++j) xf[buf][j] = *(const bf16x8*)(sX + laneX[kw][kc] + ((kh + j) * PHC) * 64);
             };
-            // the wave that is on the matrix cores gets issue priority over the other half's wave on the same SIMD (which is staging
-            // its next tile / draining its outputs on the VALU): its MFMAs and fragment reads are never queued behind that work
+            // the wave that is on the matrix cores gets issue priority over the waves that share its SIMD (the other group's wave in its
+            // mask / contraction epilogue, a staging wave copying a tile): its MFMAs and fragment reads are never queued behind that work
             if (a.prio) __builtin_amdgcn_s_setprio(3);
             fetch(0, 0);
 #pragma unroll
@@ -1059,227 +844,113 @@ __global__ __launch_bounds__(768) void conv3x3_fwd_ws_kernel(ConvArgs a) {
                 for (int i = 0; i < 2; ++i)
 #pragma unroll
                     for (int j = 0; j < 2; ++j)
-                        acc[i][j] = mfma16<TM>(wf[cur][i], xf[cur][j], acc[i][j]);
+                        acc[i][j] = mfma16<bf16>(wf[cur][i], xf[cur][j], acc[i][j]);
             }
             if (a.prio) __builtin_amdgcn_s_setprio(0);
         }
-        __builtin_amdgcn_s_waitcnt(0x0F70);                    // retire the prefetch before any output store is issued
-        // BatchNorm-backward mode: fetch the matching pre-BN activations now - their round trip runs under the half barrier and the
-        // accumulator hand-over below - and retire them BEFORE the first output store is issued (loads and stores share vmcnt and
-        // complete out of order on gfx9).  Unconditional loads from clamped addresses (out-of-image chunks are skipped in the drain).
-        uint4 yv[BNRED ? 8 : 1];
-        if (BNRED) {
+        __builtin_amdgcn_s_waitcnt(0x0F70);                    // vmcnt(0): these waves prefetch nothing; the a0 loads below start from a clean count
+        // the 4 input channels of this lane's pixel (lane & 31) in both rows: unconditional loads from clamped addresses - their round trip
+        // runs under the half barrier - and pv = the pixel is inside the image
+        uint2 av[2];
+        bool pv[2];
 #pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                const int px = (lane >> 3) + 8 * k;
-                const int f = min(tc.f0 + 2 * hw + (px >> 5), F - 1), t = min(tc.t0 + (px & 31), Tn - 1);
-                yv[k] = *(const uint4*)((const uint16_t*)a.bn_y + (((long)tc.b * F + f) * Tn + t) * 64 + (lane & 7) * 8);
-            }
-        }
-        uint2 av[C1RED ? 2 : 1];                               // C1RED: the 4 input channels of this lane's pixel (lane & 31) in both rows
-        bool pv[C1RED ? 2 : 1];
-        if (C1RED) {
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const int f = tc.f0 + 2 * hw + j, t = tc.t0 + (lane & 31);
-                pv[j] = f < F && t < Tn;
-                av[j] = *(const uint2*)((const uint16_t*)a.c1_a0 + (((long)tc.b * F + min(f, F - 1)) * Tn + min(t, Tn - 1)) * 4);
-            }
+        for (int j = 0; j < 2; ++j) {
+            const int f = tc.f0 + 2 * hw + j, t = tc.t0 + (lane & 31);
+            pv[j] = f < F && t < Tn;
+            av[j] = *(const uint2*)((const uint16_t*)a.c1_a0 + (((long)tc.b * F + min(f, F - 1)) * Tn + min(t, Tn - 1)) * 4);
         }
         half_barrier(cnt, epoch, lane);                        // the half is done reading its input tile
         uint16_t* stg = sX + hw * (64 * 64);                   // this wave's [64 px][64 co] slice (px = row * 32 + column)
-        if (C1RED) {
-            // (1) mask: pre-activation tile of the first layer in the accumulators' own layout (co x pixel), one MFMA per tile
-            __builtin_amdgcn_s_waitcnt(0x0F70);                // av landed (the next tile's prefetch too: it had the whole MFMA loop)
-            if constexpr (!__is_same(TY, bf16)) {              // saved fp16 input -> the bf16 operand of the two first-layer contractions below
+        // (1) mask: pre-activation tile of the first layer in the accumulators' own layout (co x pixel), one MFMA per tile
+        __builtin_amdgcn_s_waitcnt(0x0F70);                // av landed (the next tile's prefetch too: it had the whole MFMA loop)
+        if constexpr (!__is_same(TY, bf16)) {              // saved fp16 input -> the bf16 operand of the two first-layer contractions below
 #pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    av[j].x = pack2_bf16(H16<TY>::lo(av[j].x), H16<TY>::hi(av[j].x));
-                    av[j].y = pack2_bf16(H16<TY>::lo(av[j].y), H16<TY>::hi(av[j].y));
-                }
+            for (int j = 0; j < 2; ++j) {
+                av[j].x = pack2_bf16(H16<TY>::lo(av[j].x), H16<TY>::hi(av[j].x));
+                av[j].y = pack2_bf16(H16<TY>::lo(av[j].y), H16<TY>::hi(av[j].y));
             }
-            uint16_t* a0t = sX + 4 * (64 * 64) + hw * 256;     // [4 c][64 px] of this wave, in the part of the input tile no slice uses
-            {
-                const int j = lane >> 5;                       // lanes < 32 file row 0, lanes >= 32 row 1 (both hold both rows' pixels)
-                const uint2 q = j ? av[1] : av[0];
-                uint16_t* d = a0t + j * 32 + (lane & 31);
-                d[0] = (uint16_t)(q.x & 0xffffu); d[64] = (uint16_t)(q.x >> 16); d[128] = (uint16_t)(q.y & 0xffffu); d[192] = (uint16_t)(q.y >> 16);
+        }
+        uint16_t* a0t = sX + 4 * (64 * 64) + hw * 256;     // [4 c][64 px] of this wave, in the part of the input tile no slice uses
+        {
+            const int j = lane >> 5;                       // lanes < 32 file row 0, lanes >= 32 row 1 (both hold both rows' pixels)
+            const uint2 q = j ? av[1] : av[0];
+            uint16_t* d = a0t + j * 32 + (lane & 31);
+            d[0] = (uint16_t)(q.x & 0xffffu); d[64] = (uint16_t)(q.x >> 16); d[128] = (uint16_t)(q.y & 0xffffu); d[192] = (uint16_t)(q.y >> 16);
+        }
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const bf16x8 wfr = *(const bf16x8*)&sC1[(i * 32 + (lane & 31)) * 16 + (lane >> 5) * 8];
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                union { uint4 u; bf16x8 b; } bx;
+                bx.u = make_uint4(av[j].x, av[j].y, 0x00003f80u, 0u);          // [a0_0..a0_3, 1, 0, 0, 0]
+                f32x16 y;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) y[r] = 0.f;
+                y = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wfr, bx.b, y, 0, 0, 0);
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[i][j][r] = (y[r] > 0.f && pv[j]) ? acc[i][j][r] : 0.f;
             }
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const bf16x8 wfr = *(const bf16x8*)&sC1[(i * 32 + (lane & 31)) * 16 + (lane >> 5) * 8];
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    union { uint4 u; bf16x8 b; } bx;
-                    bx.u = make_uint4(av[j].x, av[j].y, 0x00003f80u, 0u);          // [a0_0..a0_3, 1, 0, 0, 0]
-                    f32x16 y;
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) y[r] = 0.f;
-                    y = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wfr, bx.b, y, 0, 0, 0);
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) acc[i][j][r] = (y[r] > 0.f && pv[j]) ? acc[i][j][r] : 0.f;
-                }
-            }
-            // (2) masked gradient tile, bf16, [64 px][64 co] in the transpose-read layout (swz)
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int g = 0; g < 4; ++g)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j) {
-                        uint2 w2;
-                        w2.x = pack2_bf16(acc[i][j][g * 4 + 0], acc[i][j][g * 4 + 1]);
-                        w2.y = pack2_bf16(acc[i][j][g * 4 + 2], acc[i][j][g * 4 + 3]);
-                        *(uint2*)(stg + swz(j * 32 + (lane & 31), i * 4 + g) + 4 * (lane >> 5)) = w2;
-                    }
-            __builtin_amdgcn_s_waitcnt(0xC07F);
-            __builtin_amdgcn_wave_barrier();
-            // (3) G[c'][co] += sum_px [a0 | 1][px][c'] * g[px][co]: 4 k-steps of 16 pixels x 2 channel halves
-            f32x16 d2[2];
-#pragma unroll
-            for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) d2[nb][r] = 0.f;
-            const int m = lane & 31;
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) {
-                union { uint4 u; bf16x8 b; } ax;
-                ax.u = *(const uint4*)(a0t + min(m, 3) * 64 + ks * 16 + (lane >> 5) * 8);
-                if (m == 4) ax.u = make_uint4(0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u);
-                else if (m > 4) ax.u = make_uint4(0u, 0u, 0u, 0u);
-#pragma unroll
-                for (int nb = 0; nb < 2; ++nb)
-                    d2[nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ax.b, tr_frag(stg, ks * 16, nb * 32, lane), d2[nb], 0, 0, 0);
-            }
-#pragma unroll
-            for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) gacc[nb][r] += d2[nb][r];
-        } else {
+        }
+        // (2) masked gradient tile, bf16, [64 px][64 co] in the transpose-read layout (swz)
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                // chunk (i*4+g) ^ (px & 7) only depends on the lane (px & 7 == lane & 7 for both rows): one address per (i, g)
-                uint16_t* q = stg + (lane & 31) * 64 + ((((i * 4 + g) ^ (lane & 7)) << 3) | (4 * (lane >> 5)));
+            for (int g = 0; g < 4; ++g)
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
                     uint2 w2;
-                    w2.x = H16<TM>::pack(acc[i][j][g * 4 + 0], acc[i][j][g * 4 + 1]);
-                    w2.y = H16<TM>::pack(acc[i][j][g * 4 + 2], acc[i][j][g * 4 + 3]);
-                    *(uint2*)(q + j * 32 * 64) = w2;
+                    w2.x = pack2_bf16(acc[i][j][g * 4 + 0], acc[i][j][g * 4 + 1]);
+                    w2.y = pack2_bf16(acc[i][j][g * 4 + 2], acc[i][j][g * 4 + 3]);
+                    *(uint2*)(stg + swz(j * 32 + (lane & 31), i * 4 + g) + 4 * (lane >> 5)) = w2;
                 }
-            }
         __builtin_amdgcn_s_waitcnt(0xC07F);
         __builtin_amdgcn_wave_barrier();
-        if (BNRED) __builtin_amdgcn_s_waitcnt(0x0F70);          // vmcnt(0)
-        // Interior tiles (every tile of a 256-multiple image): branch-free drain - all eight LDS reads in flight at once, one scalar base
-        // per wave, lane-constant byte offset, the row / column-block offsets immediate or scalar.  Round-3 stamps: the per-chunk validity
-        // branches (s_and_saveexec + branch around every store) made this phase a chain of eight LDS round trips, 2.4-4.5 k cycles per tile.
-        const bool interior = !BNRED && (tc.f0 + TR <= F) && (tc.t0 + PTC <= Tn);
-        if (interior) {
-            uint4 o[8];
+        // (3) G[c'][co] += sum_px [a0 | 1][px][c'] * g[px][co]: 4 k-steps of 16 pixels x 2 channel halves
+        f32x16 d2[2];
 #pragma unroll
-            for (int k = 0; k < 8; ++k) o[k] = *(const uint4*)&stg[((lane >> 3) + 8 * k) * 64 + (((lane & 7) ^ (lane >> 3)) << 3)];
-            char* obase = (char*)a.out + (((long)tc.b * F + tc.f0 + 2 * hw) * Tn + tc.t0) * 128;
-            const unsigned loff = (unsigned)((lane >> 3) * 128 + (lane & 7) * 16), rowb = (unsigned)Tn * 128u;
+        for (int nb = 0; nb < 2; ++nb)
 #pragma unroll
-            for (int k = 0; k < 8; ++k) *(uint4*)(obase + loff + (k & 3) * (8 * 128) + (k >> 2) * rowb) = o[k];
-            if (a.stats) {
+            for (int r = 0; r < 16; ++r) d2[nb][r] = 0.f;
+        const int m = lane & 31;
 #pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    const uint32_t w[4] = {o[k].x, o[k].y, o[k].z, o[k].w};
+        for (int ks = 0; ks < 4; ++ks) {
+            union { uint4 u; bf16x8 b; } ax;
+            ax.u = *(const uint4*)(a0t + min(m, 3) * 64 + ks * 16 + (lane >> 5) * 8);
+            if (m == 4) ax.u = make_uint4(0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u);
+            else if (m > 4) ax.u = make_uint4(0u, 0u, 0u, 0u);
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const float lo = H16<TM>::lo(w[q]), hi = H16<TM>::hi(w[q]);
-                        ssum[2 * q] += lo; ssq[2 * q] += lo * lo; ssum[2 * q + 1] += hi; ssq[2 * q + 1] += hi * hi;
-                    }
-                }
-            }
-        } else
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const int px = (lane >> 3) + 8 * k;
-            const int f = tc.f0 + 2 * hw + (px >> 5), t = tc.t0 + (px & 31);
-            // (px & 7) == (lane >> 3) for every k: lane-constant chunk, k only moves the row offset
-            const uint4 o = *(const uint4*)&stg[px * 64 + (((lane & 7) ^ (lane >> 3)) << 3)];
-            if (f < F && t < Tn) {
-                *(uint4*)((uint16_t*)a.out + (((long)tc.b * F + f) * Tn + t) * 64 + (lane & 7) * 8) = o;
-                if (BNRED) {            // sums of g and g*y; turned into rstd*(sum g*y - mean*sum g) per tile below
-                    const uint32_t w[4] = {o.x, o.y, o.z, o.w};
-                    const uint32_t yw[4] = {yv[k].x, yv[k].y, yv[k].z, yv[k].w};
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const float d0 = bf16_bits_to_f32(w[q] & 0xffffu), d1 = __uint_as_float(w[q] & 0xffff0000u);
-                        const float y0 = H16<TY>::lo(yw[q]), y1 = H16<TY>::hi(yw[q]);
-                        const float t0_ = __uint_as_float(__float_as_uint(y0) ^ (((bsgn >> (2 * q)) & 1u) << 31));
-                        const float t1_ = __uint_as_float(__float_as_uint(y1) ^ (((bsgn >> (2 * q + 1)) & 1u) << 31));
-                        const float g0 = t0_ > bthr[2 * q] ? d0 : 0.f, g1 = t1_ > bthr[2 * q + 1] ? d1 : 0.f;
-                        ssum[2 * q] += g0; ssq[2 * q] = fmaf(g0, y0, ssq[2 * q]);
-                        ssum[2 * q + 1] += g1; ssq[2 * q + 1] = fmaf(g1, y1, ssq[2 * q + 1]);
-                    }
-                } else if (a.stats) {
-                    const uint32_t w[4] = {o.x, o.y, o.z, o.w};
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const float lo = H16<TM>::lo(w[q]), hi = H16<TM>::hi(w[q]);
-                        ssum[2 * q] += lo; ssq[2 * q] += lo * lo; ssum[2 * q + 1] += hi; ssq[2 * q + 1] += hi * hi;
-                    }
-                }
-            }
+            for (int nb = 0; nb < 2; ++nb)
+                d2[nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ax.b, tr_frag(stg, ks * 16, nb * 32, lane), d2[nb], 0, 0, 0);
         }
-        }
+#pragma unroll
+        for (int nb = 0; nb < 2; ++nb)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) gacc[nb][r] += d2[nb][r];
         __builtin_amdgcn_s_waitcnt(0xC07F);                    // my reads of the slice have landed (lgkmcnt(0)) ...
         if (lane == 0) atomicAdd(&sFree[half], 1u);            // ... the staging waves may overwrite the buffer once all four say so
     }
-    // per-channel sums: the thread's 8 channels were accumulated over ALL its tiles in registers (folding them per tile - 48 lane
-    // exchanges + 16 LDS atomics - showed as ~2.5 k of a half-tile's ~22 k cycles in the stamps); one fold per launch.
-    // The fold is ORDERED (round 3): every wave parks its 128 partial sums in a slot of its own (the weight table is free once all
-    // eight waves are past their last tile) and thread c adds the eight slots in wave order - the round-2 f32 LDS atomics summed them
-    // in arrival order, which flipped bf16 roundings downstream from run to run.  What leaves the workgroup is one f64 atomic per
-    // channel of f32-valued terms: exact (order-free) as long as the terms' exponents span < 2^20.
+    // The first-layer sums were accumulated over ALL tiles of a wave in registers; one ORDERED fold per launch: every wave parks its 320
+    // partial sums in a slot of its own (the weight table is free once all eight MFMA waves are past their last tile) and thread q adds
+    // the eight slots in wave order.  What leaves the workgroup is one f64 atomic per entry of f32-valued terms: exact (order-free) as
+    // long as the terms' exponents span < 2^20, so the result is reproducible from run to run.
     __syncthreads();                               // every wave is done with sW
     if (a.clk && blockIdx.x == 0 && tid == 0) { a.clk[2] = __builtin_amdgcn_s_memtime(); a.clk[3] = __builtin_amdgcn_s_memrealtime(); }
-    float* part = (float*)sW;                      // [8 waves][128] statistics, then [8][320] first-layer sums (C1RED)
-    if (BNRED || a.stats) {
+    float* fold = (float*)sW + 1024;               // [8 waves][320]: [0,256) G[co][c], [256,320) s1[co]
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            ssum[e] += __shfl_xor(ssum[e], 8, 64); ssum[e] += __shfl_xor(ssum[e], 16, 64); ssum[e] += __shfl_xor(ssum[e], 32, 64);
-            ssq[e] += __shfl_xor(ssq[e], 8, 64); ssq[e] += __shfl_xor(ssq[e], 16, 64); ssq[e] += __shfl_xor(ssq[e], 32, 64);
-        }
-        if (lane < 8) {
+    for (int nb = 0; nb < 2; ++nb) {
+        const int co = nb * 32 + (lane & 31);
+        if (lane < 32) {
 #pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                float s2 = ssq[e];
-                if (BNRED) s2 = sAff[192 + lane * 8 + e] * (s2 - sAff[128 + lane * 8 + e] * ssum[e]);     // rstd * (sum g*y - mean * sum g)
-                part[wave * 128 + lane * 8 + e] = ssum[e]; part[wave * 128 + 64 + lane * 8 + e] = s2;
-            }
-        }
-        __syncthreads();
-        if (a.stats && tid < 128) {
-            float s = 0.f;
-#pragma unroll
-            for (int w = 0; w < 8; ++w) s += part[w * 128 + tid];
-            atomicAdd(&a.stats[tid], (double)s);
-        }
+            for (int r = 0; r < 4; ++r) fold[wave * 320 + co * 4 + r] = gacc[nb][r];
+        } else fold[wave * 320 + 256 + co] = gacc[nb][0];
     }
-    if (C1RED) {                                   // fold the 8 waves through LDS in wave order, then f64 atomics
-        float* fold = part + 1024;                 // [8][320]: [0,256) G[co][c], [256,320) s1[co]
+    __syncthreads();
+    for (int q = tid; q < 320; q += 512) {
+        float s = 0.f;
 #pragma unroll
-        for (int nb = 0; nb < 2; ++nb) {
-            const int co = nb * 32 + (lane & 31);
-            if (lane < 32) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) fold[wave * 320 + co * 4 + r] = gacc[nb][r];
-            } else fold[wave * 320 + 256 + co] = gacc[nb][0];
-        }
-        __syncthreads();
-        for (int q = tid; q < 320; q += 512) {
-            float s = 0.f;
-#pragma unroll
-            for (int w = 0; w < 8; ++w) s += fold[w * 320 + q];
-            atomicAdd(&a.c1_red[q < 256 ? q : 512 + (q - 256)], (double)s);
-        }
+        for (int w = 0; w < 8; ++w) s += fold[w * 320 + q];
+        atomicAdd(&a.c1_red[q < 256 ? q : 512 + (q - 256)], (double)s);
     }
 }
 
@@ -1310,7 +981,7 @@ __device__ __forceinline__ bf16x8 tr_pair(const uint16_t* p0, const uint16_t* p1
 // 8 waves = (co half) x (ci half) x (tap group: taps 0-4 | taps 5-8).  Every wave walks ALL pixels of the tile, so it only
 // needs 5 (4) accumulator fragments = 80 VGPRs; the registers that frees hold the NEXT tile (z halo + dy, 19 x 16 B per
 // thread) which is fetched from HBM while the current tile is on the matrix cores.
-template <typename T>
+// f32 storage only (the 16-bit launches take the role-split kernel below).
 __global__ __launch_bounds__(512) void conv3x3_wgrad_kernel(WgradArgs a) {
     __shared__ __attribute__((aligned(16))) uint16_t sY[Y_ELEMS];     // dy tile  [8*64 px][64 co]
     __shared__ __attribute__((aligned(16))) uint16_t sX[X_ELEMS];     // z halo tile [660 px][64 ci]
@@ -1320,8 +991,8 @@ __global__ __launch_bounds__(512) void conv3x3_wgrad_kernel(WgradArgs a) {
     const int F = a.F, Tn = a.T;
     const int tiles_f = (F + TR - 1) / TR, tiles_t = (Tn + TCOL - 1) / TCOL;
     const int ntiles = a.nb * tiles_f * tiles_t;
-    const T* zin = (const T*)a.zin;
-    const T* dy = (const T*)a.dy;
+    const float* zin = (const float*)a.zin;
+    const float* dy = (const float*)a.dy;
     const int cch = tid & 7;
 
     f32x16 acc[5];
@@ -1349,20 +1020,20 @@ __global__ __launch_bounds__(512) void conv3x3_wgrad_kernel(WgradArgs a) {
     }
 
     // staging as in the forward kernel: thread = (pixel column pc, 8-channel chunk), halo rows 0..9 + one chunk of columns 64/65
-    Chunk<T> rz[X_ITERS], ry[8];
+    Chunk<float> rz[X_ITERS], ry[8];
     const int pc = tid >> 3;
     auto issue_loads = [&](int tile) {
         const TileCoord tc = tile_coord(tile, tiles_f, tiles_t);
         const int t = tc.t0 - 1 + pc;
 #pragma unroll
-        for (int i = 0; i < HR; ++i) rz[i] = load_chunk_clamped<T>(zin, tc.b, tc.f0 - 1 + i, t, F, Tn, cch * 8);
+        for (int i = 0; i < HR; ++i) rz[i] = load_chunk_clamped<float>(zin, tc.b, tc.f0 - 1 + i, t, F, Tn, cch * 8);
         {
             const int hr = pc >> 1, te = tc.t0 + TCOL - 1 + (pc & 1);       // (threads >= 160: an unused, harmless extra chunk)
-            rz[HR] = load_chunk_clamped<T>(zin, tc.b, tc.f0 - 1 + hr, te, F, Tn, cch * 8);
+            rz[HR] = load_chunk_clamped<float>(zin, tc.b, tc.f0 - 1 + hr, te, F, Tn, cch * 8);
         }
         const int ty = tc.t0 + pc;
 #pragma unroll
-        for (int i = 0; i < 8; ++i) ry[i] = load_chunk_clamped<T>(dy, tc.b, tc.f0 + i, ty, F, Tn, cch * 8);
+        for (int i = 0; i < 8; ++i) ry[i] = load_chunk_clamped<float>(dy, tc.b, tc.f0 + i, ty, F, Tn, cch * 8);
     };
     auto write_tile = [&](int tile) {
         const TileCoord tc = tile_coord(tile, tiles_f, tiles_t);
@@ -1374,16 +1045,16 @@ __global__ __launch_bounds__(512) void conv3x3_wgrad_kernel(WgradArgs a) {
 #pragma unroll
         for (int i = 0; i < HR; ++i) {
             const int f = tc.f0 - 1 + i;
-            *(uint4*)&sX[swzc(i * HC + pc, pc, cch)] = xform_chunk<T>(rz[i], tv && f >= 0 && f < F, a.prologue, sc, sh, a.part_z);
+            *(uint4*)&sX[swzc(i * HC + pc, pc, cch)] = xform_chunk<float>(rz[i], tv && f >= 0 && f < F, a.prologue, sc, sh, a.part_z);
         }
         if (tid < 160) {
             const int hr = pc >> 1, f = tc.f0 - 1 + hr, te = tc.t0 + TCOL - 1 + (pc & 1);
-            *(uint4*)&sX[swzc(hr * HC + TCOL + (pc & 1), TCOL + (pc & 1), cch)] = xform_chunk<T>(rz[HR], f >= 0 && f < F && te < Tn, a.prologue, sc, sh, a.part_z);
+            *(uint4*)&sX[swzc(hr * HC + TCOL + (pc & 1), TCOL + (pc & 1), cch)] = xform_chunk<float>(rz[HR], f >= 0 && f < F && te < Tn, a.prologue, sc, sh, a.part_z);
         }
         const int ty = tc.t0 + pc;
 #pragma unroll
         for (int i = 0; i < 8; ++i)
-            *(uint4*)&sY[swzc(i * 64 + pc, pc, cch)] = xform_chunk<T>(ry[i], tc.f0 + i < F && ty < Tn, 0, sc, sh, a.part_dy);
+            *(uint4*)&sY[swzc(i * 64 + pc, pc, cch)] = xform_chunk<float>(ry[i], tc.f0 + i < F && ty < Tn, 0, sc, sh, a.part_dy);
     };
 
     const int nrounds = (ntiles + gridDim.x - 1) / gridDim.x;
@@ -1705,6 +1376,21 @@ static int conv_grid(int nb, int F, int T) {
     const int ncu = sarssl_cu_count();              // persistent: one workgroup per CU
     return ntiles < ncu ? ntiles : ncu;
 }
+// pairs of 8 x 32-pixel tiles (one tile per wave group) of the ping-pong / role-split kernels: their persistent work unit
+static int conv_npairs(int nb, int F, int T) { return (nb * ((F + TR - 1) / TR) * ((T + PTC - 1) / PTC) + 1) / 2; }
+// What every forward / data-gradient launch fills the same way: geometry, operands, MFMA priority, probes.  clk_slot: this launch's slot
+// in the clock-probe buffer (see conv_clk).
+static ConvArgs conv_args(const void* in, const void* w, void* out, int nb, int F, int T, int clk_slot) {
+    ConvArgs a = {};
+#ifdef CONV_STAMPS
+    a.stamps = g_conv_stamps_host;
+#endif
+    a.prio = (sarssl_mfma_prio() == 1 || sarssl_mfma_prio() == 2);
+    a.clk = conv_clk() ? conv_clk() + 4 * clk_slot : nullptr;
+    a.in = in; a.w = w; a.out = out;
+    a.nb = nb; a.F = F; a.T = T;
+    return a;
+}
 
 // in/out: (B,F,T,64) channels-last, dtype 0 f32 / 1 bf16 (same for both).  w: [9][64][64] ([tap][co][ci]) of
 // dtype w_dtype.  scale/shift: f32[64] prologue affine (+ReLU) or null for identity.
@@ -1729,24 +1415,18 @@ extern "C" int sarssl_conv3x3_dgrad_bnred(const void* dy, const void* w, void* d
 }
 
 // 3x3 convolution of relu(bn1(W1 a0)) straight from the stem's 4-channel input a0 (B,F,T,4) bf16: W1 f32[64][4], scale / shift = bn1's
-// affine; out (B,F,T,64) bf16 and, optionally, stats = [sum | sum of squares] of the stored output.  bf16 (ping-pong kernel).
+// affine; out (B,F,T,64) and, optionally, stats = [sum | sum of squares] of the stored output.  Ping-pong kernel.
 // dtype: encoding of a0, w and out (SARSSL_BF16 or SARSSL_F16).
 extern "C" int sarssl_conv3x3_fwd_c1(const void* a0, const float* W1, const float* scale, const float* shift, const void* w, void* out,
                                      int nb, int F, int T, double* stats, int dtype, void* stream) {
     SARSSL_REQUIRE(nb > 0 && F > 0 && T > 0 && a0 && W1 && scale && shift && (dtype == SARSSL_BF16 || dtype == SARSSL_F16), "sarssl_conv3x3_fwd_c1");
     if (stats && SARSSL_ZERO(stats, 128 * sizeof(double), (hipStream_t)stream) != hipSuccess) { sarssl_set_error("memset"); return -2; }
-    ConvArgs a = {};
-#ifdef CONV_STAMPS
-    a.stamps = g_conv_stamps_host;
-#endif
-    a.prio = (sarssl_mfma_prio() == 1 || sarssl_mfma_prio() == 2);
-    a.clk = conv_clk() ? conv_clk() + 4 * 3 : nullptr;
+    ConvArgs a = conv_args(a0, w, out, nb, F, T, 3);
     a.stats = stats;
-    a.in = a0; a.w = w; a.out = out; a.scale = scale; a.shift = shift; a.prologue = 1; a.c1_w = W1;
-    a.nb = nb; a.F = F; a.T = T;
-    const int npairs = (nb * ((F + TR - 1) / TR) * ((T + PTC - 1) / PTC) + 1) / 2;
-    if (dtype == SARSSL_F16) conv3x3_fwd_pp_kernel<false, true, false, f16><<<conv_persistent_grid(npairs, 0), 512, 0, (hipStream_t)stream>>>(a);
-    else conv3x3_fwd_pp_kernel<false, true><<<conv_persistent_grid(npairs, 0), 512, 0, (hipStream_t)stream>>>(a);
+    a.scale = scale; a.shift = shift; a.prologue = 1; a.c1_w = W1;
+    const int g = conv_persistent_grid(conv_npairs(nb, F, T), 0);
+    if (dtype == SARSSL_F16) conv3x3_fwd_pp_kernel<false, true, f16><<<g, 512, 0, (hipStream_t)stream>>>(a);
+    else conv3x3_fwd_pp_kernel<false, true><<<g, 512, 0, (hipStream_t)stream>>>(a);
     SARSSL_CHECK_LAUNCH("conv3x3_fwd_pp_kernel<c1in>");
     return 0;
 }
@@ -1754,25 +1434,19 @@ extern "C" int sarssl_conv3x3_fwd_c1(const void* a0, const float* W1, const floa
 // Data gradient of the first 3x3 convolution (w = its flipped / transposed taps, dy = the gradient w.r.t. its output) whose result is
 // consumed in the epilogue instead of being stored: red (f64[644], the layout of sarssl_stem_c1_bwd, zeroed here) receives
 // G[co][c] = sum_p g[p][co] a0[p][c] at [co*4 + c] and s1[co] = sum_p g[p][co] at [512 + co], g = dz1 * relu'(scale * (W1 a0) + shift);
-// the remaining entries follow from the input's moments (sarssl_stem_c1_bwd_finalize_mom).  bf16 (ping-pong kernel).
+// the remaining entries follow from the input's moments (sarssl_stem_c1_bwd_finalize_mom).  Role-split kernel.
 // a0_dtype: encoding of the saved input a0 (SARSSL_BF16 or SARSSL_F16); dy / w are bf16.
 extern "C" int sarssl_conv3x3_dgrad_c1red(const void* dy, const void* w, const void* a0, const float* W1, const float* scale,
                                           const float* shift, int nb, int F, int T, double* red, int a0_dtype, void* stream) {
     SARSSL_REQUIRE(nb > 0 && F > 0 && T > 0 && dy && w && a0 && W1 && scale && shift && red && (a0_dtype == SARSSL_BF16 || a0_dtype == SARSSL_F16),
                    "sarssl_conv3x3_dgrad_c1red");
     if (SARSSL_ZERO(red, 644 * sizeof(double), (hipStream_t)stream) != hipSuccess) { sarssl_set_error("memset"); return -2; }
-    ConvArgs a = {};
-#ifdef CONV_STAMPS
-    a.stamps = g_conv_stamps_host;
-#endif
-    a.prio = (sarssl_mfma_prio() == 1 || sarssl_mfma_prio() == 2);
-    a.clk = conv_clk() ? conv_clk() + 4 * 4 : nullptr;
-    a.in = dy; a.w = w; a.out = nullptr; a.scale = scale; a.shift = shift; a.prologue = 0; a.c1_w = W1; a.c1_a0 = a0; a.c1_red = red;
-    a.nb = nb; a.F = F; a.T = T;
-    const int npairs = (nb * ((F + TR - 1) / TR) * ((T + PTC - 1) / PTC) + 1) / 2;
-    if (a0_dtype == SARSSL_F16) conv3x3_fwd_ws_kernel<false, false, true, bf16, f16><<<conv_persistent_grid(npairs, 1), 768, 0, (hipStream_t)stream>>>(a);
-    else conv3x3_fwd_ws_kernel<false, false, true><<<conv_persistent_grid(npairs, 1), 768, 0, (hipStream_t)stream>>>(a);
-    SARSSL_CHECK_LAUNCH("conv3x3_fwd_ws_kernel<c1red>");
+    ConvArgs a = conv_args(dy, w, nullptr, nb, F, T, 4);
+    a.scale = scale; a.shift = shift; a.c1_w = W1; a.c1_a0 = a0; a.c1_red = red;       // (bn1's affine for the ReLU mask, not a staging prologue)
+    const int g = conv_persistent_grid(conv_npairs(nb, F, T), 1);
+    if (a0_dtype == SARSSL_F16) conv3x3_dgrad_c1red_ws_kernel<f16><<<g, 768, 0, (hipStream_t)stream>>>(a);
+    else conv3x3_dgrad_c1red_ws_kernel<bf16><<<g, 768, 0, (hipStream_t)stream>>>(a);
+    SARSSL_CHECK_LAUNCH("conv3x3_dgrad_c1red_ws_kernel");
     return 0;
 }
 
@@ -1782,39 +1456,29 @@ static int conv3x3_launch(const void* in, const void* w, void* out, int dtype, i
     SARSSL_REQUIRE(nb > 0 && F > 0 && T > 0, "sarssl_conv3x3_fwd");
     SARSSL_REQUIRE(stats == nullptr || dtype == SARSSL_BF16 || dtype == SARSSL_F16, "sarssl_conv3x3_fwd(fused statistics: 16-bit storage only)");
     if (stats && SARSSL_ZERO(stats, 128 * sizeof(double), (hipStream_t)stream) != hipSuccess) { sarssl_set_error("memset"); return -2; }
-    ConvArgs a = {};
-#ifdef CONV_STAMPS
-    a.stamps = g_conv_stamps_host;
-#endif
-    a.prio = (sarssl_mfma_prio() == 1 || sarssl_mfma_prio() == 2);
-    a.clk = conv_clk() ? conv_clk() + 4 * (bn_y ? 2 : (scale != nullptr ? 0 : 1)) : nullptr;
+    ConvArgs a = conv_args(in, w, out, nb, F, T, bn_y ? 2 : (scale != nullptr ? 0 : 1));
     a.bn_y = bn_y; a.bn_aff = bn_aff;
     a.stats = stats;
-    a.in = in; a.w = w; a.out = out; a.acc_ws = nullptr; a.acc_in = 0; a.acc_out = 0;
     a.scale = scale; a.shift = shift; a.prologue = (scale != nullptr);
-    a.nb = nb; a.F = F; a.T = T; a.part_in = 0; a.part_w = 0;
     hipStream_t st = (hipStream_t)stream;
-    const int grid = conv_grid(nb, F, T);
-    if (dtype == SARSSL_BF16 && w_dtype == SARSSL_BF16) {
-        const int npairs = (nb * ((F + TR - 1) / TR) * ((T + PTC - 1) / PTC) + 1) / 2;
-        const int g = conv_persistent_grid(npairs, scale != nullptr ? 0 : 1);      // (no prologue = a data-gradient launch)
-        if (bn_y && y_dtype == SARSSL_F16) conv3x3_fwd_pp_kernel<true, false, false, bf16, f16><<<g, 512, 0, st>>>(a);
+    if (dtype == w_dtype && (dtype == SARSSL_BF16 || dtype == SARSSL_F16)) {      // ping-pong kernel, tile pairs
+        const int g = conv_persistent_grid(conv_npairs(nb, F, T), scale != nullptr ? 0 : 1);      // (no prologue = a data-gradient launch)
+        if (dtype == SARSSL_F16) {                                                // forward launches of the fp16-forward mode
+            SARSSL_REQUIRE(bn_y == nullptr, "sarssl_conv3x3_fwd(fp16: forward launches only)");
+            conv3x3_fwd_pp_kernel<false, false, f16><<<g, 512, 0, st>>>(a);
+        } else if (bn_y && y_dtype == SARSSL_F16) conv3x3_fwd_pp_kernel<true, false, bf16, f16><<<g, 512, 0, st>>>(a);
         else if (bn_y) conv3x3_fwd_pp_kernel<true><<<g, 512, 0, st>>>(a);
         else conv3x3_fwd_pp_kernel<false><<<g, 512, 0, st>>>(a);
-    } else if (dtype == SARSSL_F16 && w_dtype == SARSSL_F16) {              // forward launches of the fp16-forward mode
-        SARSSL_REQUIRE(bn_y == nullptr, "sarssl_conv3x3_fwd(fp16: forward launches only)");
-        const int npairs = (nb * ((F + TR - 1) / TR) * ((T + PTC - 1) / PTC) + 1) / 2;
-        const int g = conv_persistent_grid(npairs, scale != nullptr ? 0 : 1);
-        conv3x3_fwd_pp_kernel<false, false, false, f16><<<g, 512, 0, st>>>(a);
-    } else if (dtype == SARSSL_F32 && w_dtype == SARSSL_F32) {
-        if (!precise) conv3x3_fwd_kernel<float, float><<<grid, 512, 0, st>>>(a);
+    } else if (dtype == SARSSL_F32 && w_dtype == SARSSL_F32) {                    // f32 kernel, 8 x 64-pixel tiles
+        const int grid = conv_grid(nb, F, T);
+        if (!precise) conv3x3_fwd_kernel<<<grid, 512, 0, st>>>(a);
         else {
             SARSSL_REQUIRE(ws != nullptr, "sarssl_conv3x3_fwd(precise needs workspace)");
             a.acc_ws = ws;
             ConvArgs p = a;
-            p.part_in = 0; p.part_w = 1; p.acc_in = 0; p.acc_out = 1; conv3x3_fwd_kernel<float, float><<<grid, 512, 0, st>>>(p);
-            p.part_in = 1; p.part_w = 0; p.acc_in = 1; p.acc_out = 1; conv3x3_fwd_kernel<float, float><<<grid, 512, 0, st>>>(p);
-            p.part_in = 0; p.part_w = 0; p.acc_in = 1; p.acc_out = 0; conv3x3_fwd_kernel<float, float><<<grid, 512, 0, st>>>(p);
+            p.part_in = 0; p.part_w = 1; p.acc_in = 0; p.acc_out = 1; conv3x3_fwd_kernel<<<grid, 512, 0, st>>>(p);
+            p.part_in = 1; p.part_w = 0; p.acc_in = 1; p.acc_out = 1; conv3x3_fwd_kernel<<<grid, 512, 0, st>>>(p);
+            p.part_in = 0; p.part_w = 0; p.acc_in = 1; p.acc_out = 0; conv3x3_fwd_kernel<<<grid, 512, 0, st>>>(p);
         }
     } else { sarssl_set_error("sarssl_conv3x3_fwd: unsupported dtypes (%d,%d)", dtype, w_dtype); return -1; }
     SARSSL_CHECK_LAUNCH("conv3x3_fwd_kernel");
@@ -1822,7 +1486,7 @@ static int conv3x3_launch(const void* in, const void* w, void* out, int dtype, i
 }
 
 extern "C" long sarssl_conv3x3_wgrad_workspace_bytes(int nb, int F, int T) {
-    const int g1 = conv_grid(nb, F, T), g2 = wgrad_db_grid(nb, F, T);          // (the f32 or the bf16 weight-gradient kernel may run)
+    const int g1 = conv_grid(nb, F, T), g2 = wgrad_db_grid(nb, F, T);          // (the f32 or the 16-bit weight-gradient kernel may run)
     return (long)(g1 > g2 ? g1 : g2) * W_ELEMS * sizeof(float);
 }
 
@@ -1910,7 +1574,7 @@ extern "C" int sarssl_conv3x3_wgrad(const void* dy, const void* zin, int dtype, 
         for (int pass = 0; pass < npass; ++pass) {
             WgradArgs p = a;
             if (precise) { p.part_dy = (pass == 1); p.part_z = (pass == 0); }     // hi*lo, lo*hi, hi*hi
-            conv3x3_wgrad_kernel<float><<<grid, 512, 0, st>>>(p);
+            conv3x3_wgrad_kernel<<<grid, 512, 0, st>>>(p);
             wgrad_reduce_kernel<<<rblocks, 256, 0, st>>>(partial, grid, dW, pass > 0);
         }
     } else { sarssl_set_error("sarssl_conv3x3_wgrad: unsupported dtype %d", dtype); return -1; }
@@ -1935,7 +1599,7 @@ extern "C" int sarssl_conv3x3_wgrad_acc(const void* dy, const void* zin, int nb,
     return 0;
 }
 // The same with the input operand relu(bn1(W1 a0)) formed from the stem's 4-channel input a0 (B,F,T,4) bf16 while staging (W1 f32[64][4],
-// scale / shift = bn1's affine): the first layer's 64-channel output is not read.  Double-buffered bf16 kernel.
+// scale / shift = bn1's affine): the first layer's 64-channel output is not read.  Role-split kernel (conv3x3_wgrad_ws_kernel<true>).
 extern "C" int sarssl_conv3x3_wgrad_c1_acc(const void* dy, const void* a0, const float* W1, int nb, int F, int T, const float* scale,
                                            const float* shift, float* grad_oihw, float* partial, int a0_dtype, void* stream) {
     SARSSL_REQUIRE(nb > 0 && F > 0 && T > 0 && grad_oihw && partial && W1 && scale && shift && (a0_dtype == SARSSL_BF16 || a0_dtype == SARSSL_F16),
