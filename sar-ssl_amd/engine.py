@@ -8,6 +8,7 @@ Reference semantics are cited per function; the math is restated in oracle/sarss
 """
 import math
 import os
+from collections import namedtuple
 
 import torch
 
@@ -152,19 +153,50 @@ def _as_stream(x):
     return x if x.dtype == _F32 else hip.cast(x.contiguous(), _F32)
 
 
-def _ln_bwd_hd(dln, x, ln_mod, stats, dy, drop, want16):
-    """LayerNorm backward of the hybrid mode: f32 stream gradient out; with ``want16`` also the bf16 operand of the next module of the
-    backward chain - with its dropout backward applied when ``drop`` = (p, seed, gscale) is given, else the plain copy (the module
-    multiplies a replayed tensor mask itself) -> (dx, dx16), or dx alone without ``want16``."""
-    r = hip.layernorm_bwd_stream(dln, x, ln_mod.weight.data, stats, resid=dy, dgamma=gbuf(ln_mod.weight), dbeta=gbuf(ln_mod.bias),
-                                 drop=drop if want16 else None, copy16=want16 and drop is None)
+def _w(p, view=None):
+    """Forward operand of parameter ``p`` (optionally viewed as ``view``): its (hi, lo) pair in the hybrid mode, else its runtime-dtype copy."""
+    if RT.hybrid:
+        return wpair(p, view)
+    return wt(p).view(view) if view is not None else wt(p)
+
+
+def _mm(x, w, target, **kw):
+    """nn.Linear forward against the operand ``w`` of _w.  ``target``: "branch" - a module-internal tensor (hybrid: fp16) - or "stream" - the
+    residual stream / a prediction (hybrid: f32).  Outside the hybrid mode both are the runtime dtype."""
+    if RT.hybrid:
+        return mm_nt_h(x, w, torch.float16 if target == "branch" else _F32, **kw)
+    return mm_nt(x, w, **kw)
+
+
+def _linear(x, p, view, target, **kw):
+    return _mm(x, _w(p, view), target, **kw)
+
+
+def _ln_in(x, ln_mod, family):
+    """The LayerNorm in front of the Linear layers ``family`` (an entry of _H_ALO decides whether they contract its result as a pair)
+    -> (GEMM operand, the tensor backward keeps as the weight-gradient operand, statistics)."""
+    if RT.hybrid:
+        ln, stats = hip.layernorm_fwd_pair(_as_stream(x), ln_mod.weight.data, ln_mod.bias.data, ln_mod.eps, want_lo=family in _H_ALO)
+        return ln, ln.hi, stats
+    ln, stats = hip.layernorm_fwd(x, ln_mod.weight.data, ln_mod.bias.data, ln_mod.eps)
+    return ln, ln, stats
+
+
+def _ln_bwd(dln, x, ln_mod, stats, dy, saved, next_kind):
+    """Backward of a module's (or block's) LayerNorm, ``dy`` the residual gradient added to it (None: none).  The module that runs next in
+    the backward chain (``next_kind``, see _next_drop) starts with the dropout backward of this result, so the launch writes that copy
+    as a second output -> (dx, dropped dx) where a mask applies.  Hybrid mode: dx is the f32 stream gradient and the second output the
+    bf16 operand of the next module whenever there is one (its plain copy where no mask applies; the module multiplies a replayed tensor
+    mask itself)."""
+    drop = _next_drop(next_kind, saved)
+    if not RT.hybrid:
+        return hip.layernorm_bwd(dln, x, ln_mod.weight.data, stats, resid=dy, dgamma=gbuf(ln_mod.weight), dbeta=gbuf(ln_mod.bias), drop=drop)
+    want16 = next_kind is not None
+    r = hip.layernorm_bwd_stream(dln, x, ln_mod.weight.data, stats, resid=None if dy is None else _as_stream(dy), dgamma=gbuf(ln_mod.weight),
+                                 dbeta=gbuf(ln_mod.bias), drop=drop, copy16=want16 and drop is None)
     if isinstance(r, tuple):
         r[1]._dropped = drop is not None
     return r
-
-
-def _ln_bwd_h(dln, x, ln_mod, stats, dy, saved, next_kind, want16):
-    return _ln_bwd_hd(dln, x, ln_mod, stats, dy, _next_drop(next_kind, saved) if want16 else None, want16)
 
 
 def _grad16(dy, dy16, p, seed, gscale=1.0):
@@ -179,6 +211,20 @@ def _grad16(dy, dy16, p, seed, gscale=1.0):
     if torch.is_tensor(seed) or (p <= 0 and gscale == 1.0):
         return d16
     return hip.act_bwd(d16, None, 0, p_drop=p, seed=seed, gscale=gscale, out=d16 if own else None)
+
+
+def _grad_in(dy, dy_dropped, p, seed):
+    """Gradient of a module's output projection from the module's incoming gradient ``dy``: the backward of the dropout in front of the
+    residual add ((p, seed); a tensor seed is a replayed mask).  ``dy_dropped``: what the previous LayerNorm backward already wrote for this
+    module (see _ln_bwd)."""
+    if RT.hybrid:                                          # dy: f32 stream gradient, dy_dropped: its bf16 operand copy
+        dout = _grad16(dy, dy_dropped, p, seed)
+        return dout * seed.to(dout.dtype) if torch.is_tensor(seed) else dout
+    if torch.is_tensor(seed):
+        return dy * seed.to(dy.dtype)
+    if dy_dropped is not None:
+        return dy_dropped
+    return hip.act_bwd(dy, None, 0, p_drop=p, seed=seed) if p > 0 else dy
 
 
 def to_rt(x):
@@ -202,6 +248,49 @@ def _cached(module, name, builder):
         with torch.no_grad():
             c[name] = (key, builder())
     return c[name][1]
+
+
+# ------------------------------------------------------------------------------------------------ saved records
+# What each ``*_fwd`` pushes on ``saved`` for its ``*_bwd``: one record type per module, built by keyword and read by field.  The records
+# that start a module's backward give that module's incoming dropout as ``drop_in`` = (p, seed, gscale) - what _next_drop hands the
+# LayerNorm backward in front of it.  Seeds are integers, or the mask tensors themselves when the masks are replayed (RT.replay).
+class StemRec(namedtuple("StemRec", "a0 y1 mom1 aff1 y2 aff2 y3 aff3 y4 aff4 z4 train")):
+    """y1 is None when the first layer's output was never stored (mom1: the input moments its BatchNorm came from); z4 [B*T, F*4]: the
+    operand of the frame-patch GEMM."""
+    __slots__ = ()
+
+
+class FfnRec(namedtuple("FfnRec", "x ln stats hpre a p1 s1 p2 s2 factor")):
+    """ln: LayerNorm output (hybrid: its hi half); hpre / a: hidden pre-activation / activation with its dropout applied."""
+    __slots__ = ()
+    drop_in = property(lambda r: (r.p2, r.s2, r.factor))
+
+
+ATTN_POS, ATTN_BIAS, ATTN_UNFUSED = "pos", "bias", "unfused"     # attention cores: fused with the in-kernel positional score | fused, bias tensor | GEMMs
+
+
+class MhsaRec(namedtuple("MhsaRec", "x ln stats qu qv k v pos pe core bias ctx32 lse p pd pa sa ctx po so B T")):
+    """core: the ATTN_* that ran.  The fused cores leave bias (B,H,T,T shifted positional score), ctx32 (unrounded f32 context) and lse, the
+    unfused one p / pd (probabilities / their dropped copy); the others are None.  qv is None where qu is the plain query projection
+    (ATTN_POS: the kernels add u / v while loading)."""
+    __slots__ = ()
+    drop_in = property(lambda r: (r.po, r.so, 1.0))
+
+
+class ConvRec(namedtuple("ConvRec", "x ln stats h g c aff s po so B T train")):
+    """h [M, 2d]: first pointwise convolution; g: GLU output, None when the fused GLU + depthwise pass never stored it."""
+    __slots__ = ()
+    drop_in = property(lambda r: (r.po, r.so, 1.0))
+
+
+class BlockRec(namedtuple("BlockRec", "x stats rows B T x_full", defaults=(None, 0, 0, None))):
+    """The closing LayerNorm's input and statistics.  Compact tail (block_fwd(rows=...)): x holds the gathered rows, rows / B / T say which,
+    x_full is the tail's full-row input (for a full prediction on request - vis); rows and x_full are None for the full tail."""
+    __slots__ = ()
+
+
+DecRec = namedtuple("DecRec", "e h")
+HeadRec = namedtuple("HeadRec", "x stats acts")          # acts: per Linear layer (input, output, activation)
 
 
 # ------------------------------------------------------------------------------------------------ BatchNorm plumbing
@@ -268,29 +357,23 @@ def stem_fwd(a0, pe, train, saved):
     y3, s3 = hip.conv3x3_fwd(y2, _taps(pe[6])[0], aff2[0], aff2[1], want_stats=True) if fuse else \
         (hip.conv3x3_fwd(y2, _taps(pe[6])[0], aff2[0], aff2[1], precise=RT.precise), None)
     aff3 = bn_affine(y3, 64, pe[7], train, sums=s3)
-    if RT.hybrid:
-        # the f32 stream starts at the 4-channel tensors (0.5 MB per segment): the 64 -> 4 result and BatchNorm(4) + ReLU of it travel as
-        # fp16 pairs into a three-segment frame-patch product; the hi halves are exactly the fp16 mode's y4 / z4 (what backward reads)
-        if train:
-            y4p, s4 = hip.stem_c4_fwd_pair(y3, pe[9].weight.data.view(4, 64), aff3[0], aff3[1], want_stats=True)
-            aff4 = bn_affine(y4p.hi, 4, pe[10], train, sums=s4)
-        else:
-            y4p = hip.stem_c4_fwd_pair(y3, pe[9].weight.data.view(4, 64), aff3[0], aff3[1])
-            aff4 = bn_affine(y4p.hi, 4, pe[10], train)
-        z4p = hip.cl_affine_act_pair(y4p, 4, aff4, RELU)
-        y4, z4 = y4p.hi, z4p.hi.view(B * T, F * 4)
-        e = mm_nt_h(hip.Pair(z4, z4p.lo.view(B * T, F * 4)), _patch_w_pair(pe[12], F), _F32)
-        saved.append((a0, (y1, mom1), aff1, y2, aff2, y3, aff3, y4, aff4, z4, train))
-        return e
+    # hybrid: the f32 stream starts at the 4-channel tensors (0.5 MB per segment) - the 64 -> 4 result and BatchNorm(4) + ReLU of it travel as
+    # fp16 pairs into a three-segment frame-patch product; the hi halves are exactly the fp16 mode's y4 / z4 (what backward reads)
+    hyb = RT.hybrid
+    c4, w4 = (hip.stem_c4_fwd_pair if hyb else hip.stem_c4_fwd), pe[9].weight.data.view(4, 64)
     if train:                       # BatchNorm(4) sums ride in the 64->4 pass (no statistics pass over y4)
-        y4, s4 = hip.stem_c4_fwd(y3, pe[9].weight.data.view(4, 64), aff3[0], aff3[1], want_stats=True)        # (B,T,F,4)
-        aff4 = bn_affine(y4, 4, pe[10], train, sums=s4)
+        y4, s4 = c4(y3, w4, aff3[0], aff3[1], want_stats=True)                                                # (B,T,F,4)
     else:
-        y4 = hip.stem_c4_fwd(y3, pe[9].weight.data.view(4, 64), aff3[0], aff3[1])
-        aff4 = bn_affine(y4, 4, pe[10], train)
-    z4 = hip.cl_affine_act(y4, 4, aff4, RELU).view(B * T, F * 4)
-    e = mm_nt(z4, _patch_w(pe[12], F))
-    saved.append((a0, (y1, mom1), aff1, y2, aff2, y3, aff3, y4, aff4, z4, train))
+        y4, s4 = c4(y3, w4, aff3[0], aff3[1]), None
+    aff4 = bn_affine(y4.hi if hyb else y4, 4, pe[10], train, sums=s4)
+    if hyb:
+        z4p = hip.cl_affine_act_pair(y4, 4, aff4, RELU)
+        y4, z4 = y4.hi, z4p.hi.view(B * T, F * 4)
+        e = mm_nt_h(hip.Pair(z4, z4p.lo.view(B * T, F * 4)), _patch_w_pair(pe[12], F), _F32)
+    else:
+        z4 = hip.cl_affine_act(y4, 4, aff4, RELU).view(B * T, F * 4)
+        e = mm_nt(z4, _patch_w(pe[12], F))
+    saved.append(StemRec(a0=a0, y1=y1, mom1=mom1, aff1=aff1, y2=y2, aff2=aff2, y3=y3, aff3=aff3, y4=y4, aff4=aff4, z4=z4, train=train))
     return e
 
 
@@ -314,7 +397,7 @@ def patch_bwd(de, pe, saved):
     """Backward of the frame-patch convolution (the last layer of ``patch_embed``, a plain GEMM here): accumulates its weight
     gradient - the stem's only sizeable parameter, so the data-parallel bucket holding it can be reduced before the long
     parameter-poor remainder of the stem backward - and returns the gradient w.r.t. the (B,T,F,4) activations."""
-    a0, z4 = saved[-1][0], saved[-1][9]
+    a0, z4 = saved[-1].a0, saved[-1].z4
     B, F, T, _ = a0.shape
     d = de.shape[1]
     if RT.hybrid and de.dtype == _F32:        # the stream's gradient leaves f32 here: bf16 operand of the two products below
@@ -331,7 +414,8 @@ def patch_bwd(de, pe, saved):
 
 def stem_bwd(dz4, pe, saved):
     """Backward of the CNN stem below the patch GEMM (``dz4`` = patch_bwd's result)."""
-    a0, (y1, mom1), aff1, y2, aff2, y3, aff3, y4, aff4, z4, train = saved.pop()
+    r = saved.pop()
+    a0, y1, mom1, aff1, y2, aff2, y3, aff3, y4, aff4, train = r.a0, r.y1, r.mom1, r.aff1, r.y2, r.aff2, r.y3, r.aff3, r.y4, r.aff4, r.train
     B, F, T, _ = a0.shape
     W1 = pe[0].weight.data.view(64, 4)
     red4 = hip.cl_bn_bwd_reduce(dz4, y4, 4, aff4, RELU)
@@ -434,184 +518,125 @@ def block_ffns(enc):
     return [blk.sequential[i].module for blk in enc.layers for i in (0, 3)]
 
 
-def _ffn_fwd_h(x, ff, factor, train, saved, out=None):
-    """ffn_fwd in the hybrid mode: x / result f32, LayerNorm output as an fp16 pair, hidden activation and saved pre-activation fp16."""
-    seq = ff.sequential
-    x = _as_stream(x)
-    pre = x.__dict__.pop("_pre_ln", None)
-    p1, p2 = _p(seq[3], train), _p(seq[5], train)
-    l1, l2 = seq[1].linear, seq[4].linear
-    d = x.shape[1]
-    if (_H_FFN2_FWD and d in _FFN2_WIDTHS and pre is None and not _replaying(train) and x.stride(1) == 1 and hip.ffn2h_supported(x.shape[0], d)
-            and l1.weight.shape[0] == 4 * d and wt(l1.weight).is_cuda):
-        # LayerNorm + Linear + Swish + Dropout + Linear + Dropout + scaled residual on the f32 stream in one launch (csrc/ffn2h.hip)
-        packs = _ffn_packs(ff, need_bwd=not RT.inference)
-        s1, s2 = (RT.next_seed() if p1 > 0 else 0), (RT.next_seed() if p2 > 0 else 0)
-        y, hpre, a, lnh, stats = hip.ffn2h_fwd(x, seq[0].weight.data, seq[0].bias.data, seq[0].eps, packs[0], packs[4], packs[1], packs[5],
-                                               l1.bias.data, l2.bias.data, d, p1=p1, s1=s1, p2=p2, s2=s2, out_scale=factor, out=out,
-                                               act_pair="ffn1" in _H_ALO)
-        saved.append((x, lnh, stats, hpre, a, p1, s1, p2, s2, factor))
-        return y
-    if pre is not None and pre[0] is seq[0]:
-        ln, stats = pre[1], pre[2]
-    else:
-        ln, stats = hip.layernorm_fwd_pair(x, seq[0].weight.data, seq[0].bias.data, seq[0].eps, want_lo="ffn1" in _H_ALO)
-    hpre = torch.empty((x.shape[0], l1.weight.shape[0]), dtype=torch.float16, device=x.device)
-    if _replaying(train) and (p1 > 0 or p2 > 0):          # host-drawn masks in the reference's order: hidden, then output
-        a = mm_nt_h(ln, wpair(l1.weight), torch.float16, bias=l1.bias.data, act=SWISH, preact=hpre)
-        s1 = RT.replay.mask(tuple(a.shape), p1, x.device, a.dtype) if p1 > 0 else 0
-        if p1 > 0:
-            a = a * s1
-        y = mm_nt_h(a, wpair(l2.weight), _F32, bias=l2.bias.data)
-        s2 = RT.replay.mask(tuple(y.shape), p2, x.device, _F32) if p2 > 0 else 0
-        y = torch.add(x, y * s2 if p2 > 0 else y, alpha=factor)
-        if out is not None:
-            out.copy_(y)
-            y = out
-    else:
-        s1, s2 = (RT.next_seed() if p1 > 0 else 0), (RT.next_seed() if p2 > 0 else 0)
-        a = mm_nt_h(ln, wpair(l1.weight), torch.float16, bias=l1.bias.data, act=SWISH, preact=hpre, p_drop=p1, seed=s1)
-        y = mm_nt_h(a, wpair(l2.weight), _F32, bias=l2.bias.data, p_drop=p2, seed=s2, out_scale=factor, resid=x, ldr=x.stride(0),
-                    res_scale=1.0, out=out, ldc=(out.stride(0) if out is not None else None))
-    saved.append((x, ln.hi, stats, hpre, a, p1, s1, p2, s2, factor))
-    return y
-
-
-def _ffn_bwd_h(dy, ff, saved, dy16=None, next_kind=None, want16=True):
-    """-> (dx f32, dx16) - the stream gradient and its bf16 copy for the next module of the backward chain - or dx alone (want16 False)."""
-    x, ln, stats, hpre, a, p1, s1, p2, s2, factor = saved.pop()
-    seq = ff.sequential
-    l1, l2 = seq[1].linear, seq[4].linear
-    dz2 = _grad16(dy, dy16, p2, s2, factor)
-    if torch.is_tensor(s2):
-        dz2 = dz2 * (s2 * factor).to(dz2.dtype)
-    mm_tn_acc(dz2, a, gbuf(l2.weight), bias=gbuf(l2.bias))
-    d = x.shape[1]
-    if (d in _FFN2_WIDTHS and not torch.is_tensor(s1) and dz2.stride(1) == 1 and hip.ffn2_supported(x.shape[0], d, dz2.dtype)
-            and hpre.shape[1] == 4 * d and ff.__dict__.get("_ffn2_packs") is not None and ff.__dict__["_ffn2_packs"][0][5]
-            and ff.__dict__["_ffn2_packs"][0][0] == weights_version()):
-        # both data-gradient products in the fused launch of the fp16 mode (csrc/ffn2.hip; bf16 gradients, fp16 saved pre-activation):
-        # the branch gradient dln reaches the stream's LayerNorm backward in bf16
-        dln, dh = hip.ffn2_bwd(dz2, _ffn_packs(ff)[2], _ffn_packs(ff)[3], hpre, d, p1=p1, s1=s1)
-        mm_tn_acc(dh, ln, gbuf(l1.weight), bias=gbuf(l1.bias))
-        return _ln_bwd_h(dln, x, seq[0], stats, _as_stream(dy), saved, next_kind, want16)
-    if torch.is_tensor(s1):
-        dh = mm_nn(dz2, wtg(l2.weight), aux=hpre, aux_act=SWISH)
-        dh = dh * s1.to(dh.dtype)
-    else:
-        dh = mm_nn(dz2, wtg(l2.weight), aux=hpre, aux_act=SWISH, p_drop=p1, seed=s1)
-    mm_tn_acc(dh, ln, gbuf(l1.weight), bias=gbuf(l1.bias))
-    dln = mm_nn(dh, wtg(l1.weight), out_dtype=_F32)
-    return _ln_bwd_h(dln, x, seq[0], stats, _as_stream(dy), saved, next_kind, want16)
-
-
 def ffn_fwd(x, ff, factor, train, saved, out=None):
-    """x + factor * FeedForwardModule(x)  (conformer/feed_forward.py:47-57, Conformer.py:60-67)."""
-    if RT.hybrid:
-        return _ffn_fwd_h(x, ff, factor, train, saved, out=out)
+    """x + factor * FeedForwardModule(x)  (conformer/feed_forward.py:47-57, Conformer.py:60-67).
+    Hybrid mode: x / result f32, LayerNorm output as an fp16 pair, hidden activation and saved pre-activation fp16."""
     seq = ff.sequential
+    hyb = RT.hybrid
+    if hyb:
+        x = _as_stream(x)
     pre = x.__dict__.pop("_pre_ln", None)            # (block_fwd of the previous block already normalised this very tensor for us)
     p1, p2 = _p(seq[3], train), _p(seq[5], train)
+    l1, l2 = seq[1].linear, seq[4].linear
     d = x.shape[1]
-    fused = (d in _FFN2_WIDTHS and not _replaying(train) and hip.ffn2_supported(x.shape[0], d, x.dtype)
-             and seq[1].linear.weight.shape[0] == 4 * d)
+    # one launch for (LayerNorm +) Linear + Swish + Dropout + Linear + Dropout + scaled residual: the hidden tile stays on the CU (csrc/ffn2.hip;
+    # hybrid: on the f32 stream, always with its LayerNorm, csrc/ffn2h.hip)
+    fused = (d in _FFN2_WIDTHS and not _replaying(train) and l1.weight.shape[0] == 4 * d and
+             ((_H_FFN2_FWD and pre is None and x.stride(1) == 1 and hip.ffn2h_supported(x.shape[0], d) and wt(l1.weight).is_cuda) if hyb
+              else hip.ffn2_supported(x.shape[0], d, x.dtype)))
     if pre is not None and pre[0] is seq[0]:
-        ln, stats = pre[1], pre[2]
+        xn, stats = pre[1], pre[2]
+        ln = xn.hi if hyb else xn
     elif fused and x.stride(1) == 1:
-        ln = stats = None                           # the fused launch normalises its rows itself (bit-identical to the stand-alone kernel)
+        xn = ln = stats = None                      # the fused launch normalises its rows itself (bit-identical to the stand-alone kernel)
     else:
-        ln, stats = hip.layernorm_fwd(x, seq[0].weight.data, seq[0].bias.data, seq[0].eps)
+        xn, ln, stats = _ln_in(x, seq[0], "ffn1")
     if fused:
-        # one launch for (LayerNorm +) Linear + Swish + Dropout + Linear + Dropout + scaled residual: the hidden tile stays on the CU (csrc/ffn2.hip)
         packs = _ffn_packs(ff, need_bwd=not RT.inference)
         s1, s2 = (RT.next_seed() if p1 > 0 else 0), (RT.next_seed() if p2 > 0 else 0)
-        r = hip.ffn2_fwd(ln, packs[0], packs[1], seq[1].linear.bias.data, seq[4].linear.bias.data, x, d, p1=p1, s1=s1, p2=p2, s2=s2,
-                         out_scale=factor, out=out, ln_in=None if ln is not None else (x, seq[0].weight.data, seq[0].bias.data, seq[0].eps))
-        y, hpre, a = r[0], r[1], r[2]
-        if ln is None:
-            ln, stats = r[3], r[4]
-        saved.append((x, ln, stats, hpre, a, p1, s1, p2, s2, factor))
-        return y
-    hpre = torch.empty((x.shape[0], seq[1].linear.weight.shape[0]), dtype=x.dtype, device=x.device)
-    if _replaying(train) and (p1 > 0 or p2 > 0):          # host-drawn masks in the reference's order: hidden, then output
-        a = mm_nt(ln, wt(seq[1].linear.weight), bias=seq[1].linear.bias.data, act=SWISH, preact=hpre)
-        s1 = RT.replay.mask(tuple(a.shape), p1, x.device, x.dtype) if p1 > 0 else 0
-        if p1 > 0:
-            a = a * s1
-        y = mm_nt(a, wt(seq[4].linear.weight), bias=seq[4].linear.bias.data)
-        s2 = RT.replay.mask(tuple(y.shape), p2, x.device, x.dtype) if p2 > 0 else 0
-        y = torch.add(x, y * s2 if p2 > 0 else y, alpha=factor)
-        if out is not None:
-            out.copy_(y)
-            y = out
-        saved.append((x, ln, stats, hpre, a, p1, s1, p2, s2, factor))
-        return y
-    s1, s2 = (RT.next_seed() if p1 > 0 else 0), (RT.next_seed() if p2 > 0 else 0)
-    a = mm_nt(ln, wt(seq[1].linear.weight), bias=seq[1].linear.bias.data, act=SWISH, preact=hpre, p_drop=p1, seed=s1)
-    y = mm_nt(a, wt(seq[4].linear.weight), bias=seq[4].linear.bias.data, p_drop=p2, seed=s2, out_scale=factor,
-              resid=x, ldr=x.stride(0), res_scale=1.0, out=out, ldc=(out.stride(0) if out is not None else None))
-    saved.append((x, ln, stats, hpre, a, p1, s1, p2, s2, factor))
+        if hyb:
+            y, hpre, a, ln, stats = hip.ffn2h_fwd(x, seq[0].weight.data, seq[0].bias.data, seq[0].eps, packs[0], packs[4], packs[1], packs[5],
+                                                  l1.bias.data, l2.bias.data, d, p1=p1, s1=s1, p2=p2, s2=s2, out_scale=factor, out=out,
+                                                  act_pair="ffn1" in _H_ALO)
+        else:
+            r = hip.ffn2_fwd(xn, packs[0], packs[1], l1.bias.data, l2.bias.data, x, d, p1=p1, s1=s1, p2=p2, s2=s2, out_scale=factor, out=out,
+                             ln_in=None if xn is not None else (x, seq[0].weight.data, seq[0].bias.data, seq[0].eps))
+            y, hpre, a = r[0], r[1], r[2]
+            if xn is None:
+                ln, stats = r[3], r[4]
+    else:
+        hpre = torch.empty((x.shape[0], l1.weight.shape[0]), dtype=ln.dtype, device=x.device)
+        if _replaying(train) and (p1 > 0 or p2 > 0):          # host-drawn masks in the reference's order: hidden, then output
+            a = _linear(xn, l1.weight, None, "branch", bias=l1.bias.data, act=SWISH, preact=hpre)
+            s1 = RT.replay.mask(tuple(a.shape), p1, x.device, a.dtype) if p1 > 0 else 0
+            if p1 > 0:
+                a = a * s1
+            y = _linear(a, l2.weight, None, "stream", bias=l2.bias.data)
+            s2 = RT.replay.mask(tuple(y.shape), p2, x.device, y.dtype) if p2 > 0 else 0
+            y = torch.add(x, y * s2 if p2 > 0 else y, alpha=factor)
+            if out is not None:
+                out.copy_(y)
+                y = out
+        else:
+            s1, s2 = (RT.next_seed() if p1 > 0 else 0), (RT.next_seed() if p2 > 0 else 0)
+            a = _linear(xn, l1.weight, None, "branch", bias=l1.bias.data, act=SWISH, preact=hpre, p_drop=p1, seed=s1)
+            y = _linear(a, l2.weight, None, "stream", bias=l2.bias.data, p_drop=p2, seed=s2, out_scale=factor, resid=x, ldr=x.stride(0),
+                        res_scale=1.0, out=out, ldc=(out.stride(0) if out is not None else None))
+    saved.append(FfnRec(x=x, ln=ln, stats=stats, hpre=hpre, a=a, p1=p1, s1=s1, p2=p2, s2=s2, factor=factor))
     return y
 
 
 def _next_drop(kind, saved):
-    """(p, seed, gscale) of the dropout backward the NEXT module of the backward chain (``kind``: 'ffn' | 'conv' | 'mhsa', its entry
-    is on top of ``saved``) applies to its incoming gradient, or None when there is nothing to apply (or the masks are replayed host
-    tensors).  The LayerNorm backward that produces that gradient then writes the dropped copy as a second output
-    (hip.layernorm_bwd(drop=...)) instead of a separate act_bwd pass."""
+    """(p, seed, gscale) of the dropout backward the NEXT module of the backward chain (``kind``: 'ffn' | 'conv' | 'mhsa', its record
+    is on top of ``saved``) applies to its incoming gradient - the record's ``drop_in`` -, or None when there is nothing to apply (or the
+    masks are replayed host tensors, or ``kind`` is None / 'copy': nobody / a consumer without dropout follows).  The LayerNorm backward
+    that produces that gradient then writes the dropped copy as a second output (hip.layernorm_bwd(drop=...)) instead of a separate
+    act_bwd pass."""
     if kind is None or kind == "copy" or not saved:
         return None
-    e = saved[-1]
-    if kind == "ffn":
-        p, seed, g = e[7], e[8], e[9]
-    elif kind == "conv":
-        p, seed, g = e[8], e[9], 1.0
-    else:
-        p, seed, g = e[-4], e[-3], 1.0
+    p, seed, g = saved[-1].drop_in
     if torch.is_tensor(seed) or torch.is_tensor(p) or (p <= 0 and g == 1.0):
         return None
     return (float(p), int(seed), float(g))
 
 
 def ffn_bwd(dy, ff, saved, dy_dropped=None, next_kind=None):
-    if RT.hybrid:
-        return _ffn_bwd_h(dy, ff, saved, dy16=dy_dropped, next_kind=next_kind, want16=next_kind is not None)
-    x, ln, stats, hpre, a, p1, s1, p2, s2, factor = saved.pop()
+    """-> dx, or (dx, dropped dx) where the LayerNorm backward wrote the next module's operand as well (_ln_bwd)."""
+    r = saved.pop()
+    x, hpre, p1, s1, s2, factor = r.x, r.hpre, r.p1, r.s1, r.s2, r.factor
     seq = ff.sequential
-    if torch.is_tensor(s1) or torch.is_tensor(s2):        # replayed masks (see ffn_fwd)
+    l1, l2 = seq[1].linear, seq[4].linear
+    hyb = RT.hybrid
+    # replayed masks (see ffn_fwd) on this module's own path: the hybrid mode multiplies the output mask into its bf16 operand and goes on
+    masks = torch.is_tensor(s1) or (torch.is_tensor(s2) and not hyb)
+    if hyb:
+        dz2 = _grad16(dy, dy_dropped, r.p2, s2, factor)
+        if torch.is_tensor(s2):
+            dz2 = dz2 * (s2 * factor).to(dz2.dtype)
+    elif masks:
         dz2 = (dy * s2.to(dy.dtype) if torch.is_tensor(s2) else dy) * factor
-        mm_tn_acc(dz2, a, gbuf(seq[4].linear.weight), bias=gbuf(seq[4].linear.bias))
-        dh = mm_nn(dz2, wtg(seq[4].linear.weight), aux=hpre, aux_act=SWISH)
-        if torch.is_tensor(s1):
-            dh = dh * s1.to(dh.dtype)
+    elif dy_dropped is not None:
+        dz2 = dy_dropped                                  # written by the previous LayerNorm backward (see _next_drop)
     else:
-        if dy_dropped is not None:
-            dz2 = dy_dropped                                  # written by the previous LayerNorm backward (see _next_drop)
-        else:
-            dz2 = hip.act_bwd(dy, None, 0, p_drop=p2, seed=s2, gscale=factor) if (p2 > 0 or factor != 1.0) else dy
-        mm_tn_acc(dz2, a, gbuf(seq[4].linear.weight), bias=gbuf(seq[4].linear.bias))
-        d = x.shape[1]
-        if (d in _FFN2_WIDTHS and dz2.dtype in _16 and dz2.stride(1) == 1 and hip.ffn2_supported(x.shape[0], d, dz2.dtype)
-                and hpre.shape[1] == 4 * d and ff.__dict__.get("_ffn2_packs") is not None and ff.__dict__["_ffn2_packs"][0][5]):
-            # both data-gradient products in one launch: dh = (dz2 W2) * mask * swish'(hpre) leaves the chip once (the two weight-gradient
-            # products read it), dln = dh W1 is formed from the LDS-resident tile (csrc/ffn2.hip, packs of the transposed weights)
-            packs = _ffn_packs(ff)
-            if x.dtype == hpre.dtype and x.stride(1) == 1 and dy.stride(1) == 1:
-                # ... and the LayerNorm backward of the module's first layer in the same launch's epilogue (dln never leaves the chip)
-                dx, dh = hip.ffn2_bwd(dz2, packs[2], packs[3], hpre, d, p1=p1, s1=s1,
-                                      ln_bwd=(x, seq[0].weight.data, stats, dy, gbuf(seq[0].weight), gbuf(seq[0].bias), _next_drop(next_kind, saved)))
-                mm_tn_acc(dh, ln, gbuf(seq[1].linear.weight), bias=gbuf(seq[1].linear.bias))
-                return dx
-            dln, dh = hip.ffn2_bwd(dz2, packs[2], packs[3], hpre, d, p1=p1, s1=s1)
-            mm_tn_acc(dh, ln, gbuf(seq[1].linear.weight), bias=gbuf(seq[1].linear.bias))
-            return hip.layernorm_bwd(dln, x, seq[0].weight.data, stats, resid=dy, dgamma=gbuf(seq[0].weight), dbeta=gbuf(seq[0].bias),
-                                     drop=_next_drop(next_kind, saved))
-        # dh = (dz2 @ W2) * dropout_mask1 * swish'(hpre): activation backward fused into the GEMM epilogue
-        dh = mm_nn(dz2, wtg(seq[4].linear.weight), aux=hpre, aux_act=SWISH, p_drop=p1, seed=s1)
-    mm_tn_acc(dh, ln, gbuf(seq[1].linear.weight), bias=gbuf(seq[1].linear.bias))
-    dln = mm_nn(dh, wtg(seq[1].linear.weight))
-    return hip.layernorm_bwd(dln, x, seq[0].weight.data, stats, resid=dy, dgamma=gbuf(seq[0].weight), dbeta=gbuf(seq[0].bias),
-                             drop=_next_drop(next_kind, saved))
+        dz2 = hip.act_bwd(dy, None, 0, p_drop=r.p2, seed=s2, gscale=factor) if (r.p2 > 0 or factor != 1.0) else dy
+    mm_tn_acc(dz2, r.a, gbuf(l2.weight), bias=gbuf(l2.bias))
+    d = x.shape[1]
+    pk = ff.__dict__.get("_ffn2_packs")
+    if (not masks and d in _FFN2_WIDTHS and dz2.dtype in _16 and dz2.stride(1) == 1 and hip.ffn2_supported(x.shape[0], d, dz2.dtype)
+            and hpre.shape[1] == 4 * d and pk is not None and pk[0][5] and (not hyb or pk[0][0] == weights_version())):
+        # both data-gradient products in one launch: dh = (dz2 W2) * mask * swish'(hpre) leaves the chip once (the two weight-gradient
+        # products read it), dln = dh W1 is formed from the LDS-resident tile (csrc/ffn2.hip, packs of the transposed weights; hybrid: the
+        # fp16 mode's launch - bf16 gradients, fp16 saved pre-activation - whose packs must belong to this step's weights)
+        packs = _ffn_packs(ff)
+        if x.dtype == hpre.dtype and x.stride(1) == 1 and dy.stride(1) == 1:
+            # ... and the LayerNorm backward of the module's first layer in the same launch's epilogue (dln never leaves the chip; never
+            # in the hybrid mode: x is the f32 stream)
+            dx, dh = hip.ffn2_bwd(dz2, packs[2], packs[3], hpre, d, p1=p1, s1=s1,
+                                  ln_bwd=(x, seq[0].weight.data, r.stats, dy, gbuf(seq[0].weight), gbuf(seq[0].bias), _next_drop(next_kind, saved)))
+            mm_tn_acc(dh, r.ln, gbuf(l1.weight), bias=gbuf(l1.bias))
+            return dx
+        dln, dh = hip.ffn2_bwd(dz2, packs[2], packs[3], hpre, d, p1=p1, s1=s1)      # (hybrid: dln reaches the stream's LayerNorm backward in bf16)
+        mm_tn_acc(dh, r.ln, gbuf(l1.weight), bias=gbuf(l1.bias))
+        return _ln_bwd(dln, x, seq[0], r.stats, dy, saved, next_kind)
+    # dh = (dz2 @ W2) * dropout_mask1 * swish'(hpre): activation backward fused into the GEMM epilogue
+    if torch.is_tensor(s1):
+        dh = mm_nn(dz2, wtg(l2.weight), aux=hpre, aux_act=SWISH)
+        dh = dh * s1.to(dh.dtype)
+    else:
+        dh = mm_nn(dz2, wtg(l2.weight), aux=hpre, aux_act=SWISH, p_drop=p1, seed=s1)
+    mm_tn_acc(dh, r.ln, gbuf(l1.weight), bias=gbuf(l1.bias))
+    dln = mm_nn(dh, wtg(l1.weight), out_dtype=_F32 if hyb else None)
+    return _ln_bwd(dln, x, seq[0], r.stats, dy, saved, next_kind)
 
 
 def _pe(mod, T):
@@ -695,179 +720,111 @@ def _qkv_views_lo(att):
     return torch.as_strided(ws[0], (3 * d, d), (d, 1))
 
 
-def _mhsa_fwd_h(x, mod, B, T, train, saved):
-    """mhsa_fwd in the hybrid mode: x / result f32; q, k, v, the attention core and its context are the fp16 kernels of the fp16 mode."""
-    att = mod.attention
-    H, dh, d = att.num_heads, att.d_head, att.d_model
-    M = B * T
-    x = _as_stream(x)
-    ln, stats = hip.layernorm_fwd_pair(x, mod.layer_norm.weight.data, mod.layer_norm.bias.data, mod.layer_norm.eps, want_lo="qkv" in _H_ALO)
-    fused = _qkv_views(att)
-    fused_lo = _qkv_views_lo(att) if fused is not None else None
-    if fused is not None and fused_lo is not None:
-        qkv = mm_nt_h(ln, (fused[0], fused_lo), torch.float16, bias=fused[1])
-        q, k, v = qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:]
-    else:
-        q = mm_nt_h(ln, wpair(att.query_proj.linear.weight), torch.float16, bias=att.query_proj.linear.bias.data)
-        k = mm_nt_h(ln, wpair(att.key_proj.linear.weight), torch.float16, bias=att.key_proj.linear.bias.data)
-        v = mm_nt_h(ln, wpair(att.value_proj.linear.weight), torch.float16, bias=att.value_proj.linear.bias.data)
-    ldk = k.stride(0)
-    pe = _pe(mod, T)
-    pos = _pos_proj_h(mod, T)
-    nbh = B * H
-    pa = _p(att.dropout, train)
-    sa = RT.next_seed() if pa > 0 else 0
-    scale = 1.0 / math.sqrt(d)
-    replay = _replaying(train) and (pa > 0 or _p(mod.dropout, train) > 0)
-    fused_attn = not replay and hip.relpos_attn_supported(T, dh, RT.dtype)
-    in_kernel = fused_attn and hip.relpos_attn_pos_supported(T, dh, RT.dtype)
-    ub, vb = att.u_bias.data.view(-1), att.v_bias.data.view(-1)
-    qu, qv = (q, None) if in_kernel else hip.bias2(q, ub, vb)
-    po = _p(mod.dropout, train)
-    wo = wpair(att.out_proj.linear.weight)
-    if fused_attn:
-        if in_kernel:
-            ctx, lse, bias = hip.relpos_attn_fwd_pos(q, q, k, v, pos, B, H, T, dh, scale, pa, sa, need_bwd=not RT.inference, biases=(ub, vb),
-                                                     pair=True)              # (the kernel writes the context's lo half itself)
-        else:
-            bias = torch.empty((B, H, T, T), dtype=RT.dtype, device=x.device)
-            hip.gemm(qv, pos, M=T, N=T, K=dh, lda=d, ldb=d, nbatch=nbh, batch_inner=H, sA=(T * d, dh), sB=(0, dh), out=bias, ldc=T,
-                     sC=(H * T * T, T * T), c_row_shift=True)
-            ctx, lse = hip.relpos_attn_fwd(qu, k, v, bias, B, H, T, dh, scale, pa, sa, need_bwd=not RT.inference, want_ctx32=True)
-        so = RT.next_seed() if po > 0 else 0
-        # the kernel's unrounded f32 context (it keeps it for the backward pass anyway) enters the output projection as a pair
-        if isinstance(ctx, hip.Pair):
-            cin, ctx = ctx, ctx.hi
-        else:
-            cin = hip.Pair(ctx, hip.split_pair(lse[0], want_hi=False)) if lse[0] is not None else ctx
-        y = mm_nt_h(cin, wo, _F32, bias=att.out_proj.linear.bias.data, p_drop=po, seed=so, resid=x, ldr=x.stride(0), res_scale=1.0)
-        saved.append((x, ln.hi, stats, qu, qv, k, v, pos, pe, bias, lse, pa, sa, ctx, po, so, B, T))
-        return y
-    content = hip.gemm(qu, k, M=T, N=T, K=dh, lda=d, ldb=ldk, nbatch=nbh, batch_inner=H, sA=(T * d, dh), sB=(T * ldk, dh),
-                       out_dtype=torch.float32, out_shape=(B, H, T, T))
-    pscore = hip.gemm(qv, pos, M=T, N=T, K=dh, lda=d, ldb=d, nbatch=nbh, batch_inner=H, sA=(T * d, dh), sB=(0, dh),
-                      out_dtype=torch.float32, out_shape=(B, H, T, T))
-    if replay:
-        p, pd = hip.softmax_relshift_fwd(content, pscore, scale, RT.dtype, 0.0, 0)
-        if pa > 0:
-            sa = RT.replay.mask((B, H, T, T), pa, x.device, RT.dtype)
-            pd = p * sa
-    else:
-        p, pd = hip.softmax_relshift_fwd(content, pscore, scale, RT.dtype, pa, sa)
-    del content, pscore
-    ctx = torch.empty((M, d), dtype=RT.dtype, device=x.device)
-    hip.gemm(pd, v, a_kc=True, b_kc=False, M=T, N=dh, K=T, lda=T, ldb=ldk, nbatch=nbh, batch_inner=H,
-             sA=(H * T * T, T * T), sB=(T * ldk, dh), out=ctx, ldc=d, sC=(T * d, dh))
-    if replay:
-        y = mm_nt_h(ctx, wo, _F32, bias=att.out_proj.linear.bias.data)
-        so = RT.replay.mask(tuple(y.shape), po, x.device, _F32) if po > 0 else 0
-        y = x + (y * so if po > 0 else y)
-    else:
-        so = RT.next_seed() if po > 0 else 0
-        y = mm_nt_h(ctx, wo, _F32, bias=att.out_proj.linear.bias.data, p_drop=po, seed=so, resid=x, ldr=x.stride(0), res_scale=1.0)
-    saved.append((x, ln.hi, stats, qu, qv, k, v, pos, pe, p, pd, pa, sa, ctx, po, so, B, T))
-    return y
+def _qkv_operand(att):
+    """(forward operand of the stacked [3d, d] q / k / v weight - see _w -, its [3d] bias view) when the three projections are contiguous
+    in memory (one [M, 3d] GEMM), else None."""
+    views = _qkv_views(att)
+    if views is None or not RT.hybrid:
+        return views and views[:2]
+    lo = _qkv_views_lo(att)
+    return ((views[0], lo), views[1]) if lo is not None else None
 
 
 def mhsa_fwd(x, mod, B, T, train, saved):
     """x + MultiHeadedSelfAttentionModule(x)  (conformer/attention.py:143-151, 72-113).
 
-    bf16: the positional-score GEMM writes (q+v)P^T directly in the reference's relative-shift layout and ONE flash-style kernel
-    (csrc/attention.hip) does content score + shifted positional score + 1/sqrt(d_model) + softmax + dropout + PV - no (B,H,T,T)
-    score / probability tensor.  f32 mode, replayed dropout masks and shapes the fused kernel does not take: batched MFMA GEMMs over
-    (b, head) + one scale/relative-shift/softmax/dropout kernel.  The positional projection is computed once per call (it is
-    batch-invariant)."""
+    16-bit modes: ONE flash-style kernel (csrc/attention.hip) does content score + shifted positional score + 1/sqrt(d_model) + softmax +
+    dropout + PV - no (B,H,T,T) score / probability tensor; it forms the positional score itself (ATTN_POS, T <= 256) or reads it from the
+    positional-score GEMM, which writes (q+v)P^T directly in the reference's relative-shift layout (ATTN_BIAS).  f32 mode, replayed dropout
+    masks and shapes the fused kernel does not take (ATTN_UNFUSED): batched MFMA GEMMs over (b, head) + one scale/relative-shift/softmax/
+    dropout kernel.  The positional projection is computed once per call (it is batch-invariant).
+    Hybrid mode: x / result f32; q, k, v, the attention core and its context are the fp16 kernels of the fp16 mode, and the kernel's
+    unrounded f32 context (it keeps it for the backward pass anyway) enters the output projection as a pair."""
     att = mod.attention
     H, dh, d = att.num_heads, att.d_head, att.d_model
-    M = B * T
-    if RT.hybrid:
-        return _mhsa_fwd_h(x, mod, B, T, train, saved)
-    fused = _qkv_views(att)
-    ln, stats = hip.layernorm_fwd(x, mod.layer_norm.weight.data, mod.layer_norm.bias.data, mod.layer_norm.eps)
+    M, nbh = B * T, B * H
+    hyb = RT.hybrid
+    # (a model that is not flattened refreshes stale weight shadows where they are first asked for: each mode keeps its place for that)
+    if hyb:
+        x = _as_stream(x)
+        xn, ln, stats = _ln_in(x, mod.layer_norm, "qkv")
+        fused = _qkv_operand(att)
+    else:
+        fused = _qkv_operand(att)
+        xn, ln, stats = _ln_in(x, mod.layer_norm, "qkv")
     if fused is not None:                       # one [M, 3d] GEMM; q / k / v are column slices (row stride 3d)
-        qkv = mm_nt(ln, fused[0], bias=fused[1])
+        qkv = _mm(xn, fused[0], "branch", bias=fused[1])
         q, k, v = qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:]
     else:
-        q = mm_nt(ln, wt(att.query_proj.linear.weight), bias=att.query_proj.linear.bias.data)
-        k = mm_nt(ln, wt(att.key_proj.linear.weight), bias=att.key_proj.linear.bias.data)
-        v = mm_nt(ln, wt(att.value_proj.linear.weight), bias=att.value_proj.linear.bias.data)
+        q, k, v = (_linear(xn, proj.linear.weight, None, "branch", bias=proj.linear.bias.data) for proj in (att.query_proj, att.key_proj, att.value_proj))
     ldk = k.stride(0)
     pe = _pe(mod, T)
-    pos = _pos_proj(mod, T)                                                                  # [T, d]
-    nbh = B * H
-    pa = _p(att.dropout, train)
+    pos = (_pos_proj_h if hyb else _pos_proj)(mod, T)                                        # [T, d]
+    pa, po = _p(att.dropout, train), _p(mod.dropout, train)
     sa = RT.next_seed() if pa > 0 else 0
     scale = 1.0 / math.sqrt(d)                                                               # 1/sqrt(d_model), attention.py:57
-    replay = _replaying(train) and (pa > 0 or _p(mod.dropout, train) > 0)
-    fused_attn = not replay and hip.relpos_attn_supported(T, dh, RT.dtype)
-    in_kernel = fused_attn and hip.relpos_attn_pos_supported(T, dh, RT.dtype)
+    replay = _replaying(train) and (pa > 0 or po > 0)
+    core = ATTN_UNFUSED if (replay or not hip.relpos_attn_supported(T, dh, RT.dtype)) else \
+        ATTN_POS if hip.relpos_attn_pos_supported(T, dh, RT.dtype) else ATTN_BIAS
     ub, vb = att.u_bias.data.view(-1), att.v_bias.data.view(-1)
     # (positional score in the kernels: they also form q + u / q + v while loading the query rows - no biased copies of q)
-    qu, qv = (q, None) if in_kernel else hip.bias2(q, ub, vb)
-    if fused_attn:
-        # fused path (csrc/attention.hip): the positional-score GEMM writes its product directly in the relative-shift layout and
-        # one flash-style kernel does content score + shifted bias + softmax + dropout + PV; no (B,H,T,T) score / probability tensor
-        if in_kernel:
-            # T <= 256: the kernel forms the shifted positional score itself (position tiles stream through its K buffer)
-            ctx, lse, bias = hip.relpos_attn_fwd_pos(q, q, k, v, pos, B, H, T, dh, scale, pa, sa, need_bwd=not RT.inference,
-                                                     biases=(ub, vb))
+    qu, qv = (q, None) if core == ATTN_POS else hip.bias2(q, ub, vb)
+    wo = _w(att.out_proj.linear.weight) if hyb else None       # (hybrid: looked up ahead of the attention launches - see above)
+    bias = ctx32 = lse = p = pd = None
+    if core == ATTN_UNFUSED:
+        content = hip.gemm(qu, k, M=T, N=T, K=dh, lda=d, ldb=ldk, nbatch=nbh, batch_inner=H, sA=(T * d, dh), sB=(T * ldk, dh),
+                           out_dtype=torch.float32, precise=RT.precise, out_shape=(B, H, T, T))
+        pscore = hip.gemm(qv, pos, M=T, N=T, K=dh, lda=d, ldb=d, nbatch=nbh, batch_inner=H, sA=(T * d, dh), sB=(0, dh),
+                          out_dtype=torch.float32, precise=RT.precise, out_shape=(B, H, T, T))
+        if replay:                                             # host-drawn masks: attention probabilities, then the module output
+            p, pd = hip.softmax_relshift_fwd(content, pscore, scale, RT.dtype, 0.0, 0)
+            if pa > 0:
+                sa = RT.replay.mask((B, H, T, T), pa, x.device, RT.dtype)
+                pd = p * sa
         else:
-            bias = torch.empty((B, H, T, T), dtype=RT.dtype, device=x.device)
-            hip.gemm(qv, pos, M=T, N=T, K=dh, lda=d, ldb=d, nbatch=nbh, batch_inner=H, sA=(T * d, dh), sB=(0, dh), out=bias, ldc=T,
-                     sC=(H * T * T, T * T), c_row_shift=True)
-            ctx, lse = hip.relpos_attn_fwd(qu, k, v, bias, B, H, T, dh, scale, pa, sa, need_bwd=not RT.inference)   # lse = (ctx32, lse)
-        po = _p(mod.dropout, train)
-        so = RT.next_seed() if po > 0 else 0
-        y = mm_nt(ctx, wt(att.out_proj.linear.weight), bias=att.out_proj.linear.bias.data, p_drop=po, seed=so,
-                  resid=x, ldr=x.stride(0), res_scale=1.0)
-        saved.append((x, ln, stats, qu, qv, k, v, pos, pe, bias, lse, pa, sa, ctx, po, so, B, T))
-        return y
-    content = hip.gemm(qu, k, M=T, N=T, K=dh, lda=d, ldb=ldk, nbatch=nbh, batch_inner=H, sA=(T * d, dh), sB=(T * ldk, dh),
-                       out_dtype=torch.float32, precise=RT.precise, out_shape=(B, H, T, T))
-    pscore = hip.gemm(qv, pos, M=T, N=T, K=dh, lda=d, ldb=d, nbatch=nbh, batch_inner=H, sA=(T * d, dh), sB=(0, dh),
-                      out_dtype=torch.float32, precise=RT.precise, out_shape=(B, H, T, T))
-    if replay:                                             # host-drawn masks: attention probabilities, then the module output
-        p, pd = hip.softmax_relshift_fwd(content, pscore, scale, RT.dtype, 0.0, 0)
-        if pa > 0:
-            sa = RT.replay.mask((B, H, T, T), pa, x.device, RT.dtype)
-            pd = p * sa
+            p, pd = hip.softmax_relshift_fwd(content, pscore, scale, RT.dtype, pa, sa)
+        del content, pscore
+        cin = ctx = torch.empty((M, d), dtype=RT.dtype, device=x.device)
+        hip.gemm(pd, v, a_kc=True, b_kc=False, M=T, N=dh, K=T, lda=T, ldb=ldk, nbatch=nbh, batch_inner=H,
+                 sA=(H * T * T, T * T), sB=(T * ldk, dh), out=ctx, ldc=d, sC=(T * d, dh), precise=RT.precise)
+    elif core == ATTN_POS:
+        # T <= 256: the kernel forms the shifted positional score itself (position tiles stream through its K buffer); hybrid: it writes
+        # the context's lo half as well
+        cin, (ctx32, lse), bias = hip.relpos_attn_fwd_pos(q, q, k, v, pos, B, H, T, dh, scale, pa, sa, need_bwd=not RT.inference,
+                                                          biases=(ub, vb), pair=hyb)
+        ctx = cin.hi if hyb else cin
     else:
-        p, pd = hip.softmax_relshift_fwd(content, pscore, scale, RT.dtype, pa, sa)
-    del content, pscore
-    ctx = torch.empty((M, d), dtype=RT.dtype, device=x.device)
-    hip.gemm(pd, v, a_kc=True, b_kc=False, M=T, N=dh, K=T, lda=T, ldb=ldk, nbatch=nbh, batch_inner=H,
-             sA=(H * T * T, T * T), sB=(T * ldk, dh), out=ctx, ldc=d, sC=(T * d, dh), precise=RT.precise)
-    po = _p(mod.dropout, train)
+        bias = torch.empty((B, H, T, T), dtype=RT.dtype, device=x.device)
+        hip.gemm(qv, pos, M=T, N=T, K=dh, lda=d, ldb=d, nbatch=nbh, batch_inner=H, sA=(T * d, dh), sB=(0, dh), out=bias, ldc=T,
+                 sC=(H * T * T, T * T), c_row_shift=True)
+        cin, (ctx32, lse) = hip.relpos_attn_fwd(qu, k, v, bias, B, H, T, dh, scale, pa, sa, need_bwd=not RT.inference, want_ctx32=hyb)
+        ctx = cin
+        if hyb:
+            cin = hip.Pair(ctx, hip.split_pair(ctx32, want_hi=False))
+    if wo is None:
+        wo = _w(att.out_proj.linear.weight)
     if replay:
-        y = mm_nt(ctx, wt(att.out_proj.linear.weight), bias=att.out_proj.linear.bias.data)
-        so = RT.replay.mask(tuple(y.shape), po, x.device, RT.dtype) if po > 0 else 0
+        y = _mm(cin, wo, "stream", bias=att.out_proj.linear.bias.data)
+        so = RT.replay.mask(tuple(y.shape), po, x.device, y.dtype) if po > 0 else 0
         y = x + (y * so if po > 0 else y)
     else:
         so = RT.next_seed() if po > 0 else 0
-        y = mm_nt(ctx, wt(att.out_proj.linear.weight), bias=att.out_proj.linear.bias.data, p_drop=po, seed=so,
-                  resid=x, ldr=x.stride(0), res_scale=1.0)
-    saved.append((x, ln, stats, qu, qv, k, v, pos, pe, p, pd, pa, sa, ctx, po, so, B, T))
+        y = _mm(cin, wo, "stream", bias=att.out_proj.linear.bias.data, p_drop=po, seed=so, resid=x, ldr=x.stride(0), res_scale=1.0)
+    saved.append(MhsaRec(x=x, ln=ln, stats=stats, qu=qu, qv=qv, k=k, v=v, pos=pos, pe=pe, core=core, bias=bias, ctx32=ctx32, lse=lse, p=p, pd=pd,
+                         pa=pa, sa=sa, ctx=ctx, po=po, so=so, B=B, T=T))
     return y
 
 
 def mhsa_bwd(dy, mod, saved, dy_dropped=None, next_kind=None):
-    x, ln, stats, qu, qv, k, v, pos, pe, p, pd, pa, sa, ctx, po, so, B, T = saved.pop()
+    r = saved.pop()
+    x, qu, qv, k, v, pos, pa, sa, B, T = r.x, r.qu, r.qv, r.k, r.v, r.pos, r.pa, r.sa, r.B, r.T
     att = mod.attention
     H, dh, d = att.num_heads, att.d_head, att.d_model
     M, nbh = B * T, B * H
     dev = x.device
-    fused_attn = isinstance(pd, tuple)                                # fused forward saved (bias, (ctx32, lse)) in place of (p, pd)
-    if RT.hybrid:                                          # dy: f32 stream gradient, dy_dropped: its bf16 operand copy
-        dout = _grad16(dy, dy_dropped, po, so)
-        if torch.is_tensor(so):
-            dout = dout * so.to(dout.dtype)
-    elif torch.is_tensor(so):
-        dout = dy * so.to(dy.dtype)                        # replayed mask
-    elif dy_dropped is not None:
-        dout = dy_dropped
-    else:
-        dout = hip.act_bwd(dy, None, 0, p_drop=po, seed=so) if po > 0 else dy
-    mm_tn_acc(dout, ctx, gbuf(att.out_proj.linear.weight), bias=gbuf(att.out_proj.linear.bias))
+    fused_attn = r.core != ATTN_UNFUSED
+    dout = _grad_in(dy, dy_dropped, r.po, r.so)
+    mm_tn_acc(dout, r.ctx, gbuf(att.out_proj.linear.weight), bias=gbuf(att.out_proj.linear.bias))
     dctx = mm_nn(dout, wtg(att.out_proj.linear.weight))
     fused = _qkv_views(att, grad=True)
     ldk = k.stride(0)
@@ -877,28 +834,27 @@ def mhsa_bwd(dy, mod, saved, dy_dropped=None, next_kind=None):
         if fused_attn:      # the content-score part of dq in its own buffer: its column sum (u_bias gradient) can then wait for the
             dqu = torch.empty((M, d), dtype=RT.gdtype, device=dev)    # block's batched launch instead of running before dq overwrites it
     else:
+        dqkv = None
         dqu = torch.empty((M, d), dtype=RT.gdtype, device=dev)
         dk = torch.empty((M, d), dtype=RT.gdtype, device=dev)
         dv = torch.empty((M, d), dtype=RT.gdtype, device=dev)
     ldg = dqu.stride(0)
     scale = 1.0 / math.sqrt(d)
-    if fused_attn and hip.relpos_attn_pos_supported(T, dh, RT.dtype):
+    if r.core == ATTN_POS:
         # T <= 256: the dQ kernel also forms the positional-score gradients (no d(bias) tensor, un-shift pass or batched products)
         dqv = torch.empty((M, d), dtype=RT.gdtype, device=dev)
         plain_q = qv is None                       # forward saved the plain query projection: the kernels add u / v while loading
         dq_out = dqkv[:, :d] if fused is not None else None      # dq = dqu + dqv written by the dK / dV kernel (needs a buffer of its own)
-        dposb = hip.relpos_attn_bwd_pos(qu, qu if plain_q else qv, k, v, pos, p, pd, dctx, dqu, dqv, dk, dv, B, H, T, dh, scale, pa, sa,
-                                        biases=(att.u_bias.data.view(-1), att.v_bias.data.view(-1)) if plain_q else None, dq_sum=dq_out)
-        return _mhsa_bwd_tail(dy, mod, att, x, ln, stats, pe, dqkv if fused is not None else None, dqu, dk, dv, dqv, dposb, fused, B, T, d,
-                              dev, drop=_next_drop(next_kind, saved), dq_out=dq_out if dq_out is not None else dqu,
-                              dq_done=dq_out is not None, want16=next_kind is not None)
-    if fused_attn:
-        dbias = hip.relpos_attn_bwd(qu, k, v, p, pd, dctx, dqu, dk, dv, B, H, T, dh, scale, pa, sa)      # p = bias, pd = (ctx32, lse) here
+        dposb = hip.relpos_attn_bwd_pos(qu, qu if plain_q else qv, k, v, pos, r.bias, (r.ctx32, r.lse), dctx, dqu, dqv, dk, dv, B, H, T, dh, scale,
+                                        pa, sa, biases=(att.u_bias.data.view(-1), att.v_bias.data.view(-1)) if plain_q else None, dq_sum=dq_out)
+        return _mhsa_bwd_tail(dy, mod, r, dqkv, dqu, dk, dv, dqv, dposb, fused, saved, next_kind, dq_out=dq_out if dq_out is not None else dqu,
+                              dq_done=dq_out is not None)
+    if r.core == ATTN_BIAS:
+        dbias = hip.relpos_attn_bwd(qu, k, v, r.bias, (r.ctx32, r.lse), dctx, dqu, dk, dv, B, H, T, dh, scale, pa, sa)
         dps = hip.relshift_bwd(dbias)                                                        # d (unshifted) pos score
         del dbias
     else:
-        dps = _mhsa_bwd_scores(dctx, qu, k, v, p, pd, dqu, dk, dv, B, T, H, dh, d, ldk, ldg, scale, pa, sa)
-    nbh = B * H
+        dps = _mhsa_bwd_scores(dctx, qu, k, v, r.p, r.pd, dqu, dk, dv, B, T, H, dh, d, ldk, ldg, scale, pa, sa)
     dqv = torch.empty((M, d), dtype=RT.gdtype, device=dev)
     hip.gemm(dps, pos, a_kc=True, b_kc=False, M=T, N=dh, K=T, lda=T, ldb=d, nbatch=nbh, batch_inner=H,
              sA=(H * T * T, T * T), sB=(0, dh), out=dqv, ldc=d, sC=(T * d, dh), precise=RT.precise)
@@ -907,8 +863,7 @@ def mhsa_bwd(dy, mod, saved, dy_dropped=None, next_kind=None):
     hip.gemm(dps, qv, a_kc=False, b_kc=False, M=T, N=dh, K=T, lda=T, ldb=d, nbatch=nbh, batch_inner=H,
              sA=(H * T * T, T * T), sB=(T * d, dh), out=dposb, ldc=d, sC=(T * d, dh), precise=RT.precise)
     del dps
-    return _mhsa_bwd_tail(dy, mod, att, x, ln, stats, pe, dqkv if fused is not None else None, dqu, dk, dv, dqv, dposb, fused, B, T, d, dev,
-                          drop=_next_drop(next_kind, saved), dq_out=dqkv[:, :d] if fused is not None else dqu, want16=next_kind is not None)
+    return _mhsa_bwd_tail(dy, mod, r, dqkv, dqu, dk, dv, dqv, dposb, fused, saved, next_kind, dq_out=dqkv[:, :d] if fused is not None else dqu)
 
 
 def _mhsa_bwd_scores(dctx, qu, k, v, p, pd, dqu, dk, dv, B, T, H, dh, d, ldk, ldg, scale, pa, sa):
@@ -933,52 +888,43 @@ def _mhsa_bwd_scores(dctx, qu, k, v, p, pd, dqu, dk, dv, B, T, H, dh, d, ldk, ld
     return dps
 
 
-def _mhsa_bwd_tail(dy, mod, att, x, ln, stats, pe, dqkv, dqu, dk, dv, dqv, dposb, fused, B, T, d, dev, drop=None, dq_out=None,
-                   dq_done=False, want16=False):
-    """Positional-projection, bias and q/k/v-projection gradients + LayerNorm backward (shared by both attention cores)."""
+def _mhsa_bwd_tail(dy, mod, r, dqkv, dqu, dk, dv, dqv, dposb, fused, saved, next_kind, dq_out, dq_done=False):
+    """Positional-projection, bias and q/k/v-projection gradients + LayerNorm backward (shared by the attention cores)."""
+    att = mod.attention
+    d, B, T = att.d_model, r.B, r.T
     if dposb.dtype == RT.gdtype:                                     # batch sum straight into the GEMM operand's dtype: one launch
         dpos_rt = hip.colsum_store(dposb.view(dposb.shape[0], T * d)).view(T, d)      # (B rows, or B * ntile partials of the fused backward)
     else:
-        dpos = torch.zeros((T * d,), dtype=torch.float32, device=dev)
+        dpos = torch.zeros((T * d,), dtype=torch.float32, device=r.x.device)
         hip.colsum(dposb.view(B, T * d), dpos, now=True)             # consumed right below
         dpos_rt = to_g(dpos.view(T, d))
-    mm_tn_acc(dpos_rt, pe, gbuf(att.pos_proj.linear.weight))
-    if dq_out is None:
-        dq_out = dqu
+    mm_tn_acc(dpos_rt, r.pe, gbuf(att.pos_proj.linear.weight))
     inplace = dq_out.data_ptr() == dqu.data_ptr()                    # dq = dqu + dqv overwrites dqu: its column sum has to run first
     hip.colsum(dqu, gbuf(att.u_bias).view(-1), now=inplace)
     hip.colsum(dqv, gbuf(att.v_bias).view(-1))
     dq = dq_out if dq_done else hip.axpby2d(dqu, dqv, 1.0, 1.0, out=dq_out)      # (dq_done: the attention backward wrote dqu + dqv itself)
     if fused is not None:
-        mm_tn_acc(dqkv, ln, fused[2], bias=fused[3])
+        mm_tn_acc(dqkv, r.ln, fused[2], bias=fused[3])
         dln = mm_nn(dqkv, fused[0], out_dtype=_F32 if RT.hybrid else None)
     else:
         for proj, g in ((att.query_proj, dq), (att.key_proj, dk), (att.value_proj, dv)):
-            mm_tn_acc(g, ln, gbuf(proj.linear.weight), bias=gbuf(proj.linear.bias))
+            mm_tn_acc(g, r.ln, gbuf(proj.linear.weight), bias=gbuf(proj.linear.bias))
         dln = mm_nn(dq, wtg(att.query_proj.linear.weight))
         dln = mm_nn(dk, wtg(att.key_proj.linear.weight), out=dln, ldc=d, resid=dln, ldr=d, res_scale=1.0)
         dln = mm_nn(dv, wtg(att.value_proj.linear.weight), out=dln, ldc=d, resid=dln, ldr=d, res_scale=1.0)
-    if RT.hybrid:
-        return _ln_bwd_hd(dln, x, mod.layer_norm, stats, _as_stream(dy), drop, want16)
-    return hip.layernorm_bwd(dln, x, mod.layer_norm.weight.data, stats, resid=dy, dgamma=gbuf(mod.layer_norm.weight),
-                             dbeta=gbuf(mod.layer_norm.bias), drop=drop)
+    return _ln_bwd(dln, r.x, mod.layer_norm, r.stats, dy, saved, next_kind)
 
 
 def convmod_fwd(x, cm, B, T, train, saved):
-    """x + ConformerConvModule(x)  (conformer/convolution.py:136-149)."""
+    """x + ConformerConvModule(x)  (conformer/convolution.py:136-149).  Hybrid mode: f32 stream in / out; the module's inner tensors (h, c, s)
+    are the fp16 tensors of the fp16 mode."""
     seq = cm.sequential
     d = x.shape[1]
     pw1, dw, bn, pw2 = seq[2].conv, seq[4].conv, seq[5], seq[7].conv
-    hyb = RT.hybrid
-    if hyb:
+    if RT.hybrid:
         x = _as_stream(x)
-    if hyb:                 # f32 stream in / out; the module's inner tensors (h, c, s) are the fp16 tensors of the fp16 mode
-        lnp, stats = hip.layernorm_fwd_pair(x, seq[0].weight.data, seq[0].bias.data, seq[0].eps, want_lo="pw1" in _H_ALO)
-        ln = lnp.hi
-        h = mm_nt_h(lnp, wpair(pw1.weight, (2 * d, d)), torch.float16, bias=pw1.bias.data)
-    else:
-        ln, stats = hip.layernorm_fwd(x, seq[0].weight.data, seq[0].bias.data, seq[0].eps)
-        h = mm_nt(ln, wt(pw1.weight).view(2 * d, d), bias=pw1.bias.data)                     # [M, 2d]
+    xn, ln, stats = _ln_in(x, seq[0], "pw1")
+    h = _linear(xn, pw1.weight, (2 * d, d), "branch", bias=pw1.bias.data)                    # [M, 2d]
     g = None
     if d % 8 == 0:            # GLU + depthwise conv + BatchNorm batch sums in one LDS-tiled pass (csrc/dwconv.hip)
         c, sums = hip.dwglu_fwd(h, dw.weight.data.view(d, -1), B, T, want_stats=True) if train else \
@@ -995,52 +941,37 @@ def convmod_fwd(x, cm, B, T, train, saved):
     s = (s_act if s_act is not None else hip.cl_affine_act(c, d, aff, SWISH)).view(B * T, d)
     po = _p(seq[8], train)
     if _replaying(train) and po > 0:                       # the reference draws this mask on the (B, d, T) conv output
-        y = mm_nt_h(s, wpair(pw2.weight, (d, d)), _F32, bias=pw2.bias.data) if hyb else mm_nt(s, wt(pw2.weight).view(d, d), bias=pw2.bias.data)
+        y = _linear(s, pw2.weight, (d, d), "stream", bias=pw2.bias.data)
         so = RT.replay.mask((B, d, T), po, x.device, y.dtype, to_layout=lambda m: m.permute(0, 2, 1).reshape(B * T, d))
         y = x + y * so
-    elif hyb:
-        so = RT.next_seed() if po > 0 else 0
-        y = mm_nt_h(s, wpair(pw2.weight, (d, d)), _F32, bias=pw2.bias.data, p_drop=po, seed=so, resid=x, ldr=x.stride(0), res_scale=1.0)
     else:
         so = RT.next_seed() if po > 0 else 0
-        y = mm_nt(s, wt(pw2.weight).view(d, d), bias=pw2.bias.data, p_drop=po, seed=so, resid=x, ldr=x.stride(0), res_scale=1.0)
-    saved.append((x, ln, stats, h, g, c, aff, s, po, so, B, T, train))
+        y = _linear(s, pw2.weight, (d, d), "stream", bias=pw2.bias.data, p_drop=po, seed=so, resid=x, ldr=x.stride(0), res_scale=1.0)
+    saved.append(ConvRec(x=x, ln=ln, stats=stats, h=h, g=g, c=c, aff=aff, s=s, po=po, so=so, B=B, T=T, train=train))
     return y
 
 
 def convmod_bwd(dy, cm, saved, dy_dropped=None, next_kind=None):
-    x, ln, stats, h, g, c, aff, s, po, so, B, T, train = saved.pop()
+    r = saved.pop()
+    x, h, c, aff, B, T = r.x, r.h, r.c, r.aff, r.B, r.T
     seq = cm.sequential
     d = x.shape[1]
     pw1, dw, bn, pw2 = seq[2].conv, seq[4].conv, seq[5], seq[7].conv
-    if RT.hybrid:
-        dout = _grad16(dy, dy_dropped, po, so)
-        if torch.is_tensor(so):
-            dout = dout * so.to(dout.dtype)
-    elif torch.is_tensor(so):
-        dout = dy * so.to(dy.dtype)
-    elif dy_dropped is not None:
-        dout = dy_dropped
-    else:
-        dout = hip.act_bwd(dy, None, 0, p_drop=po, seed=so) if po > 0 else dy
-    mm_tn_acc(dout, s, gbuf(pw2.weight), bias=gbuf(pw2.bias))
+    dout = _grad_in(dy, dy_dropped, r.po, r.so)
+    mm_tn_acc(dout, r.s, gbuf(pw2.weight), bias=gbuf(pw2.bias))
     ds = mm_nn(dout, wtg(pw2.weight).view(d, d))
     red = hip.cl_bn_bwd_reduce(ds, c, d, aff, SWISH)
-    dc = hip.cl_bn_bwd_apply(ds, c, d, aff, SWISH, False, train, red, out=ds, pgrads=(gbuf(bn.weight), gbuf(bn.bias))).view(B, T, d)
-    if g is None:                        # fused forward: the GLU output was never stored
+    dc = hip.cl_bn_bwd_apply(ds, c, d, aff, SWISH, False, r.train, red, out=ds, pgrads=(gbuf(bn.weight), gbuf(bn.bias))).view(B, T, d)
+    if r.g is None:                      # fused forward: the GLU output was never stored
         dh = hip.dwglu_bwd(dc.view(B * T, d), h, dw.weight.data.view(d, -1), B, T)
         hip.dwglu_wgrad(dc.view(B * T, d), h, gbuf(dw.weight).view(d, -1), B, T)
     else:
         dg = hip.dwconv(dc, dw.weight.data.view(d, -1), flip=True)
-        hip.dwconv_wgrad(dc, g.view(B, T, d), gbuf(dw.weight).view(d, -1))
+        hip.dwconv_wgrad(dc, r.g.view(B, T, d), gbuf(dw.weight).view(d, -1))
         dh = hip.glu_bwd(dg.view(B * T, d), h)
-    mm_tn_acc(dh, ln, gbuf(pw1.weight), bias=gbuf(pw1.bias))
-    if RT.hybrid:
-        dln = mm_nn(dh, wtg(pw1.weight).view(2 * d, d), out_dtype=_F32)
-        return _ln_bwd_h(dln, x, seq[0], stats, _as_stream(dy), saved, next_kind, next_kind is not None)
-    dln = mm_nn(dh, wtg(pw1.weight).view(2 * d, d))
-    return hip.layernorm_bwd(dln, x, seq[0].weight.data, stats, resid=dy, dgamma=gbuf(seq[0].weight), dbeta=gbuf(seq[0].bias),
-                             drop=_next_drop(next_kind, saved))
+    mm_tn_acc(dh, r.ln, gbuf(pw1.weight), bias=gbuf(pw1.bias))
+    dln = mm_nn(dh, wtg(pw1.weight).view(2 * d, d), out_dtype=_F32 if RT.hybrid else None)
+    return _ln_bwd(dln, x, seq[0], r.stats, dy, saved, next_kind)
 
 
 def block_fwd(x, blk, B, T, train, saved, out=None, next_blk=None, rows=None):
@@ -1061,7 +992,7 @@ def block_fwd(x, blk, B, T, train, saved, out=None, next_blk=None, rows=None):
             y, stats = hip.layernorm_fwd_pair(_as_stream(xc), seq[4].weight.data, seq[4].bias.data, seq[4].eps, out=out)
         else:
             y, stats = hip.layernorm_fwd(xc, seq[4].weight.data, seq[4].bias.data, seq[4].eps, out=out)
-        saved.append((xc, stats, (rows, B, T), x))          # (x: the full-row input of the tail, for a full prediction on request - vis)
+        saved.append(BlockRec(x=xc, stats=stats, rows=rows, B=B, T=T, x_full=x))
         return y
     x = ffn_fwd(x, seq[3].module, seq[3].module_factor, train, saved)
     if next_blk is not None and out is None and not (RT.hybrid and _H_FFN2_FWD and x.shape[1] in _FFN2_WIDTHS and not _replaying(train)
@@ -1079,7 +1010,7 @@ def block_fwd(x, blk, B, T, train, saved, out=None, next_blk=None, rows=None):
         y._pre_ln = (nln, z, zstats)
     else:
         y, stats = hip.layernorm_fwd(x, seq[4].weight.data, seq[4].bias.data, seq[4].eps, out=out)
-    saved.append((x, stats))
+    saved.append(BlockRec(x=x, stats=stats))
     return y
 
 
@@ -1088,26 +1019,22 @@ def block_bwd(dy, blk, saved, first=False):
     the block's last LayerNorm backward writes that copy next to the f32 gradient (attribute ``_g16``) instead of a cast pass."""
     seq = blk.sequential
     top = saved.pop()
-    x, stats = top[0], top[1]
-    rows = top[2] if len(top) > 2 else None        # compact tail (block_fwd(rows=...)): dy, x are [B * nm, d]
+    compact = top.rows is not None                 # compact tail (block_fwd(rows=...)): dy, top.x are [B * nm, d]
     # the block's ~9 bias-gradient column sums and the reductions of its 9 split-K weight-gradient products: one launch each, at the end
     with hip.colsum_batched(), hip.splitk_batched(), hip.ln_reduce_batched(), wgrad_block():
         # each module's backward starts with the dropout backward of its incoming gradient: the LayerNorm backward that produces
-        # that gradient writes the dropped copy as a second output (d = (gradient, dropped gradient) where a mask applies)
+        # that gradient writes the dropped copy as a second output (d = (gradient, dropped gradient) where a mask applies; hybrid: the f32
+        # stream gradient d + the bf16 operand copy dd of the module that consumes it next)
         pair = lambda r: r if isinstance(r, tuple) else (r, None)
-        if RT.hybrid:       # f32 stream gradient (d) + the bf16 operand copy of the module that consumes it next (dd)
-            d, dd = _ln_bwd_h(_as_stream(dy), x, seq[4], stats, None, saved, "ffn", True)
-        else:
-            d, dd = pair(hip.layernorm_bwd(dy, x, seq[4].weight.data, stats, dgamma=gbuf(seq[4].weight), dbeta=gbuf(seq[4].bias),
-                                           drop=_next_drop("ffn", saved)))
-        if rows is not None:    # the tail ran on the gathered rows: its input gradient goes back to its frames, zeros elsewhere
+        d, dd = pair(_ln_bwd(_as_stream(dy) if RT.hybrid else dy, top.x, seq[4], top.stats, None, saved, "ffn"))
+        if compact:             # the tail ran on the gathered rows: its input gradient goes back to its frames, zeros elsewhere
             d = pair(ffn_bwd(d, seq[3].module, saved, dy_dropped=dd, next_kind=None))[0]
             drop = _next_drop("conv", saved) if (RT.hybrid and d.dtype == _F32) else None
             if drop is not None:       # the scatter also writes the convolution module's bf16 operand (its dropout backward applied)
-                d, dd = hip.scatter_rows_drop16(d.contiguous(), rows[0], rows[1], rows[2], *drop)
+                d, dd = hip.scatter_rows_drop16(d.contiguous(), top.rows, top.B, top.T, *drop)
                 dd._dropped = True
             else:
-                d, dd = hip.scatter_rows(d, rows[0], rows[1], rows[2]), None
+                d, dd = hip.scatter_rows(d, top.rows, top.B, top.T), None
         else:
             d, dd = pair(ffn_bwd(d, seq[3].module, saved, dy_dropped=dd, next_kind="conv"))
         d, dd = pair(convmod_bwd(d, seq[2].module, saved, dy_dropped=dd, next_kind="mhsa"))
@@ -1145,22 +1072,22 @@ def encoder_bwd(dy, enc, saved):
 
 # ------------------------------------------------------------------------------------------------ decoder + loss
 def decoder_fwd(e, dec, saved):
-    """EmbedDecoder ['','fc'] (code/model.py:295-301, 321-334): Linear -> ReLU -> Linear."""
+    """EmbedDecoder ['','fc'] (code/model.py:295-301, 321-334): Linear -> ReLU -> Linear.  Hybrid mode: f32 decoder input as an fp16 pair, fp16
+    hidden layer, f32 prediction."""
     l1, l2 = dec.proj[0], dec.proj[2]
-    if RT.hybrid:           # f32 decoder input as an fp16 pair, fp16 hidden layer, f32 prediction
+    xin = e
+    if RT.hybrid:
         ep = e if isinstance(e, hip.Pair) else hip.split_pair(_as_stream(e).contiguous())
-        h = mm_nt_h(ep if "dec1" in _H_ALO else ep.hi, wpair(l1.weight), torch.float16, bias=l1.bias.data, act=RELU)
-        pred = mm_nt_h(h, wpair(l2.weight), _F32, bias=l2.bias.data)
-        saved.append((ep.hi, h))
-        return pred
-    h = mm_nt(e, wt(l1.weight), bias=l1.bias.data, act=RELU)
-    pred = mm_nt(h, wt(l2.weight), bias=l2.bias.data)
-    saved.append((e, h))
+        xin, e = (ep if "dec1" in _H_ALO else ep.hi), ep.hi
+    h = _linear(xin, l1.weight, None, "branch", bias=l1.bias.data, act=RELU)
+    pred = _linear(h, l2.weight, None, "stream", bias=l2.bias.data)
+    saved.append(DecRec(e=e, h=h))
     return pred
 
 
 def decoder_bwd(dpred, dec, saved):
-    e, h = saved.pop()
+    r = saved.pop()
+    e, h = r.e, r.h
     l1, l2 = dec.proj[0], dec.proj[2]
     with hip.colsum_batched(), hip.splitk_batched(), wgrad_block():
         mm_tn_acc(dpred, h, gbuf(l2.weight), bias=gbuf(l2.bias))
@@ -1187,13 +1114,13 @@ def head_fwd(x, seq, saved):
         y = hip.small_linear_fwd(h, lin.weight.data.contiguous(), lin.bias.data if lin.bias is not None else None, act)
         acts.append((h, y, act))
         h = y
-    saved.append((x, stats, acts))
+    saved.append(HeadRec(x=x, stats=stats, acts=acts))
     return h
 
 
 def head_bwd(dy, seq, saved):
     ln_mod, lins = _head_layers(seq)
-    x, stats, acts = saved.pop()
-    for lin, (h, y, act) in reversed(list(zip(lins, acts))):
+    r = saved.pop()
+    for lin, (h, y, act) in reversed(list(zip(lins, r.acts))):
         dy = hip.small_linear_bwd(dy, y, h, lin.weight.data.contiguous(), act, gbuf(lin.weight), gbuf(lin.bias) if lin.bias is not None else None)
-    return hip.layernorm_bwd(dy, x, ln_mod.weight.data, stats, dgamma=gbuf(ln_mod.weight), dbeta=gbuf(ln_mod.bias))
+    return hip.layernorm_bwd(dy, r.x, ln_mod.weight.data, r.stats, dgamma=gbuf(ln_mod.weight), dbeta=gbuf(ln_mod.bias))

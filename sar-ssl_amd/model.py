@@ -209,7 +209,7 @@ class _PretrainFn(torch.autograd.Function):
         else:
             net.spec_encoder._fwd_cl(spec_in, B, T, saved, out=ecat[:, :ds])
             net.spat_encoder._fwd_cl(spat_in, B, T, saved_spat, out=ecat[:, ds:])
-        tails_x = (saved[-1][3], saved_spat[-1][3]) if tail else None      # full-row inputs of the two compact tails (vis on request)
+        tails_x = (saved[-1].x_full, saved_spat[-1].x_full) if tail else None      # full-row inputs of the two compact tails (vis on request)
         saved.append(saved_spat)
         sink = net.__dict__.get("_loss_sink")            # graph.py: (persistent f32[2], running f64[2] sums) filled by the finalize launch
         ctx.dpred = None

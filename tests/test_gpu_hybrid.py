@@ -163,17 +163,17 @@ def test_fused_feed_forward_on_the_f32_stream_equals_the_unfused_sequence(train,
             y = engine.ffn_fwd(x.clone(), ff, 0.5, train, saved)
             res[fused] = (y, saved[0])
         (yf, sf), (yu, su) = res[True], res[False]
-        for i, name in ((1, "ln_hi"), (2, "stats")):
-            assert torch.equal(sf[i], su[i]), name
+        for name in ("ln", "stats"):
+            assert torch.equal(getattr(sf, name), getattr(su, name)), name
         # pre-activation / hidden tensor: the same products accumulated in another order (k-step-major here, segment-major there) - equal
         # up to the f32 summation order, i.e. an fp16 ulp on a fraction of the entries
-        for i, name in ((3, "preact"), (4, "hidden")):
-            a, b = sf[i].float(), su[i].float()
+        for f, name in (("hpre", "preact"), ("a", "hidden")):
+            a, b = getattr(sf, f).float(), getattr(su, f).float()
             check("%s.%s_vs_unfused" % (tag, name), ((a - b).abs().max() / b.abs().max()).item(), 1e-3)
             assert (a != b).float().mean().item() < 0.02, name
             if train and name == "hidden":
                 assert torch.equal(a == 0, b == 0)            # the same dropout mask
-        assert sf[5:] == su[5:]
+        assert (sf.p1, sf.s1, sf.p2, sf.s2, sf.factor) == (su.p1, su.s1, su.p2, su.s2, su.factor)
         check(tag + ".y_vs_unfused", _rel(yf, yu), 2e-4)
         if not train:
             seq = ff.sequential

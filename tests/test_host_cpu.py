@@ -273,3 +273,31 @@ def test_repeated_mask_indices_are_refused():
     net.set_masks(np.array([[5, 0, 2, 7]]), np.array([1]))
     idx, ch, mp = net._masks(1, 8, torch.device("cpu"))
     assert idx.tolist() == [[0, 2, 5, 7]] and mp.tolist() == [[0, 1, 0, 1, 1, 0, 1, 0]]
+
+
+def test_next_drop_reads_the_incoming_dropout_of_the_record_on_top():
+    """engine._next_drop hands the LayerNorm backward the (p, seed, gscale) of the dropout backward that the next module of the backward
+    chain applies to its incoming gradient: each module record's ``drop_in``, whatever else the record holds - and nothing where there is
+    no mask to apply, the masks are replayed host tensors, or nobody / a consumer without dropout follows."""
+    from sar_ssl_amd import engine
+
+    def rec(kind, p, seed, g):
+        if kind == "ffn":       # the output dropout (p2, s2) and the module factor - not the hidden layer's (p1, s1)
+            return engine.FfnRec(x=None, ln=None, stats=None, hpre=None, a=None, p1=0.3, s1=11, p2=p, s2=seed, factor=g)
+        if kind == "conv":
+            return engine.ConvRec(x=None, ln=None, stats=None, h=None, g=None, c=None, aff=None, s=None, po=p, so=seed, B=2, T=16, train=True)
+        return engine.MhsaRec(x=None, ln=None, stats=None, qu=None, qv=None, k=None, v=None, pos=None, pe=None, core=engine.ATTN_POS, bias=None,
+                              ctx32=None, lse=None, p=None, pd=None, pa=0.2, sa=13, ctx=None, po=p, so=seed, B=2, T=16)
+
+    for kind, g in (("ffn", 0.5), ("conv", 1.0), ("mhsa", 1.0)):
+        below = rec("conv" if kind != "conv" else "ffn", 0.7, 99, 1.0)            # only the record on top counts
+        got = engine._next_drop(kind, [below, rec(kind, 0.1, 1234, g)])
+        assert got == (0.1, 1234, g) and [type(v) for v in got] == [float, int, float], kind
+        assert engine._next_drop(kind, [rec(kind, 0.1, torch.ones(4), g)]) is None, kind          # a replayed mask
+        assert engine._next_drop(kind, [rec(kind, 0.0, 0, 1.0)]) is None, kind                     # nothing to apply
+        assert engine._next_drop(None, [rec(kind, 0.1, 1234, g)]) is None
+        assert engine._next_drop("copy", [rec(kind, 0.1, 1234, g)]) is None
+        assert engine._next_drop(kind, []) is None
+    # the feed-forward module's factor alone is a reason to write the second output (p = 0, gscale = 0.5)
+    assert engine._next_drop("ffn", [rec("ffn", 0.0, 0, 0.5)]) == (0.0, 0, 0.5)
+    assert engine._next_drop("ffn", [rec("ffn", torch.tensor(0.1), 5, 0.5)]) is None
