@@ -333,6 +333,18 @@ int sarssl_conv3x3_fwd_c1(const void* a0, const float* W1, const float* scale, c
                           int nb, int F, int T, double* stats, int dtype, void* stream);      /* dtype of a0 / w / out: bf16 | fp16 */
 int sarssl_conv3x3_wgrad_c1_acc(const void* dy, const void* a0, const float* W1, int nb, int F, int T, const float* scale,
                                 const float* shift, float* grad_oihw, float* partial, int a0_dtype, void* stream);
+/* The stem's two 3x3 weight gradients with the BatchNorm backward of their dy operand formed while the tile is staged (no streaming pass
+ * that writes dy, no re-read of it): dy is stored once (dy3_out / dy_out, bf16) for the data-gradient launch that follows.  y_dtype: encoding
+ * of the saved forward tensors (bf16 | fp16, the same for all of a call); gradients are bf16; aff = [4][64] scale | shift | mean | rstd.
+ * dgamma / dbeta (/ gW4): parameter-gradient buffers that receive the finished sums (all or none).
+ *   _c4_acc       : dy3 = second phase of sarssl_stem_c4_bwd_apply (y3, dy4, W4, aff3, red f64[384]); grad_oihw += wgrad(dy3, relu(scale*y2+shift))
+ *   _c1_apply_acc : dy2 = sarssl_cl_bn_bwd_apply's ReLU path (dz, y, aff, red f64[128]); dy_out may be dz; grad_oihw += the _c1_acc product */
+int sarssl_conv3x3_wgrad_c4_acc(const void* y3, const void* dy4, const float* W4, const float* aff3, const double* red, int use_stats,
+                                const void* y2, const float* scale, const float* shift, int nb, int F, int T, void* dy3_out,
+                                float* grad_oihw, float* partial, float* gW4, float* dgamma, float* dbeta, int y_dtype, void* stream);
+int sarssl_conv3x3_wgrad_c1_apply_acc(const void* dz, const void* y, const float* aff, const double* red, int use_stats, void* dy_out,
+                                      const void* a0, const float* W1, const float* scale, const float* shift, int nb, int F, int T,
+                                      float* grad_oihw, float* partial, float* dgamma, float* dbeta, int y_dtype, void* stream);
 int sarssl_stem_c1_bwd_a0(const void* dz1, const void* a0, const float* W1, long npix, const float* aff, int use_stats,
                           double* red, float* dW1, float* dgamma, float* dbeta, int dtype, void* stream);     /* bf16 | mixed 16 (a0 fp16) */
 /* conv3x3_dgrad_c1red: data gradient of patch_embed[3] consumed in its epilogue (masked with relu'(bn1(W1 a0)) and contracted over the

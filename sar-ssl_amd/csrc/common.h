@@ -187,6 +187,48 @@ __device__ __forceinline__ void st8(bf16* p, const f8& r) {
     *(uint4*)p = u;
 }
 
+// BatchNorm-backward "apply" arithmetic of the CNN stem, shared by the streaming kernels (stem.hip: cl_bn_bwd_apply_kernel's ReLU fast
+// path, stem_c4_bwd_kernel<.., 2>) and by the staging waves of the weight-gradient kernel that form the same gradient on the fly
+// (conv3x3.hip).  Every multiply-add is an explicit fmaf (or a lone product): the inlined copies cannot be contracted differently, so
+// the two callers produce the same bits.
+//   sc * (g - m1 - (y - mu) * rs * m2) = A*g + (B*y + C)   with sc = gamma * rstd, m1 = s1 / N, m2 = s2 / N
+__device__ __forceinline__ void bn_bwd_abc(float sc, float mu, float rs, float m1, float m2, float& A, float& B, float& C) {
+    A = sc;
+    B = -sc * m2 * rs;
+    C = fmaf(-sc, m1, -(B * mu));
+}
+// relu'(y*sc + sh) as a threshold test on y: the mask is (neg ? -y : y) > thr
+__device__ __forceinline__ float bn_relu_thr(float sc, float sh, bool& neg) {
+    float t = sc != 0.f ? -sh / sc : (sh > 0.f ? -INFINITY : INFINITY);
+    neg = sc < 0.f;
+    return neg ? -t : t;
+}
+// o[e] = A*g + (B*y + C), g = d masked by the threshold test (bit e of sgn: the channel's scale is negative); NE channels
+template <int NE>
+__device__ __forceinline__ void bn_bwd_apply_relu(const float* d, const float* y, const float* A, const float* B, const float* C,
+                                                  const float* thr, unsigned sgn, float* o) {
+#pragma unroll
+    for (int e = 0; e < NE; ++e) {
+        const float ys = __uint_as_float(__float_as_uint(y[e]) ^ (((sgn >> e) & 1u) << 31));
+        const float g = ys > thr[e] ? d[e] : 0.f;
+        o[e] = fmaf(A[e], g, fmaf(B[e], y[e], C[e]));
+    }
+}
+// Second phase of the 64->4 backward: o[e] = A*g + (B*y + C), g = (sum_c d4[c] * w[c][e]) masked by relu'(y*sc + sh); NE channels,
+// d4 = the pixel's four output-gradient values, w[c] = row c of W4 at these channels
+template <int NE>
+__device__ __forceinline__ void stem_c4_bwd_apply(const float* y, const float4& d4, const float* w0, const float* w1, const float* w2,
+                                                  const float* w3, const float* sc, const float* sh, const float* A, const float* B,
+                                                  const float* C, float* o) {
+#pragma unroll
+    for (int e = 0; e < NE; ++e) {
+        const float uu = fmaf(y[e], sc[e], sh[e]);
+        float gi = fmaf(d4.w, w3[e], fmaf(d4.z, w2[e], fmaf(d4.x, w0[e], d4.y * w1[e])));
+        gi = (uu > 0.f) ? gi : 0.f;
+        o[e] = fmaf(A[e], gi, fmaf(B[e], y[e], C[e]));
+    }
+}
+
 // 32x32x16 MFMA on 16-bit operands of type TM (bf16x8 is the 128-bit fragment carrier for both encodings; same rate)
 template <typename TM>
 __device__ __forceinline__ f32x16 mfma16(const bf16x8& a, const bf16x8& b, const f32x16& c) {

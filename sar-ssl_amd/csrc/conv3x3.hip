@@ -963,7 +963,18 @@ struct WgradArgs {
     int nb, F, T;
     int part_dy, part_z;
     const float* c1_w;    // first-layer input mode (see ConvArgs::c1_w): zin = a0 (B,F,T,4), the operand relu(bn1(W1 a0)) is formed while staging
+    // role-split kernel, DYSRC != DY_LOAD: the staging waves FORM dy (a BatchNorm backward) instead of loading it, write it to the LDS
+    // tile and store it once to dy_out for the data-gradient launch that follows (see conv3x3_wgrad_ws_kernel)
+    const void* y;        // (B,F,T,64) pre-BatchNorm activations of the layer dy belongs to
+    const float* aff;     // [4][64]: scale, shift, mean, rstd of that BatchNorm
+    const double* red;    // its finished backward sums: DY_APPLY f64[128] = s1 | s2;  DY_C4 f64[384] = dW4 | s1 | s2
+    int use_stats;        // 0: eval-mode BatchNorm (dy = gamma * rstd * g)
+    void* dy_out;         // (B,F,T,64) bf16; DY_APPLY: may be the same buffer as dy (= dz)
+    const void* dy4;      // DY_C4: (B,T,F,4) bf16 gradient of the 64->4 convolution's output
+    const float* W4;      // DY_C4: f32[4][64]
+    float* pg_w4; float* pg_gamma; float* pg_beta;   // parameter gradients added from red by workgroup 0 (all null: none; pg_w4: DY_C4 only)
 };
+enum { DY_LOAD = 0, DY_APPLY = 1, DY_C4 = 2 };
 
 // Weight-gradient tiles use a column-parity swizzle: 16-byte chunk index XOR 4*((column >> 1) & 1).  A 32-lane transpose read
 // touches 4 consecutive pixels x 4 consecutive chunks; pixels x and x+2 share a bank half, and this flips which four chunks of it
@@ -1117,11 +1128,27 @@ __global__ __launch_bounds__(512) void conv3x3_wgrad_kernel(WgradArgs a) {
 #define WHC (WTC + 2)
 #define WX_ELEMS (HR * WHC * 64)
 #define WY_ELEMS (TR * WTC * 64)
-template <bool C1IN = false, typename TA = bf16>
+// DYSRC: where the staging waves get the dy tile from.
+//   DY_LOAD  : dy is read from HBM.
+//   DY_APPLY : dy = BatchNorm + ReLU backward of (a.dy = dz, a.y) - cl_bn_bwd_apply_kernel's ReLU fast path (bn_bwd_apply_relu).
+//   DY_C4    : dy = the 64->4 convolution's masked data gradient through the third BatchNorm's backward, from (a.y = y3, a.dy4) -
+//              stem_c4_bwd_kernel<.., 2> (stem_c4_bwd_apply).
+// In the last two the finished bf16 chunk goes to the LDS tile AND to a.dy_out (in-image pixels only), so the streaming pass that used to
+// produce it, and the re-read of its result here, are gone.  The dy operand has no halo: every pixel is formed exactly once per launch, by
+// one thread, from that thread's own loads - which is what allows dy_out to overwrite dz in place.  The per-channel constants (32 / 56
+// floats per thread, next to the 16 / 40 of the z prologue) do not fit beside the prefetch registers under the 128-register cap: they
+// live in a workgroup-wide LDS table sK and are read back per tile - the z prologue's in front of the halo pieces, dy's four channels at a
+// time while the dy piece is formed.  TY: encoding of a.y.
+template <bool C1IN = false, typename TA = bf16, int DYSRC = DY_LOAD, typename TY = bf16>
 __global__ __launch_bounds__(1024) void conv3x3_wgrad_ws_kernel(WgradArgs a) {
     typedef bf16 T;
     __shared__ __attribute__((aligned(16))) uint16_t sYb[2][WY_ELEMS];   // dy tiles  [8*32 px][64 co]
     __shared__ __attribute__((aligned(16))) uint16_t sXb[2][WX_ELEMS];   // z halo tiles [340 px][64 ci]
+    // rows of 64 channels.  DY_APPLY: A | B | C | thr | sign flag;  DY_C4: W4[0..3] | scale | shift | B | C  (A = scale); behind them the z
+    // prologue's constants: scale | shift rows, or (C1IN) one C1Const per 8-channel group
+    constexpr int KROWS = DYSRC == DY_C4 ? 8 : 5, KZ = KROWS * 64;
+    static_assert(sizeof(C1Const) == 40 * sizeof(float), "C1Const layout");
+    __shared__ __attribute__((aligned(16))) float sK[DYSRC == DY_LOAD ? 4 : KZ + (C1IN ? 8 * 40 : 2 * 64)];
     const int lane = threadIdx.x & 63;
     const int wave_all = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const bool producer = wave_all >= 8;
@@ -1142,10 +1169,12 @@ __global__ __launch_bounds__(1024) void conv3x3_wgrad_ws_kernel(WgradArgs a) {
         // ---- staging waves: tile `it + 1` is written into the free buffer while the MFMA waves are on tile `it`; the loads of tile
         // `it + 2` are issued right behind the writes and have the rest of the iteration (the wait at the barrier) to land
         float sc[8], sh[8];
-    #pragma unroll
-        for (int e = 0; e < 8; ++e) { sc[e] = a.prologue ? a.scale[cch * 8 + e] : 1.f; sh[e] = a.prologue ? a.shift[cch * 8 + e] : 0.f; }
         C1Const kc1;
-        if (C1IN) c1_setup(kc1, a.c1_w, a.scale, a.shift, cch * 8);
+        if constexpr (DYSRC == DY_LOAD) {
+    #pragma unroll
+            for (int e = 0; e < 8; ++e) { sc[e] = a.prologue ? a.scale[cch * 8 + e] : 1.f; sh[e] = a.prologue ? a.shift[cch * 8 + e] : 0.f; }
+            if (C1IN) c1_setup(kc1, a.c1_w, a.scale, a.shift, cch * 8);
+        }
         auto load_z = [&](int b, int f, int t) __attribute__((always_inline)) {                    // clamped, unconditional (load_chunk_clamped); C1IN: the pixel's 4 input channels
             Chunk<TA> c;
             if (C1IN) {
@@ -1164,7 +1193,8 @@ __global__ __launch_bounds__(1024) void conv3x3_wgrad_ws_kernel(WgradArgs a) {
         //  one vector byte offset per thread for all rows of a tensor, one lane-constant LDS base per tensor with the row step as an
         //  immediate: 1426 -> 1019 vector issue slots per tile.  The launch time did not move (379 us alone, +0.2 % on the step): like the
         //  operand-read and look-ahead experiments in tools/conv_ng3/, it says this kernel is bound by none of them.)
-        Chunk<TA> rz[6]; Chunk<T> ry[4];
+        Chunk<TA> rz[6]; Chunk<T> ry[4];      // ry: DY_LOAD dy, DY_APPLY dz, DY_C4 unused
+        Chunk<TY> rv[4]; uint2 rd[4];         // DYSRC != DY_LOAD: the y chunks; DY_C4: the pixels' four dy4 values
         const int pcol = (tid >> 3) & 31;
         const int pr = __builtin_amdgcn_readfirstlane(tid >> 8);
         const int lbX = swzc(pr * WHC + pcol, pcol, cch), lbY = swzc(pr * WTC + pcol, pcol, cch);     // LDS element offsets of row pr; row pr + 2k: + k * 2 * W?C * 64
@@ -1187,10 +1217,14 @@ __global__ __launch_bounds__(1024) void conv3x3_wgrad_ws_kernel(WgradArgs a) {
                 const int q = tid >> 3, hr = q >> 1, te = tc.t0 + WTC - 1 + (q & 1);        // (threads >= 160: an unused, harmless extra chunk)
                 rz[5] = load_z(tc.b, tc.f0 - 1 + hr, te);
             }
+            const char* vimg = (const char*)a.y + (long)tc.b * F * (long)Tn * 128;
+            const char* dcol = (const char*)a.dy4 + ((long)tc.b * Tn + ty) * (long)F * 8;    // DY_C4: dy4 is (B,T,F,4) - the column's bins are 8 bytes apart
     #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const int f = min(tc.f0 + pr + 2 * k, F - 1);
-                ry[k].u = *(const uint4*)(yimg + (unsigned)f * yrow + vy);
+                if constexpr (DYSRC != DY_C4) ry[k].u = *(const uint4*)(yimg + (unsigned)f * yrow + vy);
+                if constexpr (DYSRC != DY_LOAD) rv[k].u = *(const uint4*)(vimg + (unsigned)f * yrow + vy);
+                if constexpr (DYSRC == DY_C4) rd[k] = *(const uint2*)(dcol + (unsigned)f * 8u);
             }
         };
         // the tile is written in three pieces (halo rows 0-2 of this thread | halo rows 3-4 + edge columns | dy rows) so that the pieces can be
@@ -1211,18 +1245,129 @@ __global__ __launch_bounds__(1024) void conv3x3_wgrad_ws_kernel(WgradArgs a) {
                 }
             } else {
                 const int ty = tc.t0 + pcol;
+                if constexpr (DYSRC == DY_LOAD) {
     #pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    *(uint4*)&sY[lbY + k * (2 * WTC * 64)] = xform_chunk<T>(ry[k], tc.f0 + pr + 2 * k < F && ty < Tn, 0, sc, sh, 0);
+                    for (int k = 0; k < 4; ++k) {
+                        *(uint4*)&sY[lbY + k * (2 * WTC * 64)] = xform_chunk<T>(ry[k], tc.f0 + pr + 2 * k < F && ty < Tn, 0, sc, sh, 0);
+                    }
+                } else {
+                    uint32_t o[4][4];
+                    // NE channels at a time: 20 (DY_APPLY, 4) / 16 (DY_C4, 2) constants live.  DY_C4 with 4 (32 constants): 44 B of scratch,
+                    // and it is the prefetched chunks that spill
+                    constexpr int NE = DYSRC == DY_C4 ? 2 : 4;
+                    auto word = [](const uint4& u, int i) __attribute__((always_inline)) { return i == 0 ? u.x : i == 1 ? u.y : i == 2 ? u.z : u.w; };
+    #pragma unroll
+                    for (int h = 0; h < 8 / NE; ++h) {
+                        const int c0 = cch * 8 + h * NE;
+                        __builtin_amdgcn_sched_barrier(0);      // keep this group's table reads behind the previous group's arithmetic
+                        auto row = [&](int r, float* v) __attribute__((always_inline)) {
+                            if constexpr (NE == 4) { const float4 q = *(const float4*)&sK[r * 64 + c0]; v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w; }
+                            else { const float2 q = *(const float2*)&sK[r * 64 + c0]; v[0] = q.x; v[1] = q.y; }
+                        };
+                        float kA[NE], kB[NE], kC[NE];
+                        if constexpr (DYSRC == DY_APPLY) {
+                            float thr[NE], sf[NE];
+                            row(0, kA); row(1, kB); row(2, kC); row(3, thr); row(4, sf);
+                            unsigned sgn = 0u;
+    #pragma unroll
+                            for (int e = 0; e < NE; ++e) sgn |= __float_as_uint(sf[e]) << e;
+    #pragma unroll
+                            for (int k = 0; k < 4; ++k) {
+                                float d[NE], y[NE], r[NE];
+    #pragma unroll
+                                for (int j = 0; j < NE / 2; ++j) {
+                                    const uint32_t dw = word(ry[k].u, h * (NE / 2) + j), yw = word(rv[k].u, h * (NE / 2) + j);
+                                    d[2 * j] = H16<T>::lo(dw); d[2 * j + 1] = H16<T>::hi(dw);
+                                    y[2 * j] = H16<TY>::lo(yw); y[2 * j + 1] = H16<TY>::hi(yw);
+                                }
+                                bn_bwd_apply_relu<NE>(d, y, kA, kB, kC, thr, sgn, r);
+    #pragma unroll
+                                for (int j = 0; j < NE / 2; ++j) {
+                                    o[k][h * (NE / 2) + j] = pack2_bf16(r[2 * j], r[2 * j + 1]);
+                                    // the result exists HERE: otherwise hipcc sinks rows 1-3 of every group into the conditional store blocks
+                                    // below, all groups' constants stay live across them and the prefetched chunks go to scratch
+                                    asm volatile("" : "+v"(o[k][h * (NE / 2) + j]));
+                                }
+                            }
+                        } else {
+                            float w0[NE], w1[NE], w2[NE], w3[NE], s3[NE], h3[NE];
+                            row(0, w0); row(1, w1); row(2, w2); row(3, w3); row(4, s3); row(5, h3); row(6, kB); row(7, kC);
+    #pragma unroll
+                            for (int k = 0; k < 4; ++k) {
+                                float y[NE], r[NE];
+    #pragma unroll
+                                for (int j = 0; j < NE / 2; ++j) {
+                                    const uint32_t yw = word(rv[k].u, h * (NE / 2) + j);
+                                    y[2 * j] = H16<TY>::lo(yw); y[2 * j + 1] = H16<TY>::hi(yw);
+                                }
+                                const float4 d4 = make_float4(H16<T>::lo(rd[k].x), H16<T>::hi(rd[k].x), H16<T>::lo(rd[k].y), H16<T>::hi(rd[k].y));
+                                stem_c4_bwd_apply<NE>(y, d4, w0, w1, w2, w3, s3, h3, s3, kB, kC, r);
+    #pragma unroll
+                                for (int j = 0; j < NE / 2; ++j) {
+                                    o[k][h * (NE / 2) + j] = pack2_bf16(r[2 * j], r[2 * j + 1]);
+                                    // the result exists HERE: otherwise hipcc sinks rows 1-3 of every group into the conditional store blocks
+                                    // below, all groups' constants stay live across them and the prefetched chunks go to scratch
+                                    asm volatile("" : "+v"(o[k][h * (NE / 2) + j]));
+                                }
+                            }
+                        }
+                    }
+                    // LDS tile + the one HBM copy for the data-gradient launch.  Only in-image pixels are stored: for them the clamped
+                    // coordinates of issue_loads are the pixel's own, so each thread overwrites exactly what it loaded (dy_out may be dz)
+                    char* oimg = (char*)a.dy_out + (long)tc.b * F * (long)Tn * 128;
+                    const unsigned yrow = (unsigned)Tn * 128u, vy = (unsigned)(ty * 64 + cch * 8) * 2u;
+    #pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const int f = tc.f0 + pr + 2 * k;
+                        const bool ok = f < F && ty < Tn;
+                        const uint4 u = ok ? make_uint4(o[k][0], o[k][1], o[k][2], o[k][3]) : make_uint4(0, 0, 0, 0);
+                        *(uint4*)&sY[lbY + k * (2 * WTC * 64)] = u;
+                        if (ok) *(uint4*)(oimg + (unsigned)f * yrow + vy) = u;
+                    }
                 }
             }
         };
         auto write_tile = [&](const TileCoord tc, uint16_t* __restrict__ sX, uint16_t* __restrict__ sY) __attribute__((always_inline)) {
+            if constexpr (DYSRC != DY_LOAD) {                      // the z prologue's constants: live for the halo pieces only
+                if constexpr (C1IN) kc1 = *(const C1Const*)&sK[KZ + cch * 40];
+                else {
+    #pragma unroll
+                    for (int e = 0; e < 8; ++e) { sc[e] = sK[KZ + cch * 8 + e]; sh[e] = sK[KZ + 64 + cch * 8 + e]; }
+                }
+            }
             write_piece(0, tc, sX, sY); write_piece(1, tc, sX, sY); write_piece(2, tc, sX, sY);
         };
 
         TileCoord tc = coord(tile < ntiles ? tile : 0);
-        if (tile < ntiles) { issue_loads(tc); write_tile(tc, sXb[0], sYb[0]); }
+        if (tile < ntiles) issue_loads(tc);
+        if constexpr (DYSRC != DY_LOAD) {
+            constexpr int RO = DYSRC == DY_C4 ? 256 : 0;           // offset of s1 | s2 in red
+            if (blockIdx.x == 0 && a.pg_gamma) {                   // parameter gradients from the finished sums, added once per launch
+                if (DYSRC == DY_C4 && tid < 256) a.pg_w4[tid] += (float)a.red[tid];
+                if (tid < 64) { a.pg_beta[tid] += (float)a.red[RO + tid]; a.pg_gamma[tid] += (float)a.red[RO + 64 + tid]; }
+            }
+            if (tid < 64) {                                        // one channel per thread, the streaming kernels' own setup arithmetic
+                const float invN = 1.0f / (float)((long)a.nb * F * Tn);
+                const float s_ = a.aff[tid], h_ = a.aff[64 + tid], mu = a.aff[128 + tid], rs = a.aff[192 + tid];
+                const float m1 = a.use_stats ? (float)a.red[RO + tid] * invN : 0.f, m2 = a.use_stats ? (float)a.red[RO + 64 + tid] * invN : 0.f;
+                float A, B, C;
+                bn_bwd_abc(s_, mu, rs, m1, m2, A, B, C);
+                if constexpr (DYSRC == DY_APPLY) {
+                    bool neg;
+                    const float t = bn_relu_thr(s_, h_, neg);
+                    sK[tid] = A; sK[64 + tid] = B; sK[128 + tid] = C; sK[192 + tid] = t; sK[256 + tid] = __uint_as_float(neg ? 1u : 0u);
+                } else {
+    #pragma unroll
+                    for (int c = 0; c < 4; ++c) sK[c * 64 + tid] = a.W4[c * 64 + tid];
+                    sK[256 + tid] = s_; sK[320 + tid] = h_; sK[384 + tid] = B; sK[448 + tid] = C;
+                }
+                if constexpr (C1IN) {
+                    if (tid < 8) { C1Const k; c1_setup(k, a.c1_w, a.scale, a.shift, tid * 8); *(C1Const*)&sK[KZ + tid * 40] = k; }
+                } else { sK[KZ + tid] = a.prologue ? a.scale[tid] : 1.f; sK[KZ + 64 + tid] = a.prologue ? a.shift[tid] : 0.f; }
+            }
+            __syncthreads();                                       // (all 16 waves: the MFMA waves have the matching barrier)
+        }
+        if (tile < ntiles) write_tile(tc, sXb[0], sYb[0]);
         int next = (1 < nrounds) ? xcd_tile(1, blockIdx.x, gridDim.x) : ntiles;
         TileCoord tcn = coord(next < ntiles ? next : 0);
         if (next < ntiles) issue_loads(tcn);
@@ -1261,6 +1406,7 @@ __global__ __launch_bounds__(1024) void conv3x3_wgrad_ws_kernel(WgradArgs a) {
             }
         }
     }
+    if constexpr (DYSRC != DY_LOAD) __syncthreads();     // the staging waves' constant table
     __syncthreads();
     int cur = 0;
     for (int it = 0; it < nrounds; ++it) {
@@ -1612,5 +1758,56 @@ extern "C" int sarssl_conv3x3_wgrad_c1_acc(const void* dy, const void* a0, const
     wgrad_bf16_launch<true>(a, g2, st, a0_dtype == SARSSL_F16);
     wgrad_reduce_kernel<<<W_ELEMS / 64, 256, 0, st>>>(partial, g2, nullptr, 0, grad_oihw);
     SARSSL_CHECK_LAUNCH("conv3x3_wgrad_ws_kernel<c1in>");
+    return 0;
+}
+
+// The two weight gradients of the stem with the BatchNorm backward of their dy operand formed by the staging waves (conv3x3_wgrad_ws_kernel,
+// DYSRC): the streaming pass that wrote dy, and this launch's read of it, are gone; dy is stored once (dy_out) for the data-gradient launch
+// that follows.  y_dtype: encoding of the saved forward tensors (SARSSL_BF16 or SARSSL_F16, the same for both); gradients are bf16.
+// dgamma / dbeta (/ gW4): f32 parameter-gradient buffers that receive the finished sums (all or none), as in the passes these replace.
+//
+// Second 3x3 convolution: dy3 = stem_c4_bwd_apply(y3, dy4, W4, aff3, red f64[384], use_stats) -> dy3_out, and
+// grad_oihw += wgrad(dy3, relu(scale * y2 + shift)).
+extern "C" int sarssl_conv3x3_wgrad_c4_acc(const void* y3, const void* dy4, const float* W4, const float* aff3, const double* red, int use_stats,
+                                           const void* y2, const float* scale, const float* shift, int nb, int F, int T, void* dy3_out,
+                                           float* grad_oihw, float* partial, float* gW4, float* dgamma, float* dbeta, int y_dtype, void* stream) {
+    SARSSL_REQUIRE(nb > 0 && F > 0 && T > 0 && y3 && dy4 && W4 && aff3 && red && y2 && dy3_out && grad_oihw && partial &&
+                   (y_dtype == SARSSL_BF16 || y_dtype == SARSSL_F16), "sarssl_conv3x3_wgrad_c4_acc");
+    SARSSL_REQUIRE((scale == nullptr) == (shift == nullptr), "sarssl_conv3x3_wgrad_c4_acc");
+    SARSSL_REQUIRE((gW4 == nullptr) == (dgamma == nullptr) && (gW4 == nullptr) == (dbeta == nullptr), "sarssl_conv3x3_wgrad_c4_acc");
+    SARSSL_REQUIRE(dy3_out != y3 && dy3_out != y2, "sarssl_conv3x3_wgrad_c4_acc");
+    WgradArgs a = {};
+    a.zin = y2; a.scale = scale; a.shift = shift; a.prologue = (scale != nullptr);
+    a.partial = partial; a.nb = nb; a.F = F; a.T = T;
+    a.y = y3; a.dy4 = dy4; a.W4 = W4; a.aff = aff3; a.red = red; a.use_stats = use_stats; a.dy_out = dy3_out;
+    a.pg_w4 = gW4; a.pg_gamma = dgamma; a.pg_beta = dbeta;
+    hipStream_t st = (hipStream_t)stream;
+    const int g2 = wgrad_db_grid(nb, F, T);
+    if (y_dtype == SARSSL_F16) conv3x3_wgrad_ws_kernel<false, f16, DY_C4, f16><<<g2, 1024, 0, st>>>(a);
+    else conv3x3_wgrad_ws_kernel<false, bf16, DY_C4, bf16><<<g2, 1024, 0, st>>>(a);
+    wgrad_reduce_kernel<<<W_ELEMS / 64, 256, 0, st>>>(partial, g2, nullptr, 0, grad_oihw);
+    SARSSL_CHECK_LAUNCH("conv3x3_wgrad_ws_kernel<c4>");
+    return 0;
+}
+// First 3x3 convolution: dy2 = bn_bwd_apply_relu(dz, y, aff, red f64[128], use_stats) -> dy_out (may be dz itself), and
+// grad_oihw += wgrad(dy2, relu(scale * (W1 a0) + shift)) with the input operand formed from a0 (sarssl_conv3x3_wgrad_c1_acc).
+extern "C" int sarssl_conv3x3_wgrad_c1_apply_acc(const void* dz, const void* y, const float* aff, const double* red, int use_stats, void* dy_out,
+                                                 const void* a0, const float* W1, const float* scale, const float* shift, int nb, int F, int T,
+                                                 float* grad_oihw, float* partial, float* dgamma, float* dbeta, int y_dtype, void* stream) {
+    SARSSL_REQUIRE(nb > 0 && F > 0 && T > 0 && dz && y && aff && red && dy_out && a0 && W1 && scale && shift && grad_oihw && partial &&
+                   (y_dtype == SARSSL_BF16 || y_dtype == SARSSL_F16), "sarssl_conv3x3_wgrad_c1_apply_acc");
+    SARSSL_REQUIRE((dgamma == nullptr) == (dbeta == nullptr), "sarssl_conv3x3_wgrad_c1_apply_acc");
+    SARSSL_REQUIRE(dy_out != y && dy_out != a0, "sarssl_conv3x3_wgrad_c1_apply_acc");
+    WgradArgs a = {};
+    a.dy = dz; a.zin = a0; a.scale = scale; a.shift = shift; a.prologue = 1; a.c1_w = W1;
+    a.partial = partial; a.nb = nb; a.F = F; a.T = T;
+    a.y = y; a.aff = aff; a.red = red; a.use_stats = use_stats; a.dy_out = dy_out;
+    a.pg_gamma = dgamma; a.pg_beta = dbeta;
+    hipStream_t st = (hipStream_t)stream;
+    const int g2 = wgrad_db_grid(nb, F, T);
+    if (y_dtype == SARSSL_F16) conv3x3_wgrad_ws_kernel<true, f16, DY_APPLY, f16><<<g2, 1024, 0, st>>>(a);
+    else conv3x3_wgrad_ws_kernel<true, bf16, DY_APPLY, bf16><<<g2, 1024, 0, st>>>(a);
+    wgrad_reduce_kernel<<<W_ELEMS / 64, 256, 0, st>>>(partial, g2, nullptr, 0, grad_oihw);
+    SARSSL_CHECK_LAUNCH("conv3x3_wgrad_ws_kernel<c1in, apply>");
     return 0;
 }

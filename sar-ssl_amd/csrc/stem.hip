@@ -511,7 +511,7 @@ __global__ __launch_bounds__(256) void stem_c4_bwd_kernel(const TA* __restrict__
         for (int e = 0; e < 8; ++e) {
             const int ci = cg * 8 + e;
             const float m1 = use_stats ? (float)red[256 + ci] * invN : 0.f, m2 = use_stats ? (float)red[320 + ci] * invN : 0.f;
-            cA[e] = sc[e]; cB[e] = -sc[e] * m2 * rs[e]; cC[e] = -sc[e] * m1 - cB[e] * mu[e];
+            bn_bwd_abc(sc[e], mu[e], rs[e], m1, m2, cA[e], cB[e], cC[e]);
         }
     }
     // Pixel order.  y3 / g3 are (B,F,T,64) - frames contiguous - while dy4 is (B,T,F,4) - bins contiguous: walking pixels in y3's
@@ -556,13 +556,13 @@ __global__ __launch_bounds__(256) void stem_c4_bwd_kernel(const TA* __restrict__
             const float4 d = sD[pl & 15][pl >> 4];
             const f8 vv = raw8_unpack(v[u]);
             f8 o;
+            if (MODE == 2) stem_c4_bwd_apply<8>(vv.v, d, w[0], w[1], w[2], w[3], sc, sh, cA, cB, cC, o.v);
+            else {
 #pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const float uu = fmaf(vv.v[e], sc[e], sh[e]);
-                float gi = d.x * w[0][e] + d.y * w[1][e] + d.z * w[2][e] + d.w * w[3][e];
-                gi = (uu > 0.f) ? gi : 0.f;
-                if (MODE == 2) o.v[e] = fmaf(cA[e], gi, fmaf(cB[e], vv.v[e], cC[e]));
-                else {
+                for (int e = 0; e < 8; ++e) {
+                    const float uu = fmaf(vv.v[e], sc[e], sh[e]);
+                    float gi = d.x * w[0][e] + d.y * w[1][e] + d.z * w[2][e] + d.w * w[3][e];
+                    gi = (uu > 0.f) ? gi : 0.f;
                     const float z = fmaxf(uu, 0.f);
                     o.v[e] = gi;
                     acc[0 * 8 + e] += d.x * z; acc[1 * 8 + e] += d.y * z; acc[2 * 8 + e] += d.z * z; acc[3 * 8 + e] += d.w * z;
@@ -1002,13 +1002,11 @@ __global__ void cl_bn_bwd_apply_kernel(const T* __restrict__ dz, const TA* __res
         unsigned sgn = 0u;
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-            A[e] = sc[e];
-            Bc[e] = -sc[e] * m2[e] * rs[e];
-            Cc[e] = -sc[e] * m1[e] - Bc[e] * mu[e];
-            float t = sc[e] != 0.f ? -sh[e] / sc[e] : (sh[e] > 0.f ? -INFINITY : INFINITY);
-            if (g_is_masked) t = -INFINITY;
-            else if (sc[e] < 0.f) { t = -t; sgn |= 1u << e; }
-            thr[e] = t;
+            bn_bwd_abc(sc[e], mu[e], rs[e], m1[e], m2[e], A[e], Bc[e], Cc[e]);
+            bool neg;
+            const float t = bn_relu_thr(sc[e], sh[e], neg);
+            thr[e] = g_is_masked ? -INFINITY : t;
+            if (!g_is_masked && neg) sgn |= 1u << e;
         }
         const long stride = (long)gridDim.x * rpb;
         long n = (long)blockIdx.x * rpb + rslot;
@@ -1016,14 +1014,8 @@ __global__ void cl_bn_bwd_apply_kernel(const T* __restrict__ dz, const TA* __res
             const f8 d0 = ld8(dz + n * L + col), v0 = ld8(y + n * L + col);
             const f8 d1 = ld8(dz + (n + stride) * L + col), v1 = ld8(y + (n + stride) * L + col);
             f8 o0, o1;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const unsigned sb = ((sgn >> e) & 1u) << 31;
-                const float g0 = __uint_as_float(__float_as_uint(v0.v[e]) ^ sb) > thr[e] ? d0.v[e] : 0.f;
-                const float g1 = __uint_as_float(__float_as_uint(v1.v[e]) ^ sb) > thr[e] ? d1.v[e] : 0.f;
-                o0.v[e] = fmaf(A[e], g0, fmaf(Bc[e], v0.v[e], Cc[e]));
-                o1.v[e] = fmaf(A[e], g1, fmaf(Bc[e], v1.v[e], Cc[e]));
-            }
+            bn_bwd_apply_relu<8>(d0.v, v0.v, A, Bc, Cc, thr, sgn, o0.v);
+            bn_bwd_apply_relu<8>(d1.v, v1.v, A, Bc, Cc, thr, sgn, o1.v);
             st8(dy + n * L + col, o0);
             st8(dy + (n + stride) * L + col, o1);
         }
@@ -1031,12 +1023,7 @@ __global__ void cl_bn_bwd_apply_kernel(const T* __restrict__ dz, const TA* __res
             const f8 d = ld8(dz + n * L + col);
             const f8 v = ld8(y + n * L + col);
             f8 o;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const float ys = __uint_as_float(__float_as_uint(v.v[e]) ^ (((sgn >> e) & 1u) << 31));
-                const float g = ys > thr[e] ? d.v[e] : 0.f;
-                o.v[e] = fmaf(A[e], g, fmaf(Bc[e], v.v[e], Cc[e]));
-            }
+            bn_bwd_apply_relu<8>(d.v, v.v, A, Bc, Cc, thr, sgn, o.v);
             st8(dy + n * L + col, o);
         }
         return;

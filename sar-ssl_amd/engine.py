@@ -39,6 +39,10 @@ def mm_nn(dy, W, **kw):
 # companion-stream schedules for these products - per product and per block; neither beat keeping them on the chain, and a stream
 # forked off a forked stream crashes hipStreamEndCapture on ROCm 7.2 (tools/capture_nested_fork_repro.py).  Removed in round 3.)
 _STEM_LAST_ALL_CUS = True     # gradient convolutions of the stem that runs last (spat) on every CU (model.py)
+# Stem backward, 16-bit training path: the BatchNorm backward in front of each 3x3 weight gradient is formed by that launch's staging
+# waves (hip.conv3x3_wgrad_c4 / conv3x3_wgrad_c1_apply) instead of a streaming pass of its own; same bits either way (tests/test_gpu_wgrad_dysrc.py)
+_WGRAD_FUSE_C4 = True         # second 3x3 convolution: dy3 from (y3, dy4) - replaces the second phase of stem_c4_bwd_two_phase
+_WGRAD_FUSE_APPLY = True      # first 3x3 convolution: dy2 from (dz2, y2), written over dz2 - replaces cl_bn_bwd_apply
 _WGRAD_SPLIT_BIG = 4          # K-slices of a grouped launch with >= .._TILES output tiles
 _WGRAD_SPLIT_BIG_TILES = 128
 _wg_blocks = []              # stack of pending-product lists (wgrad_block)
@@ -387,7 +391,8 @@ def knobs():
             "SARSSL_FFN2_FWD": sorted(_FFN2_WIDTHS), "SARSSL_FFN2_BWD": sorted(_FFN2_WIDTHS), "SARSSL_FFN2_LN": 1, "SARSSL_HYBRID_ALO": sorted(_H_ALO),
             "SARSSL_LIN256": 0, "SARSSL_DEC_MASKED": int(_DEC_MASKED), "SARSSL_TAIL_MASKED": int(_TAIL_MASKED), "SARSSL_PREP_ASYNC": 1,
             "SARSSL_WGRAD_SPLIT_BIG": [_WGRAD_SPLIT_BIG, _WGRAD_SPLIT_BIG_TILES], "SARSSL_TWO_STREAMS": os.environ.get("SARSSL_TWO_STREAMS", "1"),
-            "SARSSL_STEM_LAST_ALL_CUS": int(_STEM_LAST_ALL_CUS), "SARSSL_WGRAD_WS": "1", "SARSSL_CONV_WS": "4",
+            "SARSSL_STEM_LAST_ALL_CUS": int(_STEM_LAST_ALL_CUS), "SARSSL_WGRAD_FUSE_C4": int(_WGRAD_FUSE_C4),
+            "SARSSL_WGRAD_FUSE_APPLY": int(_WGRAD_FUSE_APPLY), "SARSSL_WGRAD_WS": "1", "SARSSL_CONV_WS": "4",
             "SARSSL_CONV_CUS_FWD": "default(256)", "SARSSL_CONV_CUS_BWD": "default(224)",
             "SARSSL_GRAPH": os.environ.get("SARSSL_GRAPH", "default"),
             "precision": runtime.get_precision()}
@@ -421,13 +426,20 @@ def stem_bwd(dz4, pe, saved):
     red4 = hip.cl_bn_bwd_reduce(dz4, y4, 4, aff4, RELU)
     # (BatchNorm / 1x1-conv parameter gradients are added from the finished sums by workgroup 0 of the pass that consumes them)
     dy4 = hip.cl_bn_bwd_apply(dz4, y4, 4, aff4, RELU, False, train, red4, pgrads=(gbuf(pe[10].weight), gbuf(pe[10].bias)))
-    # 64->4 conv + BN3/ReLU backward: sums pass + direct dy3 pass over y3 (1.7 GB per encoder)
-    dy3, red = hip.stem_c4_bwd_two_phase(y3, dy4, pe[9].weight.data.view(4, 64), aff3, train,
-                                         pgrads=(gbuf(pe[9].weight), gbuf(pe[7].weight), gbuf(pe[7].bias)))
-    # second 3x3 conv
-    dW = hip.conv3x3_wgrad(dy3, y2, aff2[0], aff2[1], precise=RT.precise, acc_into=gbuf(pe[6].weight))
-    if dW is not None:
-        gbuf(pe[6].weight).add_(dW.view(3, 3, 64, 64).permute(2, 3, 0, 1))
+    fused = RT.dtype in _16 and y1 is None       # the 16-bit training path (stem_fwd): every other case keeps the streaming passes
+    W4, pg3 = pe[9].weight.data.view(4, 64), (gbuf(pe[9].weight), gbuf(pe[7].weight), gbuf(pe[7].bias))
+    if fused and _WGRAD_FUSE_C4:
+        # 64->4 conv + BN3/ReLU backward: sums pass over y3; dy3 is formed from (y3, dy4) by the staging waves of the second 3x3
+        # convolution's weight gradient, which stores it once for the data gradient
+        red = hip.stem_c4_bwd_sums(y3, dy4, W4, aff3)
+        dy3 = hip.conv3x3_wgrad_c4(y3, dy4, W4, aff3, train, red, y2, aff2[0], aff2[1], gbuf(pe[6].weight), pgrads=pg3)
+    else:
+        # 64->4 conv + BN3/ReLU backward: sums pass + direct dy3 pass over y3 (1.7 GB per encoder)
+        dy3, red = hip.stem_c4_bwd_two_phase(y3, dy4, W4, aff3, train, pgrads=pg3)
+        # second 3x3 conv
+        dW = hip.conv3x3_wgrad(dy3, y2, aff2[0], aff2[1], precise=RT.precise, acc_into=gbuf(pe[6].weight))
+        if dW is not None:
+            gbuf(pe[6].weight).add_(dW.view(3, 3, 64, 64).permute(2, 3, 0, 1))
     red2 = None
     if RT.dtype in _16:              # BatchNorm-backward sums accumulated in the data-gradient kernel's epilogue
         dz2, red2 = hip.conv3x3_dgrad_bnred(dy3, _taps(pe[6])[1], y2, aff2)
@@ -435,9 +447,14 @@ def stem_bwd(dz4, pe, saved):
         dz2 = hip.conv3x3_fwd(dy3, _taps(pe[6])[1], precise=RT.precise)
         red2 = hip.cl_bn_bwd_reduce(dz2, y2, 64, aff2, RELU)
     # first 3x3 conv
-    dy2 = hip.cl_bn_bwd_apply(dz2, y2, 64, aff2, RELU, False, train, red2, out=dz2, pgrads=(gbuf(pe[4].weight), gbuf(pe[4].bias)))
+    pg2 = (gbuf(pe[4].weight), gbuf(pe[4].bias))
+    if fused and _WGRAD_FUSE_APPLY:    # dy2 formed from (dz2, y2) by the weight gradient's staging waves, written over dz2
+        dy2 = hip.conv3x3_wgrad_c1_apply(dz2, y2, aff2, train, red2, a0, W1, aff1[0], aff1[1], gbuf(pe[3].weight), out=dz2, pgrads=pg2)
+    else:
+        dy2 = hip.cl_bn_bwd_apply(dz2, y2, 64, aff2, RELU, False, train, red2, out=dz2, pgrads=pg2)
     if y1 is None:                     # first layer never stored (stem_fwd): its operand is formed from a0 while staging
-        hip.conv3x3_wgrad_c1(dy2, a0, W1, aff1[0], aff1[1], gbuf(pe[3].weight))
+        if not (fused and _WGRAD_FUSE_APPLY):
+            hip.conv3x3_wgrad_c1(dy2, a0, W1, aff1[0], aff1[1], gbuf(pe[3].weight))
         if hip.conv3x3_dgrad_c1red(dy2, _taps(pe[3])[1], a0, W1, aff1, mom1, train, gbuf(pe[0].weight),
                                      gbuf(pe[1].weight), gbuf(pe[1].bias)):
             return None     # the data gradient of the first 3x3 convolution was consumed in its epilogue: the first layer is done

@@ -895,14 +895,21 @@ def stem_c4_bwd(y3, dy4, W4, aff):
     return g3, red
 
 
+def stem_c4_bwd_sums(y3, dy4, W4, aff):
+    """First phase of the 64->4 backward -> red f64[384] = [dW4 | s1 | s2] (nothing stored)."""
+    B, F, T, _ = y3.shape
+    red = _sums(384, y3.device)
+    _lib.call("sarssl_stem_c4_bwd_sums", _p(y3), _p(dy4), _p(W4), _p(aff[0]), _p(aff[1]), _p(aff[2]), _p(aff[3]), c_int(B), c_int(F),
+              c_int(T), _p(red), c_int(dt_ga(dy4, y3)), _stream())
+    return red
+
+
 def stem_c4_bwd_two_phase(y3, dy4, W4, aff, train, pgrads=None):
     """-> dy3 (B,F,T,64) = gradient w.r.t. the third BatchNorm's input, red f64[384] = [dW4 | s1 | s2]; two kernels, no
     intermediate 64-channel tensor.  pgrads = (gW4 (4,64), dgamma, dbeta) f32 gradient buffers: accumulated from red by the second
     kernel."""
     B, F, T, _ = y3.shape
-    red = _sums(384, y3.device)
-    _lib.call("sarssl_stem_c4_bwd_sums", _p(y3), _p(dy4), _p(W4), _p(aff[0]), _p(aff[1]), _p(aff[2]), _p(aff[3]), c_int(B), c_int(F),
-              c_int(T), _p(red), c_int(dt_ga(dy4, y3)), _stream())
+    red = stem_c4_bwd_sums(y3, dy4, W4, aff)
     dy3 = torch.empty(y3.shape, dtype=dy4.dtype, device=y3.device)
     gw, dg, db = pgrads if pgrads is not None else (None, None, None)
     _lib.call("sarssl_stem_c4_bwd_apply_pg", _p(y3), _p(dy4), _p(W4), _p(aff[0]), _p(aff[1]), _p(aff[2]), _p(aff[3]), c_int(B), c_int(F),
@@ -1038,6 +1045,52 @@ def conv3x3_wgrad_c1(dy, a0, W1, scale, shift, acc_into):
         _lib.call("sarssl_conv3x3_wgrad_c1_acc", _p(dy), _p(a0), _p(W1), c_int(B), c_int(F), c_int(T), _p(scale), _p(shift), _p(acc_into),
                   _p(part), c_int(dt(a0)), _stream())
     return True
+
+
+def _wgrad_part(B, F, T, device):
+    nbytes = _lib.lib().sarssl_conv3x3_wgrad_workspace_bytes
+    nbytes.restype = c_long
+    return workspace(nbytes(c_int(B), c_int(F), c_int(T)), device, "wgrad_part")
+
+
+def conv3x3_wgrad_c4(y3, dy4, W4, aff3, train, red, y2, scale, shift, acc_into, out=None, pgrads=None):
+    """Second 3x3 convolution's weight gradient with its dy operand formed while staging: dy3 = the second phase of
+    stem_c4_bwd_two_phase (from y3, dy4 (B,T,F,4), W4, aff3 and the finished sums ``red`` f64[384]) -> ``out`` / a new (B,F,T,64) bf16 for the
+    data gradient; acc_into (64,64,3,3) f32 += wgrad(dy3, relu(scale * y2 + shift)).  pgrads = (gW4, dgamma, dbeta) as there."""
+    _need_cuda(y3, dy4, W4, aff3, red, y2)
+    B, F, T, C = y3.shape
+    assert C == 64 and y3.dtype in _16 and y2.dtype == y3.dtype and y2.shape == y3.shape and dy4.dtype == torch.bfloat16
+    assert dy4.shape == (B, T, F, 4) and dy4.is_contiguous() and y3.is_contiguous() and y2.is_contiguous() and W4.is_contiguous()
+    assert aff3.dtype == torch.float32 and aff3.is_contiguous() and aff3.numel() == 256 and red.numel() == 384
+    assert acc_into.shape == (64, 64, 3, 3) and acc_into.dtype == torch.float32 and acc_into.is_contiguous()
+    dy3 = out if out is not None else torch.empty(y3.shape, dtype=torch.bfloat16, device=y3.device)
+    assert dy3.dtype == torch.bfloat16 and dy3.shape == y3.shape and dy3.is_contiguous()
+    gw, dg, db = pgrads if pgrads is not None else (None, None, None)
+    with _Timed("conv3x3_wgrad_kernel"):
+        _lib.call("sarssl_conv3x3_wgrad_c4_acc", _p(y3), _p(dy4), _p(W4), _p(aff3), _p(red), c_int(1 if train else 0), _p(y2), _p(scale),
+                  _p(shift), c_int(B), c_int(F), c_int(T), _p(dy3), _p(acc_into), _p(_wgrad_part(B, F, T, y3.device)), _p(gw), _p(dg), _p(db),
+                  c_int(dt(y3)), _stream())
+    return dy3
+
+
+def conv3x3_wgrad_c1_apply(dz, y, aff, train, red, a0, W1, scale, shift, acc_into, out=None, pgrads=None):
+    """First 3x3 convolution's weight gradient (conv3x3_wgrad_c1) with its dy operand formed while staging: dy = cl_bn_bwd_apply's ReLU
+    path on (dz, y, aff, red f64[128]) -> ``out`` (default: a new tensor; may be dz itself), returned.  pgrads = (dgamma, dbeta)."""
+    _need_cuda(dz, y, aff, red, a0, W1)
+    B, F, T, _ = a0.shape
+    assert a0.dtype in _16 and y.dtype == a0.dtype and dz.dtype == torch.bfloat16 and y.shape == (B, F, T, 64) and dz.shape == y.shape
+    assert dz.is_contiguous() and y.is_contiguous() and a0.is_contiguous() and W1.is_contiguous()
+    assert aff.dtype == torch.float32 and aff.is_contiguous() and aff.numel() == 256 and red.numel() == 128
+    assert acc_into.shape == (64, 64, 3, 3) and acc_into.dtype == torch.float32 and acc_into.is_contiguous()
+    if out is None:
+        out = torch.empty_like(dz)
+    assert out.dtype == torch.bfloat16 and out.shape == dz.shape and out.is_contiguous()
+    dg, db = pgrads if pgrads is not None else (None, None)
+    with _Timed("conv3x3_wgrad_kernel"):
+        _lib.call("sarssl_conv3x3_wgrad_c1_apply_acc", _p(dz), _p(y), _p(aff), _p(red), c_int(1 if train else 0), _p(out), _p(a0), _p(W1),
+                  _p(scale), _p(shift), c_int(B), c_int(F), c_int(T), _p(acc_into), _p(_wgrad_part(B, F, T, a0.device)), _p(dg), _p(db),
+                  c_int(dt(y)), _stream())
+    return out
 
 
 def conv3x3_dgrad_bnred(dy, w_tap_dgrad, y, aff):
