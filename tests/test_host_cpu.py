@@ -31,6 +31,221 @@ def test_cabi_library_exports_every_declared_symbol():
         assert lib.sarssl_comm_rccl_version() > 20000
 
 
+_C_SCALARS = ("int", "long", "float", "double", "unsigned long long", "unsigned int")
+
+
+def _c_kind(text, named, stmt):
+    """'ptr' or the scalar's C type of one parameter (``named``: drop the parameter's name) or of the return type."""
+    if "*" in text:
+        return "ptr"
+    words = [w for w in text.split() if w != "const"]
+    k = " ".join(words[:-1] if named else words)
+    assert k in _C_SCALARS, "unknown type `%s` in: %s" % (text, stmt)
+    return k
+
+
+def _header_prototypes(text=None):
+    """{entry point: (return kind, [parameter kinds])} read from include/sarssl_hip.h (or ``text``)."""
+    hdr = open(os.path.join(ROOT, "include", "sarssl_hip.h")).read() if text is None else text
+    src = re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
+    src = re.sub(r"^\s*#.*$", " ", src, flags=re.M).replace('extern "C" {', " ")
+    protos = {}
+    for stmt in src.split(";"):
+        stmt = " ".join(stmt.split()).strip("} ")
+        if "sarssl_" not in stmt or stmt.startswith("typedef "):
+            continue
+        m = re.match(r"^([\w\s*]+?)\s*\b(sarssl_\w+)\s*\(([^()]*)\)$", stmt)
+        assert m is not None, "unreadable declaration: " + stmt
+        params = [a.strip() for a in m.group(3).split(",")] if m.group(3).strip() not in ("", "void") else []
+        protos[m.group(2)] = (_c_kind(m.group(1), False, stmt), [_c_kind(a, True, stmt) for a in params])
+    return protos
+
+
+_WRAPPER_KIND = {"c_int": "int", "c_long": "long", "c_float": "float", "c_ulonglong": "unsigned long long", "c_double": "double",
+                 "c_void_p": "ptr", "c_char_p": "ptr", "_p": "ptr", "_stream": "ptr", "byref": "ptr", "data_as": "ptr",
+                 "create_string_buffer": "ptr"}
+
+
+def _wrapper_kind(node):
+    """Kind a call-site argument is wrapped as (None where the expression does not say: a name, an array constructor)."""
+    import ast
+    if isinstance(node, ast.IfExp):
+        kinds = {_wrapper_kind(node.body), _wrapper_kind(node.orelse)} - {None}
+        return kinds.pop() if len(kinds) == 1 else "mixed" if kinds else None
+    if isinstance(node, ast.Call):
+        fn = node.func.id if isinstance(node.func, ast.Name) else node.func.attr if isinstance(node.func, ast.Attribute) else None
+        return _WRAPPER_KIND.get(fn)
+    return None
+
+
+def _abi_sites(source, path="<source>"):
+    """Every way into the library in one Python file -> (sites, restypes).
+    sites: (entry point, line, argument nodes, scope, direct, certain) of
+      * ``<x>.call("sarssl_name", ...)`` with a literal name (direct False: _lib.call sets nothing on the function and checks the status),
+      * ``<x>.sarssl_name(...)`` - the attribute-style call on the CDLL -, and
+      * ``fn(...)`` where the enclosing function (or the module) holds ``fn = <x>.sarssl_name``;
+      calls with a starred argument are left out; certain False: the receiver is not recognisably the library (an oracle function of
+      the same prefix), the site counts only if the header knows the name.  restypes: (entry point, line, name of the assigned ctypes type, scope) of every
+      ``<x>.sarssl_name.restype = T`` / ``fn.restype = T``.  scope: line of the enclosing def, 0 for the module."""
+    import ast
+    tree = ast.parse(source, path)
+    sites, restypes, done = [], [], set()
+
+    def entry(node, alias):
+        if isinstance(node, ast.Attribute) and node.attr.startswith("sarssl_"):
+            return node.attr
+        return alias.get(node.id) if isinstance(node, ast.Name) else None
+
+    def on_library(node):          # lib().x, _lib.lib().x, lib.x, L.x, _lib.x or a local alias: certainly the CDLL, so x must be declared
+        r = node.value if isinstance(node, ast.Attribute) else None
+        if isinstance(r, ast.Call):
+            r = r.func
+        return r is None or (r.attr if isinstance(r, ast.Attribute) else getattr(r, "id", None)) in ("lib", "_lib", "L")
+
+    scopes = [tree] + [n for n in ast.walk(tree) if isinstance(n, (ast.FunctionDef, ast.AsyncFunctionDef, ast.Lambda))]
+    for scope in sorted(scopes, key=lambda n: -getattr(n, "lineno", 0)):            # innermost first: a site belongs to its nearest def
+        sline = getattr(scope, "lineno", 0)
+        nodes = sorted((n for n in ast.walk(scope) if hasattr(n, "lineno")), key=lambda n: (n.lineno, n.col_offset))
+        alias = {}
+        for n in nodes:
+            if isinstance(n, ast.Assign) and len(n.targets) == 1 and isinstance(n.targets[0], ast.Name) and entry(n.value, {}):
+                alias[n.targets[0].id] = n.value.attr
+        for n in nodes:
+            key = (type(n).__name__, n.lineno, n.col_offset)
+            if key in done:
+                continue
+            if isinstance(n, ast.Assign):
+                for t in n.targets:
+                    targets = t.elts if isinstance(t, ast.Tuple) else [t]
+                    values = n.value.elts if isinstance(t, ast.Tuple) and isinstance(n.value, ast.Tuple) else [n.value] * len(targets)
+                    for tt, v in zip(targets, values):
+                        if isinstance(tt, ast.Attribute) and tt.attr == "restype" and entry(tt.value, alias):
+                            ty = v.attr if isinstance(v, ast.Attribute) else v.id if isinstance(v, ast.Name) else None
+                            restypes.append((entry(tt.value, alias), n.lineno, ty, sline))
+                            done.add(key)
+            elif isinstance(n, ast.Call) and not any(isinstance(a, ast.Starred) for a in n.args):
+                if (isinstance(n.func, ast.Attribute) and n.func.attr == "call" and n.args and isinstance(n.args[0], ast.Constant)
+                        and isinstance(n.args[0].value, str) and n.args[0].value.startswith("sarssl_")):
+                    sites.append((n.args[0].value, n.lineno, n.args[1:], sline, False, True))
+                    done.add(key)
+                elif entry(n.func, alias):
+                    sites.append((entry(n.func, alias), n.lineno, n.args, sline, True, on_library(n.func)))
+                    done.add(key)
+    return sorted(sites, key=lambda s: s[1]), sorted(restypes, key=lambda r: r[1])
+
+
+# sarssl_wall_clock_khz returns long, and bench.py / tools/step_stamps.py read it through the untyped default (int): the constant-rate
+# device clock in kHz (1e5 on this part) is far below 2^31, so nothing is cut.  Every other long is a byte count and must be declared.
+_LONG_THAT_FITS_INT = {"sarssl_wall_clock_khz"}
+_RESTYPE_OF = {"long": "c_long", "ptr": ("c_void_p", "c_char_p")}
+
+
+def _check_abi_file(path, source, protos, probe, at_load=()):
+    """Asserts on one file; -> (sites, argument kinds compared, entry points seen).  at_load: names whose restype the loader (_lib.lib())
+    sets on the CDLL every caller shares."""
+    sites, restypes = _abi_sites(source, path)
+    nkinds, seen = 0, set()
+    for name, line, args, scope, direct, certain in sites:
+        where = "%s:%d: %s" % (path, line, name)
+        want = protos[name][1] if name in protos else probe.get(name)
+        if want is None and not certain:
+            continue
+        assert want is not None, where + " is not declared in include/sarssl_hip.h"
+        assert len(args) == len(want), "%s takes %d arguments, %d passed" % (where, len(want), len(args))
+        for i, (arg, k) in enumerate(zip(args, want)):
+            got = _wrapper_kind(arg)
+            if got is not None:
+                assert got == k, "%s: argument %d is wrapped as %s, the header says %s" % (where, i + 1, got, k)
+                nkinds += 1
+        ret = protos[name][0] if name in protos else "int"
+        if direct and ret == "long" and name not in _LONG_THAT_FITS_INT:
+            # a byte count read through the default restype (int) comes back cut to 32 bits: c_long, set in this function before the call
+            assert any(r[0] == name and r[2] == "c_long" and r[3] == scope and r[1] <= line for r in restypes), \
+                where + " returns long: set restype = c_long in front of the call"
+        if direct and ret == "ptr":
+            # handles and strings: declared when the library loads, or in this file
+            assert name in at_load or any(r[0] == name and r[2] in _RESTYPE_OF["ptr"] for r in restypes), \
+                where + " returns a pointer: restype is not set, here or at load"
+        seen.add(name)
+    for name, line, ty, _ in restypes:
+        ret = protos[name][0] if name in protos else "int"
+        assert ty == "c_int" if ret == "int" else ty in _RESTYPE_OF[ret], "%s:%d: %s.restype = %s, the header says %s" % (path, line, name, ty, ret)
+    return sum(1 for s in sites if s[0] in seen), nkinds, seen
+
+
+def test_cabi_call_sites_agree_with_the_header():
+    """The call sites wrap every argument by hand (c_int / c_long / c_float / c_ulonglong / pointers) and ctypes checks none of it: a
+    c_int where the header says long, a dropped or swapped argument, a byte count read without ``restype = c_long`` would show on the GPU
+    only.  This walks both ways into the library - `call("sarssl_...", ...)` with a literal name, and the attribute-style calls on the
+    CDLL (`lib().sarssl_x(...)`, also through a local `fn = lib().sarssl_x`) - in the package, the tools and the drivers, and compares
+    argument count, wrapper kinds and the assigned return types with the header's prototypes (probe-build symbols, which the header does
+    not declare, take one pointer)."""
+    import glob
+    protos = _header_prototypes()
+    hdr = open(os.path.join(ROOT, "include", "sarssl_hip.h")).read()
+    assert sorted(protos) == sorted(set(re.findall(r"\b(sarssl_[a-z0-9_]+)\s*\(", hdr))) and len(protos) >= 150
+    assert {"sarssl_istft_workspace_bytes", "sarssl_wall_clock_khz", "sarssl_conv3x3_wgrad_workspace_bytes", "sarssl_dwglu_wgrad_workspace_bytes",
+            "sarssl_layernorm_bwd_workspace_bytes", "sarssl_dwconv_wgrad_workspace_bytes",
+            "sarssl_step_state_bytes"} <= {n for n, (r, _) in protos.items() if r == "long"}
+    assert {"sarssl_comm_create", "sarssl_create", "sarssl_last_error"} <= {n for n, (r, _) in protos.items() if r == "ptr"}
+    probe = {"sarssl_conv_stamp_buffer": ["ptr"], "sarssl_gemm_stamp_buffer": ["ptr"], "sarssl_ffn_stamp_buffer": ["ptr"]}
+    files = [os.path.join(ROOT, "bench.py"), os.path.join(ROOT, "__graft_entry__.py")]
+    for d in ("sar-ssl_amd", "tools"):
+        files += glob.glob(os.path.join(ROOT, d, "**", "*.py"), recursive=True)
+    loader = os.path.join(ROOT, "sar-ssl_amd", "_lib.py")
+    at_load = {r[0] for r in _abi_sites(open(loader).read())[1]}
+    assert {"sarssl_create", "sarssl_last_error"} <= at_load
+    nsites, nkinds, seen, per_file = 0, 0, set(), {}
+    for path in sorted(files):
+        rel = os.path.relpath(path, ROOT)
+        n, k, names = _check_abi_file(rel, open(path).read(), protos, probe, at_load)
+        per_file[rel] = n
+        nsites, nkinds, seen = nsites + n, nkinds + k, seen | names
+    # the scan really finds the sites: 129 literal call(...) sites and 37 attribute-style ones today, 1528 wrapped arguments
+    assert nsites >= 160 and len(seen) >= 125 and nkinds >= 1450, (nsites, len(seen), nkinds)
+    hip = os.path.join("sar-ssl_amd", "hip.py")
+    direct = [s for s in _abi_sites(open(os.path.join(ROOT, hip)).read())[0] if s[4]]
+    assert len(direct) >= 25 and {"sarssl_gemm_group_tn", "sarssl_layernorm_bwd_workspace_bytes", "sarssl_conv3x3_wgrad_workspace_bytes",
+                                  "sarssl_colsum_slices", "sarssl_comm_create", "sarssl_step_state_skipped"} <= {s[0] for s in direct}
+    assert per_file[os.path.join("sar-ssl_amd", "_lib.py")] >= 5 and per_file["__graft_entry__.py"] >= 1 and per_file["bench.py"] >= 1
+
+
+def test_cabi_call_site_scan_catches_what_it_is_for(tmp_path):
+    """The scan of test_cabi_call_sites_agree_with_the_header on small sources with one mistake each."""
+    import ast
+    protos = _header_prototypes()
+    assert protos["sarssl_glu_fwd"] == ("int", ["ptr", "long", "int", "ptr", "int", "ptr"])
+    assert protos["sarssl_layernorm_bwd_workspace_bytes"] == ("long", ["long", "int"])
+    assert _wrapper_kind(ast.parse("_p(x) if x is not None else c_void_p(0)").body[0].value) == "ptr"
+    assert _wrapper_kind(ast.parse("c_int(1) if x else c_long(0)").body[0].value) == "mixed"
+    ok = ('def f(M, d):\n    fn = _lib.lib().sarssl_layernorm_bwd_workspace_bytes\n    fn.restype = c_long\n'
+          '    n = fn(c_long(M), c_int(d))\n    _lib.call("sarssl_glu_fwd", _p(h), c_long(M), c_int(d), _p(g), c_int(1), _stream())\n'
+          '    return bool(_lib.lib().sarssl_ffn2_supported(c_long(M), c_int(d)))\n')
+    assert _check_abi_file("ok.py", ok, protos, {})[:2] == (3, 10)
+    for old, new, what in (
+            ("c_long(M), c_int(d), _p(g)", "c_int(M), c_int(d), _p(g)", "argument 2 is wrapped as int, the header says long"),
+            ("c_int(d), _p(g), c_int(1)", "c_int(d), _p(g)", "takes 6 arguments, 5 passed"),
+            ("fn(c_long(M), c_int(d))", "fn(c_int(M), c_int(d))", "argument 1 is wrapped as int, the header says long"),
+            ("fn(c_long(M), c_int(d))", "fn(c_long(M))", "takes 2 arguments, 1 passed"),
+            ("    fn.restype = c_long\n", "", "returns long: set restype = c_long"),
+            ("fn.restype = c_long", "fn.restype = c_int", "returns long: set restype = c_long"),
+            ("sarssl_ffn2_supported(c_long(M), c_int(d))", "sarssl_ffn2_supported(c_int(M), c_int(d))", "argument 1 is wrapped as int"),
+            ("sarssl_ffn2_supported(", "sarssl_ffn3_supported(", "is not declared"),
+            ("    return bool", "    c = L.sarssl_comm_create(c_int(n), c_int(r), buf)\n    return bool", "returns a pointer: restype is not set, here or at load")):
+        assert old in ok
+        with pytest.raises(AssertionError, match=re.escape(what)):
+            _check_abi_file("bad.py", ok.replace(old, new), protos, {})
+    # a restype set in another function does not count for a byte count
+    with pytest.raises(AssertionError, match="returns long"):
+        _check_abi_file("bad.py", ok.replace("    fn.restype = c_long\n", "") + "def g():\n    _lib.lib().sarssl_layernorm_bwd_workspace_bytes.restype = c_long\n",
+                        protos, {})
+    # the header reader names what it cannot read
+    for text, what in (("int sarssl_x(int a, size_t n);", "unknown type `size_t n`"), ("void sarssl_x(int a);", "unknown type `void`"),
+                       ("int sarssl_x(int (*cb)(int));", "unreadable declaration")):
+        with pytest.raises(AssertionError, match=re.escape(what)):
+            _header_prototypes("/* c */\n#ifndef H\nint sarssl_ok(const float* p, unsigned long long s);\n" + text + "\n#endif\n")
+
+
 def test_state_dict_layout_matches_reference_manifest():
     from sar_ssl_amd import model
     man = json.load(open(os.path.join(GOLD, "state_dict_manifest.json")))
