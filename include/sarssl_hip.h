@@ -104,6 +104,13 @@ int sarssl_mean_rows_bwd(const float* dy, int B, int Tn, int d, void* dx, int dt
 int sarssl_small_linear_fwd(const float* x, const float* W, const float* bias, int M, int N, int K, int act, float* y, void* stream);
 int sarssl_small_linear_bwd(const float* dy, const float* y, const float* x, const float* W, int M, int N, int K, int act, float* dz_ws, float* dx,
                             float* dW, float* db, void* stream);
+/*      the downstream learner's loss, metric and gradient in one launch (code/learner.py:620-627: F.mse_loss, mean |pred - target|): pred, target
+ *      f32 [B][L]; out f32[2] = (mean squared error, mean absolute error); dpred f32 [B][L] (may be NULL) = 2 (pred - target) / (B L).
+ *      Differences and sums in f64, rounded once; one workgroup, ordered fold, no atomics: run-to-run identical.  out_keep f32[2] (may be
+ *      NULL) receives a copy; acc f64[3] (may be NULL) += (loss, mae, 1) - with skip_nonfinite != 0 only when the loss is finite (a
+ *      training step the guarded optimiser launch skips is not part of the epoch mean; evaluation adds every batch). */
+int sarssl_regress_loss(const float* pred, const float* target, int B, int L, float* out, float* dpred, float* out_keep, double* acc,
+                        int skip_nonfinite, void* stream);
 
 /* ---- "hybrid" numeric mode (round 6): fp16 CNN stem + f32 residual stream in the Conformer blocks / decoder - the mode that meets the
  *      1e-3 per-bin tolerance against the reference's f32 path (code/learner.py:100-103 runs the model in f32 by default) at 16-bit

@@ -3,6 +3,7 @@
 // C-ABI library (round-5 verdict), not speed: one wave per output element / one thread per gradient element, f32 throughout.
 //   mean over frames fwd / bwd                         embed.mean(dim = 1)
 //   small Linear fwd (+ ReLU) / dX / dW, db            nn.Linear(d, n) with n as small as 1 (the MFMA GEMM needs n % 8 == 0)
+//   regression loss + metric + gradient                F.mse_loss / mean |pred - target| of the downstream learner
 #include "common.h"
 #define ST ((hipStream_t)stream)
 
@@ -105,5 +106,43 @@ extern "C" int sarssl_small_linear_bwd(const float* dy, const float* y, const fl
     if (dx) small_linear_dx_kernel<<<(int)(((long)M * K + 255) / 256), 256, 0, ST>>>(dz, W, M, N, K, dx);
     small_linear_dw_kernel<<<(int)(((long)N * K + 255) / 256), 256, 0, ST>>>(dz, x, M, N, K, dW, db);
     SARSSL_CHECK_LAUNCH("small_linear_bwd");
+    return 0;
+}
+
+// Regression loss of the downstream step (code/learner.py:620-627: F.mse_loss, mean |pred - target|) with its gradient, one launch:
+// out = [mean (p - t)^2, mean |p - t|], dpred = 2 (p - t) / n.  Differences and sums in f64, rounded once.  ONE workgroup, strided
+// loop, wave fold + LDS in a fixed order - no atomics: the result is ordered and run-to-run identical (n = B * L is a few hundred at most).
+// out_keep / acc as in loss_finalize_kernel (csrc/elementwise.hip); acc = f64[3]: += loss, += mae, += 1.  skip_nonfinite: a step
+// whose loss is not finite stays out of acc (the guarded optimizer launch skips it too); 0: it is added like any other (evaluation).
+__global__ void __launch_bounds__(256) regress_loss_kernel(const float* __restrict__ pred, const float* __restrict__ target, long n,
+                                                           float* __restrict__ out, float* __restrict__ dpred, float* __restrict__ out_keep,
+                                                           double* __restrict__ acc, int skip_nonfinite) {
+    __shared__ double red[2][4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    double s2 = 0.0, s1 = 0.0;
+    for (long i = threadIdx.x; i < n; i += 256) {
+        const double d = (double)pred[i] - (double)target[i];
+        s2 += d * d;
+        s1 += fabs(d);
+        if (dpred) dpred[i] = (float)(2.0 * d / (double)n);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { s2 += __shfl_xor(s2, o, 64); s1 += __shfl_xor(s1, o, 64); }
+    if (lane == 0) { red[0][wave] = s2; red[1][wave] = s1; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const float l = (float)((((red[0][0] + red[0][1]) + red[0][2]) + red[0][3]) / (double)n);
+        const float m = (float)((((red[1][0] + red[1][1]) + red[1][2]) + red[1][3]) / (double)n);
+        out[0] = l; out[1] = m;
+        if (out_keep) { out_keep[0] = l; out_keep[1] = m; }
+        if (acc && (!skip_nonfinite || isfinite(l))) { acc[0] += (double)l; acc[1] += (double)m; acc[2] += 1.0; }
+    }
+}
+// pred, target f32 [B][L] contiguous; out f32[2]; dpred f32 [B][L] or NULL; out_keep f32[2] or NULL; acc f64[3] or NULL.
+extern "C" int sarssl_regress_loss(const float* pred, const float* target, int B, int L, float* out, float* dpred, float* out_keep,
+                                   double* acc, int skip_nonfinite, void* stream) {
+    SARSSL_REQUIRE(B > 0 && L > 0 && pred && target && out, "sarssl_regress_loss");
+    regress_loss_kernel<<<1, 256, 0, ST>>>(pred, target, (long)B * L, out, dpred, out_keep, acc, skip_nonfinite);
+    SARSSL_CHECK_LAUNCH("regress_loss_kernel");
     return 0;
 }

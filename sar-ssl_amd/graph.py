@@ -1,5 +1,5 @@
 """One pretraining step (code/learner.py:93-115: data -> model -> loss.backward() -> optimizer.step() -> optimizer.zero_grad())
-captured into HIP graphs and replayed.
+captured into HIP graphs and replayed; DownstreamStepGraph does the same for the downstream train and evaluation steps.
 
 Why: the eager step enqueues ~450 launches from Python (9 ms of host time against 14 ms of GPU time at batch 64); every kernel-side
 gain beyond that would be hidden by the host.  A captured step costs the host one graph launch.
@@ -37,33 +37,23 @@ class _Ctx:
         pass
 
 
-class PretrainStepGraph:
-    """``g = PretrainStepGraph(net, flat, lr=...)``; ``g.step(x)`` or ``g.step(pcm=...)`` runs one training step and returns the
-    device tensor ``[loss, diff]`` (overwritten by the next step).  Captured lazily for the first input shape; inputs of another
-    shape raise (the caller falls back to the eager step for ragged tail batches)."""
+class _StepGraph:
+    """What the captured steps share (PretrainStepGraph, DownstreamStepGraph): Adam moments and the device-resident step state, the
+    guarded Adam launch with its lo-shadow bookkeeping, the warm-up / restore / capture sequence, the per-epoch optimizer reset.  A
+    subclass provides ``self.acc`` (running f64 sums the loss launch adds to) and the step's body."""
 
-    def __init__(self, net, flat, reducer=None, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, two_streams=None):
-        assert net.pretrain and flat.on_gpu
-        self.net, self.flat, self.reducer = net, flat, reducer
+    reducer = None
+
+    def _init_step(self, net, flat, lr, betas, eps, salt):
+        self.net, self.flat = net, flat
         self.lr, self.betas, self.eps = float(lr), betas, eps
         self.dev = flat.flat.device
         self.m = torch.zeros_like(flat.flat)
         self.v = torch.zeros_like(flat.flat)
-        self.state = hip.step_state_new(self.dev, RT._seed ^ 0x6A09E667F3BCC909, self.lr, betas)
-        self.acc = torch.zeros(2, dtype=torch.float64, device=self.dev)        # running sum of (loss, diff) since reset_epoch()
+        self.state = hip.step_state_new(self.dev, RT._seed ^ salt, self.lr, betas)
         self.nsteps = 0
-        self._plan = None         # the first captured plan (kept under this name for tests / tools)
-        self._plans = {}          # full_pred (bool) -> (plan, pred, xin, vis_masks, ecat): the compact step and, captured on first use, the
-                                  # step with the decoder / block tails on EVERY frame (the batch whose vis an epoch returns)
-        self._plan_lo = {}        # full_pred (bool) -> the lo shadow the plan's Adam launch rewrites (None: captured before it existed)
-        self._key = None
-        self._pool = None
-        self._stage = []          # ring of (pinned staging buffer, event) for the masks
-        self._stage_i = 0
-        self.guard = torch.zeros(1, dtype=torch.float32, device=self.dev)      # data parallel: the ranks' summed loss = the optimizer launch's guard
         self.zero_grad_in_adam = True     # optimizer.zero_grad() folded into the Adam pass (tests switch it off to read the gradient)
 
-    # ------------------------------------------------------------------------------------------------ optimizer interface
     def reset_epoch(self, lr=None):
         """The reference constructs a new Adam at the start of every epoch (learner.py:83): moments and step count restart."""
         if lr is not None:
@@ -73,6 +63,111 @@ class PretrainStepGraph:
         hip.step_state_reset(self.state, self.lr, self.betas)
         self.acc.zero_()
         self.nsteps = 0
+
+    def skipped_steps(self):
+        """Steps whose update was skipped because the loss was not finite (synchronises)."""
+        return hip.step_state_skipped(self.state)
+
+    def _exchange_in_graph(self):
+        """True when the bucket all-reduces are captured INSIDE the step graph: the library's own exchange (sarssl_allreduce_bucket,
+        SARSSL_NATIVE_RCCL=1) - and only at world size 1 unless SARSSL_NATIVE_RCCL_CAPTURE=1 says otherwise.  With more than one rank
+        a captured RCCL kernel has never run (no multi-GPU node in five rounds): there the native exchange is issued BETWEEN the
+        segment graphs like torch.distributed's, which is the form the 2- and 4-rank tests pin (advisor, round 4)."""
+        import os
+        red = self.reducer
+        if red is None or getattr(red, "native", None) is None:
+            return False
+        return red.world == 1 or os.environ.get("SARSSL_NATIVE_RCCL_CAPTURE", "0") == "1"
+
+    def _adam(self, guard, world=1):
+        """The step's optimizer launch.  guard = the step's loss: a forward that overflowed fp16 (non-finite loss) leaves parameters and
+        moments alone - the reference's GradScaler skips such a step too (code/learner.py:105-108); decided on the device, counted in
+        the step state.  Deliberately stricter than the reference in the modes without a GradScaler counterpart (fp32 / bf16, where the
+        reference would let a NaN propagate into the parameters): the captured step never applies an update computed from a non-finite
+        loss, in any mode; the launch-by-launch learner path guards under --use-amp only, like the reference (advisor, round 5:
+        documented, not aligned)."""
+        lo = self.flat.wl16
+        hip.adam_step_dev(self.flat.flat, self.flat.grad, self.m, self.v, self.flat.w16, self.state, gscale=1.0 / world, eps=self.eps,
+                          zero_grad=self.zero_grad_in_adam, ph16=self.flat.wh16, guard=guard,
+                          pl16=lo)                  # hybrid mode: the weights' fp16 lo shadow is rewritten by the same pass (None otherwise)
+        if lo is not None:
+            self.flat._lo_synced = self.flat._synced
+        self._adam_lo = lo                          # (captured: the lo shadow every replay of this step rewrites - see _after_replay)
+
+    def _after_replay(self, plan_lo):
+        """Host bookkeeping behind a replayed training step.  plan_lo: the lo shadow the plan's Adam launch rewrites."""
+        if self.flat.wl16 is not None and plan_lo is not self.flat.wl16:
+            self.flat.refresh_lo()                         # captured before the hybrid mode allocated the lo shadow: rewrite it behind the step
+        runtime.bump_version()                             # weights moved: eager users of the re-laid-out caches must rebuild
+        self.nsteps += 1
+
+    def _capture_segments(self, body, accs):
+        """Warm-up, restore, capture.  ``body(seg, with_adam)`` enqueues the step; it runs once eagerly without side effects (lazy kernel
+        loading, workspaces, allocator - BatchNorm buffers, the gradient and the accumulators ``accs`` are restored, no Adam) and once
+        under capture.  -> the _Segments holding the plan."""
+        net, dev = self.net, self.dev
+        bufs = [b for b in net.buffers()]
+        keep = [b.clone() for b in bufs]
+        accs_keep = [a.clone() for a in accs]
+        hook, net._stage_hook = net._stage_hook, None
+        torch.cuda.synchronize()
+        cur = torch.cuda.current_stream()
+        cap = torch.cuda.Stream(device=dev)
+        cap.wait_stream(cur)
+        try:
+            with torch.cuda.stream(cap):
+                body(None, False)
+                cap.synchronize()
+                self.flat.grad.zero_()
+                for b, k in zip(bufs, keep):
+                    b.copy_(k)
+                for a, k in zip(accs, accs_keep):
+                    a.copy_(k)
+                runtime.bump_version()            # every re-laid-out weight cache misses during capture: its rebuild becomes graph nodes
+                seg = _Segments(self, cap)
+                net._stage_hook = seg.on_stage
+                # cut mode: the spat / spec hooks fire on the ORIGIN stream after the side stream has joined it.  Needed where the graph is
+                # cut at a bucket boundary, and also when the exchange is captured: its communication stream must fork off the origin
+                # stream, not off the already-forked side stream (a fork of a fork crashes hipStreamEndCapture on ROCm 7.2,
+                # tools/capture_nested_fork_repro.py)
+                in_graph = self._exchange_in_graph()
+                net._cut_mode = in_graph or (self.reducer is not None and (self.reducer.exchange or getattr(self.reducer, "native", None) is not None))
+                seg.in_graph = in_graph
+                hip.step_state_attach(self.state)
+                try:
+                    self._seed_ctr0 = RT._ctr               # (tests: the static dropout seeds of the captured launches)
+                    seg.begin()
+                    body(seg, True)
+                    seg.end()
+                finally:
+                    hip.step_state_attach(None)
+                    net._cut_mode = False
+        finally:
+            net._stage_hook = hook
+        cur.wait_stream(cap)
+        torch.cuda.synchronize()
+        return seg
+
+
+class PretrainStepGraph(_StepGraph):
+    """``g = PretrainStepGraph(net, flat, lr=...)``; ``g.step(x)`` or ``g.step(pcm=...)`` runs one training step and returns the
+    device tensor ``[loss, diff]`` (overwritten by the next step).  Captured lazily for the first input shape; inputs of another
+    shape raise (the caller falls back to the eager step for ragged tail batches)."""
+
+    def __init__(self, net, flat, reducer=None, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, two_streams=None):
+        assert net.pretrain and flat.on_gpu
+        self._init_step(net, flat, lr, betas, eps, 0x6A09E667F3BCC909)
+        self.reducer = reducer
+        self.acc = torch.zeros(2, dtype=torch.float64, device=self.dev)        # running sum of (loss, diff) since reset_epoch()
+        self._plan = None         # the first captured plan (kept under this name for tests / tools)
+        self._plans = {}          # full_pred (bool) -> (plan, pred, xin, vis_masks, ecat): the compact step and, captured on first use, the
+                                  # step with the decoder / block tails on EVERY frame (the batch whose vis an epoch returns)
+        self._plan_lo = {}        # full_pred (bool) -> the lo shadow the plan's Adam launch rewrites (None: captured before it existed)
+        self._key = None
+        self._pool = None
+        self._stage = []          # ring of (pinned staging buffer, event) for the masks
+        self._stage_i = 0
+        self.guard = torch.zeros(1, dtype=torch.float32, device=self.dev)      # data parallel: the ranks' summed loss = the optimizer launch's guard
 
     # ------------------------------------------------------------------------------------------------ masks
     def _mask_layout(self, B, T, nm):
@@ -157,29 +252,7 @@ class PretrainStepGraph:
                 seg.cut(("finish", None))
         elif self.reducer is not None:                     # (native exchange under capture: the join with the communication stream becomes a graph edge)
             self.reducer.finish(guard=self.guard if world > 1 else None)      # (world 1: closes the step's hook record, see FlatGradAllReduce.strict)
-        # guard = the step's loss: a forward that overflowed fp16 (non-finite loss) leaves parameters and moments alone - the reference's
-        # GradScaler skips such a step too (code/learner.py:105-108); decided on the device, counted in the step state.  Deliberately
-        # stricter than the reference in the modes without a GradScaler counterpart (fp32 / bf16, where the reference would let a NaN
-        # propagate into the parameters): the captured step never applies an update computed from a non-finite loss, in any mode; the
-        # launch-by-launch learner path guards under --use-amp only, like the reference (advisor, round 5: documented, not aligned)
-        lo = self.flat.wl16
-        hip.adam_step_dev(self.flat.flat, self.flat.grad, self.m, self.v, self.flat.w16, self.state, gscale=1.0 / world, eps=self.eps,
-                          zero_grad=self.zero_grad_in_adam, ph16=self.flat.wh16, guard=guard,
-                          pl16=lo)                  # hybrid mode: the weights' fp16 lo shadow is rewritten by the same pass (None otherwise)
-        if lo is not None:
-            self.flat._lo_synced = self.flat._synced
-        self._adam_lo = lo                          # (captured: the lo shadow every replay of this step rewrites - see step())
-
-    def _exchange_in_graph(self):
-        """True when the bucket all-reduces are captured INSIDE the step graph: the library's own exchange (sarssl_allreduce_bucket,
-        SARSSL_NATIVE_RCCL=1) - and only at world size 1 unless SARSSL_NATIVE_RCCL_CAPTURE=1 says otherwise.  With more than one rank
-        a captured RCCL kernel has never run (no multi-GPU node in five rounds): there the native exchange is issued BETWEEN the
-        segment graphs like torch.distributed's, which is the form the 2- and 4-rank tests pin (advisor, round 4)."""
-        import os
-        red = self.reducer
-        if red is None or getattr(red, "native", None) is None:
-            return False
-        return red.world == 1 or os.environ.get("SARSSL_NATIVE_RCCL_CAPTURE", "0") == "1"
+        self._adam(guard, world)                           # (guarded by the step's loss, see _StepGraph._adam)
 
     def step_eager(self, x=None, pcm=None):
         """The same step enqueued launch by launch (inputs whose shape differs from the captured one, e.g. a ragged last batch):
@@ -232,48 +305,10 @@ class PretrainStepGraph:
                 net.__dict__["_full_pred_once"] = True      # (popped by the forward pass: decoder and block tails on every frame)
             self._body(seg, self.src, self.idx, self.ch, self.mp, pcm is not None, with_adam=with_adam)
 
-        # ---- warm-up: one eager pass without side effects (lazy kernel loading, workspaces, allocator) - buffers restored, no Adam
-        bufs = [b for b in net.buffers()]
-        keep = [b.clone() for b in bufs]
-        acc_keep = self.acc.clone()
-        hook, net._stage_hook = net._stage_hook, None
+        # ---- warm-up (one eager pass without side effects, no Adam), then the capture
         idx, ch = self._draw_masks(B, T, consume_rng=False)
         self._upload_masks(idx, ch, B, T)
-        torch.cuda.synchronize()
-        cur = torch.cuda.current_stream()
-        cap = torch.cuda.Stream(device=dev)
-        cap.wait_stream(cur)
-        try:
-            with torch.cuda.stream(cap):
-                body(None, False)
-                cap.synchronize()
-                self.flat.grad.zero_()
-                for b, k in zip(bufs, keep):
-                    b.copy_(k)
-                self.acc.copy_(acc_keep)
-                runtime.bump_version()            # every re-laid-out weight cache misses during capture: its rebuild becomes graph nodes
-                seg = _Segments(self, cap)
-                net._stage_hook = seg.on_stage
-                # cut mode: the spat / spec hooks fire on the ORIGIN stream after the side stream has joined it.  Needed where the graph is
-                # cut at a bucket boundary, and also when the exchange is captured: its communication stream must fork off the origin
-                # stream, not off the already-forked side stream (a fork of a fork crashes hipStreamEndCapture on ROCm 7.2,
-                # tools/capture_nested_fork_repro.py)
-                in_graph = self._exchange_in_graph()
-                net._cut_mode = in_graph or (self.reducer is not None and (self.reducer.exchange or getattr(self.reducer, "native", None) is not None))
-                seg.in_graph = in_graph
-                hip.step_state_attach(self.state)
-                try:
-                    self._seed_ctr0 = RT._ctr               # (tests: the static dropout seeds of the captured launches)
-                    seg.begin()
-                    body(seg, True)
-                    seg.end()
-                finally:
-                    hip.step_state_attach(None)
-                    net._cut_mode = False
-        finally:
-            net._stage_hook = hook
-        cur.wait_stream(cap)
-        torch.cuda.synchronize()
+        seg = self._capture_segments(body, [self.acc])
         self._plans[bool(full)] = (seg.plan, self.pred, self.xin, self.vis_masks, self.ecat)
         self._plan_lo[bool(full)] = self._adam_lo
         if self._plan is None:
@@ -311,15 +346,8 @@ class PretrainStepGraph:
                 self.reducer._on_stage(item)
             else:                                           # "finish": wait for the buckets (stream-side for RCCL) + the collective guard
                 self.reducer.finish(guard=self.guard if self.reducer.world > 1 else None)
-        if self.flat.wl16 is not None and self._plan_lo.get(full_pred) is not self.flat.wl16:
-            self.flat.refresh_lo()                         # captured before the hybrid mode allocated the lo shadow: rewrite it behind the step
-        runtime.bump_version()                             # weights moved: eager users of the re-laid-out caches must rebuild
-        self.nsteps += 1
+        self._after_replay(self._plan_lo.get(full_pred))
         return self.out
-
-    def skipped_steps(self):
-        """Steps whose update was skipped because the loss was not finite (synchronises)."""
-        return hip.step_state_skipped(self.state)
 
     def vis(self):
         """vis dict of the last step (same keys as SARSSL.forward's third result).  Copies: the graph's pool tensors are overwritten
@@ -334,6 +362,183 @@ class PretrainStepGraph:
             e = tuple(t.clone() if torch.is_tensor(t) else t for t in e) if isinstance(e, tuple) else e.clone()
             pred = _full_pred_fn(e, self.net.decoder, self.net, step_rows=(pred, self.idx.clone(), self.B, self.T))     # the step's own rows at the masked frames
         return LazyVis(pred, self.xin.clone(), self.vis_masks[0].clone(), self.vis_masks[1].clone())
+
+
+class DownstreamStepGraph(_StepGraph):
+    """The downstream (fine-tuning) step of ``SARSSL(pretrain=False)`` - code/learner.py:168-269 - as two captured variants that share the
+    input buffer, the target buffer and the loss words:
+      ``g.step(pcm=, target=)``       front-end -> both encoders -> mean over the frames -> head -> regression loss + gradient -> backward
+                                      -> frozen gradients zeroed -> guarded Adam (train mode; returns the device tensor [loss, metric]);
+      ``g.eval_step(pcm=, target=)``  forward only (eval mode), loss and metric added to the evaluation sums ``acc_eval``; ``pred`` and the
+                                      pooled embedding ``pooled`` stay in fixed buffers until the next step.
+    ``step_eager`` / ``eval_step_eager`` enqueue the same bodies launch by launch (ragged last batches) on the same moments, step state
+    and sums.  The forward / backward pairs are called directly (no torch.autograd inside the capture); which encoder runs under
+    RT.inference is decided as autograd.tape_apply would: an encoder without a trainable parameter ('lineareval'), and an encoder the head
+    does not read (its forward still runs: the reference computes that branch and its BatchNorm statistics move in train mode).
+    Everything is captured on ONE stream.  The evaluation plan rebuilds its re-laid-out weights from the current 16-bit shadows inside
+    the replay (every cache misses while it is captured), so it follows the weights the training replays move.
+    ``acc`` / ``acc_eval`` = f64 [sum loss, sum metric, count]: training steps with a non-finite loss stay out (and are skipped by the
+    Adam launch), evaluation adds every batch, as test_epoch does."""
+
+    EMBEDS = ("spat", "spec", "spec_spat")
+
+    def __init__(self, net, flat, lr=1e-4, betas=(0.9, 0.999), eps=1e-8):
+        assert not net.pretrain and net.embed_use4ds in self.EMBEDS and flat.on_gpu
+        self._init_step(net, flat, lr, betas, eps, 0xBB67AE8584CAA73B)
+        self.acc = torch.zeros(3, dtype=torch.float64, device=self.dev)
+        self.acc_eval = torch.zeros(3, dtype=torch.float64, device=self.dev)
+        self.out = torch.zeros(2, dtype=torch.float32, device=self.dev)      # (loss, metric) of the last step, either variant
+        self.head = net.mlp_head if net.downstream_dlabel == 1 else net.joint_head
+        self.requires_grad = tuple(p.requires_grad for p in flat.params)
+        self.frozen = flat.frozen_ranges()
+        self.precision = runtime.get_precision()
+        self._plans = {}          # training (bool) -> (plan, key, src, tgt, pred, pooled)
+        self._bufs = {}           # (input shape, dtype) -> (input buffer, target buffer): one pair when both variants see the same shape
+        self._plan_lo = {}
+        self._seed_base = 1 << 20     # RT._ctr at the start of every body: captured and eager launches draw with the same static seeds
+        self.pred = self.pooled = None
+
+    def reset_eval(self):
+        self.acc_eval.zero_()
+
+    # ------------------------------------------------------------------------------------------------ the step
+    def _body(self, train, src, tgt, with_adam=True):
+        """Enqueues one step on the current stream; -> (pred [B, L], pooled [B, d]), loss words in ``self.out``."""
+        from . import engine
+        net, dev = self.net, self.dev
+        assert net.training == train, "step() needs the model in train mode, eval_step() in eval mode"
+        B, T, F = src.shape[0], (src.shape[1] - 512) // 256 + 1, 256
+        spe, spa = net.spec_encoder, net.spat_encoder
+        use = {"spec": (spe,), "spat": (spa,), "spec_spat": (spe, spa)}[net.embed_use4ds]
+        reads = [any(e is u for u in use) for e in (spe, spa)]
+        need = [train and r and any(p.requires_grad for p in e.parameters()) for e, r in zip((spe, spa), reads)]
+        ctr, RT._ctr = RT._ctr, self._seed_base
+        try:
+            if train and with_adam:
+                hip.step_tick(self.state)
+            runtime.begin_forward(net.parameters())
+            RT.inference = not any(need)
+            try:
+                engine.prepare_step_weights(net, F, T, need_bwd=any(need))
+            finally:
+                RT.inference = False
+            x = hip.stft_frontend(src)
+            a_spec, a_spat = hip.mask_inputs(x, None, None, 1, RT.dtype)      # (B, F, T, 4) in the forward dtype, nothing masked
+            d = sum(e.dembed for e in use)
+            ecat = torch.empty((B * T, d), dtype=torch.float32 if RT.hybrid else RT.dtype, device=dev) if len(use) == 2 else None
+            saved, col = [], 0
+            for enc, a0, r, nd in ((spe, a_spec, reads[0], need[0]), (spa, a_spat, reads[1], need[1])):
+                sv = []
+                RT.inference = not nd
+                try:
+                    if r and ecat is not None:
+                        enc._fwd_cl(a0, B, T, sv, out=ecat[:, col:col + enc.dembed])
+                        col += enc.dembed
+                    elif r:
+                        e1 = enc._fwd_cl(a0, B, T, sv)
+                    else:
+                        enc._fwd_cl(a0, B, T, sv)
+                finally:
+                    RT.inference = False
+                saved.append(sv)
+            pooled = hip.mean_rows((ecat if ecat is not None else e1).view(B, T, d))
+            hsaved = []
+            pred = engine.head_fwd(pooled, self.head, hsaved)
+            if not train:
+                hip.regress_loss(pred, tgt, sink=(self.out, self.acc_eval), skip_nonfinite=False)
+                return pred, pooled
+            _, dpred = hip.regress_loss(pred, tgt, sink=(self.out, self.acc), with_grad=True, skip_nonfinite=True)
+            hip.sums_arena_reset(dev)
+            dpool = engine.head_bwd(dpred, self.head, hsaved)
+            col = 0
+            for enc, sv, r, nd in zip((spe, spa), saved, reads, need):
+                if not r:
+                    continue
+                if nd:
+                    dy = hip.mean_rows_bwd(dpool[:, col:col + enc.dembed] if ecat is not None else dpool, T, RT.gdtype)
+                    enc._bwd_cl(dy.view(B * T, enc.dembed), sv)
+                col += enc.dembed
+            self.flat.zero_frozen_grads(self.frozen)       # (the hand-written backward may have accumulated into frozen slices)
+            if with_adam:
+                self._adam(self.out)
+            return pred, pooled
+        finally:
+            RT._ctr = ctr
+
+    def _key(self, pcm, train):
+        return (tuple(pcm.shape), pcm.dtype, runtime.get_precision(), bool(train))
+
+    def matches(self, pcm, train=True):
+        """True when ``pcm`` can take the captured variant (not captured yet, or captured for this shape / dtype / numeric mode)."""
+        ent = self._plans.get(bool(train))
+        return self.net.training == bool(train) and (ent is None or ent[1] == self._key(pcm, train))
+
+    def _target(self, target, B):
+        return target.to(device=self.dev, dtype=torch.float32).reshape(B, -1).contiguous()
+
+    def _eager(self, train, pcm, target):
+        src = pcm.contiguous()
+        tgt = self._target(target, src.shape[0])
+        self.flat._fresh = False
+        self.flat.ensure_shadow()
+        hip.step_state_attach(self.state)                  # the dropout launches add the salt the tick advances, like the captured ones
+        try:
+            self.pred, self.pooled = self._body(train, src, tgt)
+        finally:
+            hip.step_state_attach(None)
+        if train:
+            runtime.bump_version()
+            self.nsteps += 1
+        return self.out
+
+    def step_eager(self, pcm, target):
+        return self._eager(True, pcm, target)
+
+    def eval_step_eager(self, pcm, target):
+        return self._eager(False, pcm, target)
+
+    def _capture(self, train, pcm, target):
+        assert pcm.dim() == 3 and pcm.shape[2] == 2, "graph step: 2-channel segments ('M' pairing of two mics)"
+        tgt0 = self._target(target, pcm.shape[0])
+        bk = (tuple(pcm.shape), pcm.dtype, tuple(tgt0.shape))
+        if bk not in self._bufs:
+            self._bufs[bk] = (pcm.clone(), tgt0.clone())
+        src, tgt = self._bufs[bk]
+        src.copy_(pcm, non_blocking=True)                  # (the warm-up runs on real data: nothing non-finite reaches the statistics)
+        tgt.copy_(tgt0, non_blocking=True)
+        res = {}
+
+        def body(seg, with_adam):
+            res["out"] = self._body(train, src, tgt, with_adam=with_adam)
+        seg = self._capture_segments(body, [self.acc, self.acc_eval])
+        self._plans[train] = (seg.plan, self._key(pcm, train), src, tgt) + res["out"]
+        self._plan_lo[train] = getattr(self, "_adam_lo", None) if train else None
+
+    def _replay(self, train, pcm, target):
+        assert RT.replay is None, "replayed dropout masks (parity tests) need the eager step"
+        assert self.net.training == train, "step() needs the model in train mode, eval_step() in eval mode"
+        if train not in self._plans:
+            self._capture(train, pcm, target)
+        plan, key, src, tgt, pred, pooled = self._plans[train]
+        if key != self._key(pcm, train):
+            raise ValueError("DownstreamStepGraph was captured for %r, got %r" % (key, self._key(pcm, train)))
+        if src.data_ptr() != pcm.data_ptr():
+            src.copy_(pcm, non_blocking=True)
+        tgt.copy_(self._target(target, src.shape[0]), non_blocking=True)
+        self.flat._fresh = False
+        self.flat.ensure_shadow()                          # parameters changed through torch since the last step (load_state_dict, ...)
+        for _, g in plan:
+            g.replay()
+        self.pred, self.pooled = pred, pooled
+        if train:
+            self._after_replay(self._plan_lo[train])
+        return self.out
+
+    def step(self, pcm, target):
+        return self._replay(True, pcm, target)
+
+    def eval_step(self, pcm, target):
+        return self._replay(False, pcm, target)
 
 
 class _Segments:

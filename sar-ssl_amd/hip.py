@@ -1655,6 +1655,24 @@ def masked_mse_fwd(pred, x, idx_i32, mch_i32, sink=None, with_grad=False):
     return out
 
 
+def regress_loss(pred, target, sink=None, with_grad=False, skip_nonfinite=True):
+    """pred, target f32 (B, L) -> out f32[2] device tensor (mean squared error, mean absolute error), or (out, dpred) with the loss
+    gradient 2 (pred - target) / (B L) from the same launch.  sink = (out_keep f32[2], acc f64[3]) as in masked_mse_fwd: acc += (loss,
+    mae, 1); skip_nonfinite: a non-finite loss stays out of acc (training steps) or is added like any other (evaluation)."""
+    _need_cuda(pred, target)
+    assert pred.dtype == torch.float32 and target.dtype == torch.float32 and pred.shape == target.shape and pred.dim() == 2
+    assert pred.is_contiguous() and target.is_contiguous()
+    B, L = pred.shape
+    out = torch.empty((2,), dtype=torch.float32, device=pred.device)
+    dpred = torch.empty_like(pred) if with_grad else None
+    keep, acc = sink if sink is not None else (None, None)
+    assert keep is None or (keep.dtype == torch.float32 and keep.numel() == 2)
+    assert acc is None or (acc.dtype == torch.float64 and acc.numel() == 3)
+    _lib.call("sarssl_regress_loss", _p(pred), _p(target), c_int(B), c_int(L), _p(out), _p(dpred), _p(keep), _p(acc),
+              c_int(1 if skip_nonfinite else 0), _stream())
+    return (out, dpred) if with_grad else out
+
+
 # ---- decoder on the masked frames only (include/sarssl_hip.h): gather / scatter of the masked rows, loss on the compact prediction
 def gather_rows(src2d, idx_i32, B, T):
     """src [B*T, d] (row stride any) -> [B*nm, d]: rows (b, idx[b][j]); idx ascending per item."""

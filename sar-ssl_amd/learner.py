@@ -216,6 +216,11 @@ class Learner(ABC):
         """One epoch of downstream training: Adam re-created per epoch (learner.py:176), per batch preprocess -> model ->
         ``self.loss`` -> backward -> step.  Loss / metric are accumulated on the device (one sync per epoch, not per step)."""
         self.model.train()
+        g = self._downstream_graph()
+        if g is not None:
+            dataset, raw = self._peek_raw(dataset)
+            if raw:
+                return self._train_epoch_graph(g, dataset, lr, return_metric)
         optimizer = runtime.FusedAdam(self._flat, lr=float(lr), betas=(0.9, 0.999))
         optimizer.zero_grad()
         frozen = self._flat.frozen_ranges()
@@ -241,15 +246,101 @@ class Learner(ABC):
             torch.distributed.all_reduce(acc)
             acc /= world
         loss, metric = float(acc[0]), acc[1].float().cpu()
+        self._warn_fp16_overflow()
+        return (loss, metric) if return_metric else loss
+
+    def _warn_fp16_overflow(self):
         if self.use_amp and runtime.RT.dtype == torch.float16 and hip.fp16_overflow(clear=True):
             # (the downstream path has no loss launch that reads the context's fp16-overflow word: report it once per epoch)
             import warnings
             warnings.warn("network input outside fp16's range in this epoch (spectrum / (mean|X_0| + eps) > 65 504: a near-silent reference "
                           "microphone?) - the fp16 forward clipped it; SARSSL_AMP_DTYPE=bf16 or no --use-amp has the range")
+
+    def _downstream_graph(self):
+        """The captured downstream step (graph.DownstreamStepGraph) when it serves this learner, else None (the launch-by-launch epoch).
+        Same switch as pretraining (SARSSL_GRAPH=0 opts out); one GPU; no replayed dropout masks; a downstream SARSSL whose head reads
+        'spat', 'spec' or 'spec_spat'; and the default front-end, loss and metric - a subclass's own ``loss`` / ``evaluate`` /
+        ``data_preprocess`` must be honoured, and only the launch-by-launch epoch calls them.  The graph is dropped with the flat buffers
+        (cuda(), _load_model_state) and rebuilt when the numeric mode or a requires_grad flag has changed."""
+        from .graph import DownstreamStepGraph
+        from .model import SARSSL
+        m = self.model
+        ok = (os.environ.get("SARSSL_GRAPH", "1") != "0" and sdist.world_size() == 1 and runtime.RT.replay is None
+              and isinstance(m, SARSSL) and not m.pretrain and m.embed_use4ds in DownstreamStepGraph.EMBEDS
+              and self._flat is not None and self._flat.on_gpu
+              and all(getattr(type(self), n, None) is getattr(STFTLearner, n) for n in ("data_preprocess", "loss", "evaluate")))
+        if not ok:
+            return None
+        g = self.__dict__.get("_step_graph")
+        flags = tuple(p.requires_grad for p in self._flat.params)
+        if (not isinstance(g, DownstreamStepGraph) or g.flat is not self._flat or g.requires_grad != flags
+                or g.precision != runtime.get_precision()):
+            g = self.__dict__["_step_graph"] = DownstreamStepGraph(m, self._flat, betas=(0.9, 0.999))
+        return g
+
+    def _peek_raw(self, dataset):
+        """-> (the same batches, whether the first one is a plain 2-microphone batch of the default front-end): the captured step runs
+        the front-end itself, so the epoch takes it only for such batches (_graph_takes_raw_batch)."""
+        import itertools
+        it = iter(dataset)
+        try:
+            first = next(it)
+        except StopIteration:
+            return [], False
+        sig = first[0] if torch.is_tensor(first[0]) else torch.as_tensor(first[0])
+        return itertools.chain([first], it), self._graph_takes_raw_batch(sig)
+
+    def _graph_batch(self, mic_sig_batch, gt_batch):
+        """(raw batch on the device, targets as get_tar_batch forms them) of one batch of an epoch that runs through the captured step."""
+        if not torch.is_tensor(mic_sig_batch):
+            mic_sig_batch = torch.as_tensor(mic_sig_batch)
+        if not self._graph_takes_raw_batch(mic_sig_batch):
+            raise hip._lib.SarsslHipError("the epoch began with plain 2-microphone batches (captured downstream step) and met a batch of "
+                                          "another kind; SARSSL_GRAPH=0 takes mixed epochs launch by launch")
+        sig = mic_sig_batch.to(self.device, non_blocking=True).contiguous()
+        return sig, self.get_tar_batch(gt_batch[self.task].to(self.device))
+
+    def _train_epoch_graph(self, g, dataset, lr, return_metric):
+        """train_epoch with every full-size batch replayed from the captured step; a batch of another shape (a ragged last batch) takes
+        the same step launch by launch on the same optimizer state."""
+        g.reset_epoch(float(lr))                                                            # "Adam re-created every epoch" (learner.py:176)
+        skipped0 = g.skipped_steps()
+        self._flat.grad.zero_()
+        for mic_sig_batch, gt_batch in dataset:
+            b = self._graph_batch(mic_sig_batch, gt_batch)
+            (g.step if g.matches(b[0], True) else g.step_eager)(pcm=b[0], target=b[1])
+        nskip = g.skipped_steps() - skipped0
+        self._report_skipped(nskip, g.nsteps)
+        acc = g.acc.clone()
+        acc = acc[:2] / acc[2].clamp(min=1.0)                                               # (skipped steps are not part of the mean)
+        loss, metric = float(acc[0]), acc[1].float().cpu()
+        self._warn_fp16_overflow()
         return (loss, metric) if return_metric else loss
+
+    def _test_epoch_graph(self, g, dataset, return_metric, return_vis):
+        g.reset_eval()
+        embed, gt = [], []
+        for mic_sig_batch, gt_batch in dataset:
+            b = self._graph_batch(mic_sig_batch, gt_batch)
+            (g.eval_step if g.matches(b[0], False) else g.eval_step_eager)(pcm=b[0], target=b[1])
+            if return_vis:
+                embed += [g.pooled.clone()]
+                gt += [b[1]]
+        acc = g.acc_eval.clone()
+        acc = acc[:2] / acc[2].clamp(min=1.0)
+        loss, metric = float(acc[0]), acc[1].float().cpu()
+        out = (loss,) + ((metric,) if return_metric else ())
+        if return_vis:
+            out += ({"embed": torch.cat(embed, dim=0), "label": torch.cat(gt, dim=0)},)
+        return out if len(out) > 1 else loss
 
     def test_epoch(self, dataset, return_metric=False, return_vis=False):
         self.model.eval()
+        g = self._downstream_graph()
+        if g is not None:
+            dataset, raw = self._peek_raw(dataset)
+            if raw:
+                return self._test_epoch_graph(g, dataset, return_metric, return_vis)
         with torch.no_grad():
             acc = torch.zeros(2, dtype=torch.float64, device=self.device)
             embed, gt = [], []
