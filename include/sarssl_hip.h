@@ -284,6 +284,11 @@ int sarssl_relpos_attn_bwd(const void* qu, long ldq, const void* k, const void* 
                            unsigned long long seed, int dtype, void* stream);      /* bf16 | mixed 16 (qu / k / v / bias fp16) */
 
 /* ---- CNN stem, channels-last (B,F,T,C): code/model.py:50-64 (patch_embed), masking code/model.py:533-564 */
+/* x (nb,2,F,Tn,2) f32 -> the two encoders' inputs spec / spat (nb,F,Tn,4) of `dtype`.  mp (nb,Tn): 1 = visible frame, 0 = masked; mch (nb):
+ * masked channel.  mode 0: pretraining masks - spec = unmasked channel at the masked frames + masked channel at the visible frames, spat =
+ * x at the visible frames; mode 1: no masking (mp / mch unused, may be null); mode 2: frozen-encoder probe (code/model.py:623, :629) - spec =
+ * the unmasked channel at the masked frames only, spat as in mode 0.  fp16 output: input outside fp16's range sets the context's overflow
+ * flag in every mode. */
 int sarssl_mask_inputs(const float* x, const unsigned char* mp, const int* mch, int nb, int F, int Tn, int mode, void* spec,
                        void* spat, int dtype, void* stream);
 int sarssl_stem_c1_fwd(const void* a0, const float* W1, long npix, void* y1, double* stats, int dtype, void* stream);

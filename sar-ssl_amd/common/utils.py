@@ -34,7 +34,10 @@ def get_nparams(model, param_key_list=[]):
 def create_learning_rate_schedule(total_steps, base, decay_type, warmup_steps, linear_end=1e-5):
     def step_fn(step):
         lr = base
-        progress = np.clip((step - warmup_steps) / float(total_steps - warmup_steps), 0.0, 1.0)
+        if total_steps > warmup_steps:
+            progress = np.clip((step - warmup_steps) / float(total_steps - warmup_steps), 0.0, 1.0)
+        else:       # nothing behind the warm-up (`--nepoch 1` with its one warm-up epoch): no decay yet, where the reference divides by zero
+            progress = 0.0 if step <= warmup_steps else 1.0
         if decay_type == "linear":
             lr = linear_end + (lr - linear_end) * (1.0 - progress)
         elif decay_type == "cosine":

@@ -11,7 +11,9 @@
 // ------------------------------------------------------------------------------------------------
 // x: (B, 2, F, T, 2) f32 [mic][f][t][reim];  mp: (B, T) u8 (1 = visible frame, 0 = masked);
 // mch: (B) int32 masked channel.  spec/spat: (B, F, T, 4) with c = reim*2 + mic.
-// mode 0: pretrain masks (model.py:541, :563);  mode 1: no masking, both outputs = x (model.py:676).
+// mode 0: pretrain masks (model.py:541, :563);  mode 1: no masking, both outputs = x (model.py:676);
+// mode 2: frozen-encoder probe masks (model.py:623, :629): spec = the UNMASKED channel at the MASKED frames only (mode 0's first term),
+//         spat = x at the visible frames as in mode 0.
 template <typename T>
 __global__ void mask_inputs_kernel(const float* __restrict__ x, const uint8_t* __restrict__ mp, const int* __restrict__ mch,
                                    int nb, int F, int Tn, int mode, T* __restrict__ spec, T* __restrict__ spat, int* __restrict__ ovf) {
@@ -30,6 +32,11 @@ __global__ void mask_inputs_kernel(const float* __restrict__ x, const uint8_t* _
             const float v0 = (mc == 0) ? 0.f : 1.f, v1 = (mc == 1) ? 0.f : 1.f;   // mask_ch_dense per mic
             s0 = (1.f - p) * v0 + p * (1.f - v0);
             s1 = (1.f - p) * v1 + p * (1.f - v1);
+        } else if (mode == 2) {
+            p = mp[(long)b * Tn + t] ? 1.f : 0.f;
+            const int mc = mch[b];
+            s0 = (mc == 0) ? 0.f : 1.f - p;
+            s1 = (mc == 1) ? 0.f : 1.f - p;
         }
         // this is where externally scaled data (the spectrum divided by mean|X_0| + eps, code/learner.py:539-542) is first encoded in the
         // forward dtype: a value outside fp16's range would become inf, and inf does NOT reach the loss (BatchNorm turns it into NaN,

@@ -762,7 +762,8 @@ def _f64ws(n, device, tag):
 
 
 def mask_inputs(x, mp_u8, mch_i32, mode, dtype):
-    """x (B,2,F,T,2) f32 -> spec_in, spat_in (B,F,T,4) of `dtype` (csrc/stem.hip)."""
+    """x (B,2,F,T,2) f32 -> spec_in, spat_in (B,F,T,4) of `dtype` (csrc/stem.hip).  mode 0: pretraining masks, 1: none, 2: the
+    frozen-encoder probe (spec_in = the unmasked channel at the masked frames only, spat_in as in mode 0)."""
     _need_cuda(x)
     B, _, F, T, _ = x.shape
     spec = torch.empty((B, F, T, 4), dtype=dtype, device=x.device)

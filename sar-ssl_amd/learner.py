@@ -85,6 +85,9 @@ class Learner(ABC):
             return self._pretrain_epoch_graph(dataset, lr, return_diff)
         optimizer = runtime.FusedAdam(self._flat, lr=float(lr), betas=(0.9, 0.999))        # re-created every epoch (learner.py:83)
         optimizer.zero_grad()
+        # frozen-encoder stage (model.SARSSL(pretrain_frozen_encoder=True)): its backward writes the probe decoder's gradients only; the frozen
+        # ranges are zeroed in front of every Adam launch all the same, so a frozen parameter cannot move whatever ran before
+        frozen = self._flat.frozen_ranges() if getattr(self.model, "pretrain_frozen_encoder", False) else ()
         acc = torch.zeros(2, dtype=torch.float64, device=self.device)
         n = 0
         vis_batch = None
@@ -99,6 +102,8 @@ class Learner(ABC):
             #  data parallel: the guard is the sum of the ranks' losses, exchanged with the buckets - every replica takes the same decision)
             guard = loss_batch.detach().clone().reshape(1) if (self.use_amp and loss_batch.dtype == torch.float32) else None
             gscale = self._reducer.finish(guard=guard) if self._reducer is not None else 1.0
+            if frozen:
+                self._flat.zero_frozen_grads(frozen)
             optimizer.step(grad_scale=gscale, guard=guard)
             optimizer.zero_grad()
             if self.use_amp:                                                                # a skipped step is not part of the epoch mean

@@ -318,6 +318,92 @@ class _PretrainFn(torch.autograd.Function):
         return (None,) * (5 + ctx.nparams)
 
 
+class _NoSave(list):
+    """``saved`` list of a forward pass no backward pass follows: keeps nothing alive."""
+
+    def append(self, rec):
+        pass
+
+
+class _FrozenProbeFn(torch.autograd.Function):
+    """Frozen-encoder probe stage (code/model.py:603-666) as one autograd node: probe masks -> both encoders FORWARD ONLY (nothing saved;
+    in train() mode they still normalise with batch statistics, update the BatchNorm running statistics and draw dropout, as the
+    reference's ``model.train()`` makes them) -> ``spec_spat_decoder`` -> masked MSE.  A training step runs the decoder and the loss on the
+    gathered rows of the masked frames; backward is the decoder's backward and nothing else."""
+
+    @staticmethod
+    def forward(ctx, net, x, idx_i32, ch_i32, mp_u8, *params):
+        B, _, F, T, _ = x.shape
+        runtime_begin_forward(net.parameters())
+        step = not RT.inference                              # a backward pass follows (the caller sets RT.inference for eval / no_grad)
+        full_once = net.__dict__.pop("_full_pred_once", False)
+        compact = engine._DEC_MASKED and step and not full_once
+        spe, spa, dec = net.spec_encoder, net.spat_encoder, net.spec_spat_decoder
+        ds, dt_ = spe.dembed, spa.dembed
+        train = net.training
+        RT.inference = True                                  # the encoders: no backward-only outputs
+        try:
+            prep = net.prepare_weights(F, T)
+            spec_in, spat_in = hip.mask_inputs(x, mp_u8, ch_i32, 2, RT.dtype)
+            ecat = torch.empty((B * T, ds + dt_), dtype=torch.float32 if RT.hybrid else RT.dtype, device=x.device)
+            side = net._side_stream(x.device)
+            main = torch.cuda.current_stream()
+            if prep is not True:
+                main.wait_event(prep)
+            if side is not None:                             # the two encoders on two streams, enqueued in alternating chunks (see _PretrainFn)
+                side.wait_stream(main)
+                spat_in.record_stream(side)
+                ecat.record_stream(side)
+                nl = len(spa.embed.layers)
+                assert len(spe.embed.layers) == 1
+                with torch.cuda.stream(side):
+                    e_spat = engine.stem_fwd(spat_in, spa.patch_embed, train, _NoSave())
+                e_spec = engine.stem_fwd(spec_in, spe.patch_embed, train, _NoSave())
+                with torch.cuda.stream(side):
+                    e_spat = engine.block_fwd(e_spat, spa.embed.layers[0], B, T, train, _NoSave(), out=ecat[:, ds:] if nl == 1 else None,
+                                              next_blk=spa.embed.layers[1] if nl > 1 else None)
+                engine.block_fwd(e_spec, spe.embed.layers[0], B, T, train, _NoSave(), out=ecat[:, :ds])
+                with torch.cuda.stream(side):
+                    for li in range(1, nl):
+                        e_spat = engine.block_fwd(e_spat, spa.embed.layers[li], B, T, train, _NoSave(), out=ecat[:, ds:] if li == nl - 1 else None,
+                                                  next_blk=spa.embed.layers[li + 1] if li + 1 < nl else None)
+                del e_spat, e_spec
+                main.wait_stream(side)
+            else:
+                spe._fwd_cl(spec_in, B, T, _NoSave(), out=ecat[:, :ds])
+                spa._fwd_cl(spat_in, B, T, _NoSave(), out=ecat[:, ds:])
+        finally:
+            RT.inference = not step
+        saved = []
+        net.__dict__["_last_ecat"] = None
+        if compact:
+            pred = engine.decoder_fwd(hip.gather_rows(ecat, idx_i32, B, T), dec, saved)             # [B * nm, F * 4]
+            out = hip.masked_mse_compact(pred, x, idx_i32, ch_i32)
+            net.__dict__["_last_ecat"] = ecat                # what a full prediction would start from (vis on request)
+        else:
+            pred = engine.decoder_fwd(ecat, dec, saved)
+            out = hip.masked_mse_fwd(pred, x, idx_i32, ch_i32)
+        # (the launch's second value is pretraining's `diff`; this stage returns loss * 0.0, code/model.py:666 - an exact 0, no device sync)
+        zero = torch.zeros((), dtype=torch.float32, device=x.device)
+        ctx.net, ctx.saved, ctx.aux, ctx.nparams = net, saved, (pred, x, mp_u8, ch_i32, idx_i32, compact), len(params)
+        ctx.mark_non_differentiable(zero, pred)
+        return out[0].clone(), zero, pred
+
+    @staticmethod
+    def backward(ctx, dloss, _dzero, _dpred):
+        net, saved = ctx.net, ctx.saved
+        pred, x, mp_u8, ch_i32, idx_i32, compact = ctx.aux
+        hip.sums_arena_reset(x.device)
+        gs = dloss.contiguous().float()
+        if compact:
+            dpred = hip.masked_mse_bwd_compact(pred, x, idx_i32, ch_i32, 1.0, gs)
+        else:
+            dpred = hip.masked_mse_bwd(pred, x, mp_u8, ch_i32, idx_i32.shape[1], 1.0, gs)
+        engine.decoder_bwd(dpred, net.spec_spat_decoder, saved)
+        net._after_backward_stage("decoder")
+        return (None,) * (5 + ctx.nparams)
+
+
 class SARSSL(nn.Module):
     def __init__(self, sig_shape=[256, 256, 2, 2], patch_shape=(256, 1), patch_mode="T", nmasked_patch=128 * 1, pretrain=True,
                  use_cls=False, downstream_token="all", downstream_head="mlp", downstream_embed="spec_spat",
@@ -329,8 +415,8 @@ class SARSSL(nn.Module):
         npatch_shape = [int(nf / patch_shape[0]), int(nt / patch_shape[1])]
         if nmasked_patch != (npatch_shape[0] * npatch_shape[1] // 2):                         # code/model.py:361-364
             nmasked_patch = npatch_shape[0] * npatch_shape[1] // 2
-        if use_cls or pretrain_frozen_encoder:
-            raise NotImplementedError("use_cls / pretrain_frozen_encoder are outside the pretraining hot path")
+        if use_cls:
+            raise NotImplementedError("use_cls is outside the pretraining hot path")
         self.pretrain, self.pretrain_frozen_encoder, self.device, self.use_cls = pretrain, pretrain_frozen_encoder, device, use_cls
         self.sig_shape = list(sig_shape)
         self.patch_split = at_module.PatchSplit(patch_shape=patch_shape, f_first=False)
@@ -347,6 +433,13 @@ class SARSSL(nn.Module):
                                                   npatch_shape=npatch_shape, device=device)
             self.decoder = EmbedDecoder(sig_shape=sig_shape, patch_shape=patch_shape, dembed=spec_dembed + spat_dembed,
                                         model=["", "fc"], use_cls=False)
+        elif self.pretrain_frozen_encoder:                                                    # code/model.py:470-481
+            self.patch_mask = at_module.PatchMask(patch_mode=patch_mode, nmasked_patch=nmasked_patch,
+                                                  npatch_shape=npatch_shape, device=device)
+            dec = lambda d: EmbedDecoder(sig_shape=sig_shape, patch_shape=patch_shape, dembed=d, model=["", "fc"], use_cls=False)
+            self.spec_spat_decoder = dec(spec_dembed + spat_dembed)                           # the probe: the only module that is trained
+            self.spec_decoder = dec(spec_dembed)                                              # (state_dict keys only: the reference's
+            self.spat_decoder = dec(spec_dembed)                                              #  single-encoder probes are commented out; width sic)
         else:
             dembed_ds = {"spec_spat": spec_dembed + spat_dembed, "spec": spec_dembed, "spat": spat_dembed,
                          "noinfo": spec_dembed}[downstream_embed]
@@ -374,6 +467,8 @@ class SARSSL(nn.Module):
                   ("spat_encoder", body(self.spat_encoder))]
         if self.pretrain:
             groups.append(("decoder", list(self.decoder.parameters())))
+        elif self.pretrain_frozen_encoder:
+            groups.append(("decoder", [p for d in (self.spec_spat_decoder, self.spec_decoder, self.spat_decoder) for p in d.parameters()]))
         return groups
 
     def prepare_weights(self, F, T):
@@ -438,6 +533,31 @@ class SARSSL(nn.Module):
             return h.to(dev, non_blocking=True).to(dt_)
         return to(idx.astype(np.int32), torch.int32), to(ch.astype(np.int32), torch.int32), to(mp, torch.uint8)
 
+    def _forward_frozen(self, x):
+        """Frozen-encoder probe (code/model.py:603-666): (loss, an exact 0, vis).  The stage is defined for frozen encoders - the CLI flips
+        ``requires_grad`` after the learner is built, so the flags are read at every call."""
+        if torch.is_grad_enabled():
+            for name in ("spec_encoder", "spat_encoder"):
+                for k, p in getattr(self, name).named_parameters():
+                    if p.requires_grad:
+                        raise NotImplementedError("pretrain_frozen_encoder trains a decoder on FROZEN encoders (no encoder backward on this path), "
+                                                  "but %s.%s still requires a gradient" % (name, k))
+        nbatch, _, _, nt, _ = x.shape
+        idx, ch, mp = self._masks(nbatch, nt, x.device)
+        params = [p for p in self.spec_spat_decoder.parameters() if p.requires_grad] if torch.is_grad_enabled() else []
+        if params:
+            loss, zero, pred = _FrozenProbeFn.apply(self, x, idx, ch, mp, *params)
+        else:
+            RT.inference = True
+            try:
+                loss, zero, pred = _FrozenProbeFn.forward(_NoCtx(), self, x, idx, ch, mp)
+            finally:
+                RT.inference = False
+        ecat = self.__dict__.pop("_last_ecat", None)
+        if ecat is not None:                # compact training step: the full prediction on request, the step's own rows at the masked frames
+            pred = _full_pred_fn(ecat, self.spec_spat_decoder, self, step_rows=(pred.detach(), idx, nbatch, nt))
+        return loss, zero, LazyVis(pred, x, mp, ch)
+
     def forward(self, x):
         if not x.is_cuda:
             raise hip._lib.SarsslHipError("SARSSL runs on the GPU only (no CPU fallback); got a CPU tensor")
@@ -459,6 +579,8 @@ class SARSSL(nn.Module):
             if ecat is not None:        # compact training step: vis["pred"] = the decoder on every frame of this step's decoder input, on request,
                 pred = _full_pred_fn(ecat, self.decoder, self, step_rows=(pred.detach(), idx, nbatch, nt))      # with the step's own rows at the masked frames
             return loss, out[1], LazyVis(pred, x, mp, ch)
+        if self.pretrain_frozen_encoder:
+            return self._forward_frozen(x)
         # ---- downstream branch (code/model.py:667-719): both encoders on the unmasked input, mean over frames, MLP head
         B, T, F = nbatch, nt, nf
         v = x.permute(0, 3, 2, 4, 1).reshape(B, T, F * 4)                                      # (B, npatch, dpatch*nreim*nmic)

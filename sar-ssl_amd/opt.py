@@ -31,7 +31,8 @@ class opt_pretrain():
         p.add_argument("--source-state", type=str, default="static", metavar="SourceState", help="state of sources")
         p.add_argument("--simu-exp", action="store_true", default=False, help="Experiments on simulated data")
         p.add_argument("--pretrain", action="store_true", default=False, help="change to pretrain stage")
-        p.add_argument("--pretrain-frozen-encoder", action="store_true", default=False, help="(not implemented on this path)")
+        p.add_argument("--pretrain-frozen-encoder", action="store_true", default=False, help="second stage: load the encoders of the pretraining run (exp/pretrain/<time>/best_model.tar), freeze them and train a fresh "
+                            "decoder to reconstruct the masked channel (single GPU; checkpoints under exp/pretrain_frozen_encoder/<time>)")
         p.add_argument("--nepoch", type=int, default=30, metavar="Epoch", help="number of epochs to train (default: 30)")
         p.add_argument("--lr", type=float, default=0.001, metavar="LR", help="learning rate (default:0.001)")
         p.add_argument("--test", action="store_true", default=False, help="change to test stage")
@@ -53,6 +54,7 @@ class opt_pretrain():
         dirs["micsig_simu_pretest"] = dirs["gerdata"] + "/MicSig/simu/pretest"
         dirs["micsig_simu_pretest_ins"] = [dirs["gerdata"] + "/MicSig/simu/pretest_ins_T1000"]
         dirs["log_pretrain"] = dirs["exp"] + "/pretrain/" + self.time
+        dirs["log_pretrain_frozen_encoder"] = dirs["exp"] + "/pretrain_frozen_encoder/" + self.time            # code/opt.py:113
         return dirs
 
 

@@ -1,11 +1,13 @@
 """Pretraining entry point with the reference's command line (code/run_pretrain.py):
 
     python run_pretrain.py --pretrain --simu-exp --gpu-id 0,                      # one GPU
+    python run_pretrain.py --pretrain-frozen-encoder --simu-exp --gpu-id 0, --time <time of the --pretrain run>      # second stage, one GPU
     python run_pretrain.py --pretrain --simu-exp --gpu-id 0,1,2,3,4,5,6,7 [--use-amp]       # eight GPUs, the reference's own form
     torchrun --nproc-per-node 8 run_pretrain.py --pretrain --simu-exp --gpu-id 0,1,2,3,4,5,6,7 [--use-amp]     # same thing
 
-Only the ``--pretrain --simu-exp`` branch (fixed pre-generated simulated segments) is implemented - the path BASELINE.json
-names.  Multi-GPU = one process per GPU over RCCL, not DataParallel (code/learner.py:25-31): with more than one id in ``--gpu-id``
+The ``--simu-exp`` branches (fixed pre-generated simulated segments) are implemented: ``--pretrain`` - the path BASELINE.json names -,
+``--test`` and ``--pretrain-frozen-encoder`` (code/run_pretrain.py:315-402: the encoders of the pretraining run's best checkpoint, frozen,
+under a fresh decoder that learns to reconstruct the masked channel; launch by launch on one GPU).  Multi-GPU = one process per GPU over RCCL, not DataParallel (code/learner.py:25-31): with more than one id in ``--gpu-id``
 and no launcher in the environment this entry point starts its own ranks (launch.py) before anything touches the GPU, like the
 reference's single command (code/run_pretrain.py:204-205); per-epoch scalars go to a JSONL log (tensorboardX is optional and absent
 here).
@@ -26,6 +28,10 @@ def main(argv=None):
     dirs = opts.dir()
     from sar_ssl_amd import launch
     gpu_ids = launch.parse_gpu_ids(args.gpu_id)
+    frozen = bool(args.pretrain_frozen_encoder)
+    if frozen and (len(gpu_ids) > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1):
+        raise SystemExit("--pretrain-frozen-encoder runs on one GPU (its step has no data-parallel form): give --gpu-id a single id, "
+                         "e.g. `--gpu-id 0,`")
     if not launch.launched():
         if len(gpu_ids) > 1 and not args.no_cuda and not args.test:
             # one rank per listed GPU; this process only waits for them (it has not initialised HIP and never will)
@@ -39,21 +45,22 @@ def main(argv=None):
 
     if args.no_cuda or not torch.cuda.is_available():
         raise SystemExit("run_pretrain.py (sar_ssl_amd) needs an MI355X GPU: the HIP path has no CPU fallback")
-    if not (args.pretrain or args.test) or not args.simu_exp:
-        raise SystemExit("only `--pretrain --simu-exp` and `--test --simu-exp` are implemented on this path")
+    if not (args.pretrain or args.test or frozen) or not args.simu_exp:
+        raise SystemExit("only `--pretrain --simu-exp`, `--pretrain-frozen-encoder --simu-exp` and `--test --simu-exp` are implemented on this path")
     rank, world, local = sdist.init_from_env()
     device = torch.device("cuda", local)
     set_seed(args.seed)
+    log_dir = dirs["log_pretrain_frozen_encoder"] if frozen else dirs["log_pretrain"]
     if rank == 0:
-        os.makedirs(dirs["log_pretrain"], exist_ok=True)
-        save_config_to_file([{k: v for k, v in args.__dict__.items()}, dirs], os.path.join(dirs["log_pretrain"], "config.json"))
+        os.makedirs(log_dir, exist_ok=True)
+        save_config_to_file([{k: v for k, v in args.__dict__.items()}, dirs], os.path.join(log_dir, "config.json"))
 
     fs, T = args.acoustic_setting["fs"], args.acoustic_setting["T"]
     seeds = {"train": int(args.seed + 4e8), "val": int(args.seed + 1e8), "test": int(args.seed + 1)}
     win_len, nfft, win_shift_ratio, fre_used_ratio = 512, 512, 0.5, 1                       # code/run_pretrain.py:67-72
     nf = nfft // 2
     nt = int((T * fs - win_len * (1 - win_shift_ratio)) / (win_len * win_shift_ratio))
-    net = at_model.SARSSL(sig_shape=(nf, nt, 2, 2), pretrain=True, device=device)
+    net = at_model.SARSSL(sig_shape=(nf, nt, 2, 2), pretrain=not frozen, pretrain_frozen_encoder=frozen, device=device)
     nparam, nparam_sum = get_nparams(net, param_key_list=["spec_encoder", "spat_encoder", "decoder"])
     if rank == 0:
         print(f"T: {T:.3f}, nt: {nt}, nf: {nf}; # Parameters (M): {nparam_sum:.2f}")
@@ -93,10 +100,20 @@ def main(argv=None):
     if args.use_amp:
         learner.amp()
     if args.checkpoint_start:
-        learner.resume_checkpoint(checkpoints_dir=dirs["log_pretrain"], from_latest=True, as_all_state=True)
+        learner.resume_checkpoint(checkpoints_dir=log_dir, from_latest=True, as_all_state=True)
+    if frozen:
+        # code/run_pretrain.py:357-370: the pretraining run's encoders (its decoder has no counterpart here), then every parameter whose
+        # name contains 'encoder' is frozen - the model reads the flags at every forward
+        learner.load_checkpoint_best(checkpoints_dir=dirs["log_pretrain"], as_all_state=False, param_frozen=False)
+        nfrozen = 0
+        for key, value in learner.model.named_parameters():
+            if "encoder" in key:
+                value.requires_grad = False
+                nfrozen += 1
+        print("Frozen encoders and continue pre-training! # matched keys:", nfrozen)
     lr_schedule = create_learning_rate_schedule(total_steps=args.nepoch, base=args.lr, decay_type="cosine", warmup_steps=1,
                                                 linear_end=1e-6)
-    log = open(os.path.join(dirs["log_pretrain"], "scalars.jsonl"), "a") if rank == 0 else None
+    log = open(os.path.join(log_dir, "scalars.jsonl"), "a") if rank == 0 else None
     for epoch in range(learner.start_epoch, args.nepoch + 1):
         lr = float(lr_schedule(epoch))
         set_random_seed(seeds["train"] + epoch + 1000003 * rank)                              # per-rank mask / dropout streams
@@ -111,8 +128,11 @@ def main(argv=None):
         loss_val, diff_val, _ = learner.pretest_epoch(dl_val, return_diff=True)
         if world > 1:                                       # one decision for early stopping / best epoch on every rank
             loss_val, diff_val = sdist.agree([loss_val, diff_val], device=device)
-        stop_flag, is_best = learner.early_stopping(current_score=-loss_val, patience=100)
-        learner.save_checkpoint(epoch=epoch, checkpoints_dir=dirs["log_pretrain"], is_best_epoch=is_best, save_extra_hist=True)
+        if frozen:                                          # code/run_pretrain.py:389-390: no early stopping, no per-epoch history
+            stop_flag, is_best = False, learner.is_best_epoch(current_score=-loss_val)
+        else:
+            stop_flag, is_best = learner.early_stopping(current_score=-loss_val, patience=100)
+        learner.save_checkpoint(epoch=epoch, checkpoints_dir=log_dir, is_best_epoch=is_best, save_extra_hist=not frozen)
         if rank == 0:
             rec = {"epoch": epoch, "lr": lr, "loss_train": loss_train, "diff_train": diff_train, "loss_val": loss_val,
                    "diff_val": diff_val, "nparam_M": nparam_sum}
@@ -121,7 +141,7 @@ def main(argv=None):
         if stop_flag:
             break
     if rank == 0:
-        print("\nPre-Training finished\n")
+        print("\nFrozen Pre-Training finished\n" if frozen else "\nPre-Training finished\n")
 
 
 def run_test(args, dirs, net, device, fs, stft_cfg):
