@@ -50,6 +50,22 @@ def create_learning_rate_schedule(total_steps, base, decay_type, warmup_steps, l
     return step_fn
 
 
+def vis_TSNE(data, label):
+    """t-SNE scatter of ``data`` (nins, dim) coloured by ``label`` (code/common/utils.py:280-291) -> (pyplot, {'data': (nins, 2), 'label'}).
+    sklearn and matplotlib are imported here, not with the package: a caller without them catches the ImportError.  sklearn refuses
+    a perplexity (default 30) >= nins, so for nins <= 30 ``max(1, (nins - 1) // 3)`` is passed; the reference never meets so few points."""
+    from sklearn.manifold import TSNE
+    import matplotlib.pyplot as plt
+    plt.switch_backend("agg")
+    n = len(data)
+    kwargs = {"perplexity": max(1, (n - 1) // 3)} if n <= 30 else {}
+    data_vis = TSNE(n_components=2, learning_rate=100, **kwargs).fit_transform(data)
+    plt.figure(figsize=(4, 3.2))
+    p = plt.scatter(data_vis[:, 0], data_vis[:, 1], c=label, s=15, marker="o", cmap="plasma")
+    plt.colorbar(p)
+    return plt, {"data": data_vis, "label": label}
+
+
 def save_config_to_file(config, file_path):
     with open(file_path, "w") as f:
         json.dump(config, f, indent=4, default=str)

@@ -465,6 +465,36 @@ class Learner(ABC):
                     value.requires_grad = False
         return checkpoint["epoch"]
 
+    def _cast_to_live(self, sd):
+        """``sd`` with every tensor in the live model's dtype.  The reference's ``ensembling`` writes ``num_batches_tracked`` as float
+        (``long * 1/n``, code/learner.py:319); its integral value is kept."""
+        own = self.model.state_dict()
+        out = {}
+        for k, v in sd.items():
+            name = k[len("module."):] if k.startswith("module.") else k
+            out[name] = v.to(own[name].dtype) if name in own and torch.is_tensor(v) else v
+        return out
+
+    def load_checkpoint_epoch(self, checkpoints_dir, epoch):
+        """Load ``model<epoch>.tar`` (code/learner.py:450-465)."""
+        model_path = checkpoints_dir + "/model" + str(epoch) + ".tar"
+        assert os.path.exists(model_path), f"{model_path} does not exist, can not load the checkpoint of specific epoch."
+        checkpoint = torch.load(model_path, map_location="cpu", weights_only=False)
+        assert epoch == checkpoint["epoch"], "loaded epoch wrong~"
+        self._load_model_state(self._cast_to_live(checkpoint["model"]), as_all_state=True)
+        print(f"Model of {epoch} epoch loaded.")
+
+    def load_checkpoint_ensemble(self, checkpoints_dir):
+        """Load ``ensemble_model.tar`` = {'epoch': [..], 'model': sd}, as ``ensembling`` here or the reference's writes it
+        (code/learner.py:467-479); -> the list of averaged epochs."""
+        model_path = checkpoints_dir + "/ensemble_model.tar"
+        assert os.path.exists(model_path), f"{model_path} does not exist, can not load the checkpoint of ensembled model."
+        checkpoint = torch.load(model_path, map_location="cpu", weights_only=False)
+        epoch = checkpoint["epoch"]
+        self._load_model_state(self._cast_to_live(checkpoint["model"]), as_all_state=True)
+        print(f"Model of {epoch} epoch loaded.")
+        return epoch
+
 
 class STFTLearner(Learner):
     """Learner for models fed with STFTs of the microphone signals (code/learner.py:488-553)."""
@@ -542,3 +572,17 @@ class STFTLearner(Learner):
 
     def evaluate(self, pred_batch, gt_batch):
         return torch.mean(torch.abs(pred_batch.contiguous().detach() - gt_batch.contiguous().detach()))
+
+    def mae_wotrain(self, dataset_train, dataset_test):
+        """MAE of the test (and training) targets when the mean of the training targets is the prediction (code/learner.py:655-686)
+        -> (mae_test, min_test, max_test, mae, mean, min, max) as floats.  Label arithmetic only, in f32 like the reference: it reads the
+        second item of every batch, launches no kernel and works on a learner that was never moved to a GPU."""
+        def targets(dataset):
+            tar = [self.get_tar_batch(torch.as_tensor(batch[1][self.task]).to(self.device)) for batch in dataset]
+            return torch.cat(tar, dim=0).float()
+        gt = targets(dataset_train)
+        mean = torch.mean(gt).item()
+        mae = torch.mean(torch.abs(gt - mean)).item()
+        gt_test = targets(dataset_test)
+        mae_test = torch.mean(torch.abs(gt_test - mean)).item()
+        return mae_test, torch.min(gt_test).item(), torch.max(gt_test).item(), mae, mean, torch.min(gt).item(), torch.max(gt).item()

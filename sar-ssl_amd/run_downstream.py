@@ -1,11 +1,14 @@
-"""Downstream entry point with the reference's command line (code/run_downstream.py), simulated-data training branch:
+"""Downstream entry point with the reference's command line (code/run_downstream.py), simulated-data branch, both stages:
 
     python run_downstream.py --ds-train --simu-exp --ds-trainmode finetune --ds-task TDOA --ds-nsimroom 8 --time <pretrain tag>
+    python run_downstream.py --ds-test --simu-exp --test-mode cal_metric --ds-trainmode finetune --ds-task TDOA --ds-nsimroom 8 --time <tag>
 
-Per task and per (trial, batch size, learning rate) of the sweep: train / validate / test every epoch, early stopping on the
+``--ds-train``.  Per task and per (trial, batch size, learning rate) of the sweep: train / validate / test every epoch, early stopping on the
 smoothed validation loss with one learning-rate decay (code/run_downstream.py:262-308), ensembling of the last five epochs up to
 the best one, final test on the large test set, results to the same ``*-lr_bs_tri_result.mat`` file.  Scalars go to a JSONL log
 (tensorboardX is absent here).  Same model code, kernels and learner as pretraining, at T = 1.04 s (nt = 64) for TDOA.
+
+``--ds-test`` (code/run_downstream.py:380-534) evaluates what ``--ds-train`` left, see ``ds_test_stage``.
 """
 import copy
 import json
@@ -15,6 +18,141 @@ import sys
 _HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(_HERE))
 import sarssl_boot  # noqa: E402,F401
+
+
+TEST_BS = 16                                            # code/run_downstream.py:389
+
+
+def ds_test_lr_index(lr_set):
+    """Index into the sweep's learning rates of the run the test stage reads: the reference hard-wires ``lr_idx = 1``
+    (code/run_downstream.py:386).  The build-side ``--ds-lr-set`` may hold one entry only, so: ``min(1, len(lr_set) - 1)``."""
+    return min(1, len(lr_set) - 1)
+
+
+def run_dir(dirs, trainmode, task, num, lr, bs, trial_idx):
+    """Directory of one run of the sweep, named as the training branch names it."""
+    return (dirs["log_task_" + trainmode].replace("TASK", task).replace("NUM", str(num)).replace("LR", str(lr))
+            .replace("BAS", str(bs)).replace("TRI", str(trial_idx)))
+
+
+def ds_test_data_num(test_mode, num, eval_num=None):
+    """Sizes of the two sets (code/run_downstream.py:414-417); ``--ds-eval-num`` replaces the test set's, as for the training
+    branch's evaluation sets."""
+    n = {"train": num, "test": 4000} if test_mode in ("cal_metric", "cal_metric_wo_info") else {"train": 8000, "test": 8000}
+    if eval_num:
+        n["test"] = eval_num
+    return n
+
+
+def save_embed(result_dir, stage, run, vis, seed):
+    """``embed_<stage>_<run>.mat`` = {'embed' (n, d) f32, 'label' (n, 1)}, always; the reference's ``tsne_vis_<stage>_<run>.png`` / ``.mat``
+    (code/run_downstream.py:493-503) when sklearn and matplotlib import, else one line saying so.  -> the names of the files written."""
+    import numpy as np
+    import scipy.io
+    from sar_ssl_amd.common.utils import set_random_seed, vis_TSNE
+    embed = vis["embed"].detach().float().cpu().numpy()
+    label = vis["label"].detach().float().cpu().numpy()
+    files = ["embed_%s_%s.mat" % (stage, run)]
+    scipy.io.savemat(os.path.join(result_dir, files[0]), {"embed": embed, "label": label})
+    set_random_seed(seed)
+    try:
+        plt, data_vis = vis_TSNE(data=embed, label=label)
+    except ImportError as e:
+        print("t-SNE files of the %s set skipped (%s); %s holds the embeddings" % (stage, e, files[0]))
+        return files
+    stem = "tsne_vis_%s_%s" % (stage, run)
+    plt.savefig(os.path.join(result_dir, stem + ".png"))
+    plt.close()
+    scipy.io.savemat(os.path.join(result_dir, stem + ".mat"), {"data": data_vis["data"], "label": data_vis["label"]})
+    return files + [stem + ".png", stem + ".mat"]
+
+
+def ds_test_stage(args, dirs, net, seeds, selecting, stft):
+    """``--ds-test --simu-exp`` (code/run_downstream.py:380-534).  Per task, the run at ``bs_set[0]`` and ``lr_set[ds_test_lr_index(lr_set)]``
+    of every trial, on the trial's training directories and the simulated test set, batches of 16 in file order:
+
+      cal_metric           load ensemble_model.tar, test_epoch on the test set: loss and MAE per trial and their mean
+      cal_metric_wo_info   no model: the MAE when the mean training target is the prediction (mae_wotrain); mean of the MAEs and
+                           means, min of the minima, max of the maxima over the trials
+      vis_embed            load ensemble_model.tar, test_epoch(return_vis=True) on both sets: embed_{train,test}_<run>.mat and, with
+                           sklearn and matplotlib, tsne_vis_{train,test}_<run>.{png,mat}
+
+    All under ``exp/<TASK>/<time>/test_result/`` (created here; the reference assumes it), with one record per task and mode,
+    ``<test_mode>-<trainmode>.json`` = {task, test_mode, lr, bs, trials: [..], mean: {..}}.  One process on the first listed GPU: the stage only
+    evaluates and has no data-parallel form.  The evaluation is ``Learner.test_epoch``: full batches replay the captured evaluation step, the
+    ragged last one takes its launch-by-launch twin.  Not copied from the reference: its final summary, which formats a list with
+    ``{:.4f}`` and raises (the per-task values are printed instead), and its ``'valsim' in dirs[...]`` special case, which never applies
+    to the simulated layout."""
+    import numpy as np
+    import torch
+    from sar_ssl_amd import dataset as at_dataset, learner as at_learner
+    from sar_ssl_amd.common.utils import set_seed, set_random_seed
+
+    print("Downstream test stage!", args.ds_trainmode)
+    print("Number of simulated rooms: ", args.ds_nsimroom)
+    mode, fs = args.test_mode, stft["fs"]
+    summary = {}
+    for task in args.ds_task:
+        set_seed(args.seed)
+        st = args.ds_setting[task]
+        nepoch, num, bs_set, lr_set, ntrials = st["nepoch"], st["num"], st["bs_set"], st["lr_set"], st["ntrial"]
+        lr_init, bs = lr_set[ds_test_lr_index(lr_set)], bs_set[0]
+        data_num = ds_test_data_num(mode, num, args.ds_eval_num)
+        print(task, "nepoch=", nepoch, "num=", num, "lr=", lr_init, "bs=", bs)
+        result_dir = os.path.join(dirs["log_task"].replace("TASK", task), "test_result")
+        os.makedirs(result_dir, exist_ok=True)
+        trials = []
+        for trial_idx in range(ntrials):
+            print("trial(or cross_validation_dataset)_idx=", trial_idx, "ntrial=", ntrials)
+            task_dir = run_dir(dirs, args.ds_trainmode, task, num, lr_init, bs, trial_idx)
+            run = os.path.basename(task_dir)
+            datasets = {}
+            for stage in ("train", "test"):
+                key = "micsig_" + stage + "_simu"
+                data_dir = dirs[key][trial_idx] if stage == "train" else dirs[key]
+                datasets[stage] = at_dataset.FixMicSigDataset(data_dir=data_dir, load_anno=True, load_dp=False, fs=fs,
+                                                              dataset_sz=data_num[stage], transforms=[selecting])
+            kwargs = {"num_workers": args.workers, "pin_memory": True}
+            dl_train = torch.utils.data.DataLoader(datasets["train"], batch_size=TEST_BS, shuffle=False, **kwargs)
+            dl_test = torch.utils.data.DataLoader(datasets["test"], batch_size=TEST_BS, shuffle=False, **kwargs)
+            learner = at_learner.STFTLearner(net, win_len=stft["win_len"], win_shift_ratio=stft["win_shift_ratio"], nfft=stft["nfft"],
+                                             fre_used_ratio=stft["fre_used_ratio"], fs=fs, task=task, ch_mode="M")
+            learner.cuda()
+            if args.use_amp:
+                learner.amp()
+            rec = {"trial": trial_idx, "run": run}
+            if mode == "cal_metric":
+                rec["epochs"] = [int(e) for e in learner.load_checkpoint_ensemble(checkpoints_dir=task_dir)]
+                set_random_seed(seeds["test"])
+                loss_test, metric_test = learner.test_epoch(dl_test, return_metric=True, return_vis=False)
+                rec.update(loss=float(loss_test), metric=float(metric_test))
+                print("{} estimation, Test loss: {:.4f}, Test metric: {:.4f}".format(task, rec["loss"], rec["metric"]))
+            elif mode == "vis_embed":
+                rec["epochs"] = [int(e) for e in learner.load_checkpoint_ensemble(checkpoints_dir=task_dir)]
+                set_random_seed(seeds["train"])
+                loss_train, metric_train, vis_train = learner.test_epoch(dl_train, return_metric=True, return_vis=True)
+                set_random_seed(seeds["test"])
+                loss_test, metric_test, vis_test = learner.test_epoch(dl_test, return_metric=True, return_vis=True)
+                rec.update(loss_train=float(loss_train), metric_train=float(metric_train), loss=float(loss_test), metric=float(metric_test))
+                rec["files"] = (save_embed(result_dir, "train", run, vis_train, seeds["train"])
+                                + save_embed(result_dir, "test", run, vis_test, seeds["test"]))
+            else:
+                names = ("mae_test", "min_test", "max_test", "mae_train", "mean_train", "min_train", "max_train")
+                rec.update(zip(names, learner.mae_wotrain(dl_train, dl_test)))
+                print("Trial: {}, Data MAE: {:.4f}".format(trial_idx, rec["mae_test"]))
+            trials.append(rec)
+        how = {"min_test": np.min, "min_train": np.min, "max_test": np.max, "max_train": np.max}
+        mean = {k: float(how.get(k, np.mean)([t[k] for t in trials])) for k, v in trials[0].items() if isinstance(v, float)}
+        if mode == "cal_metric_wo_info":
+            print("Data MAE: {:.4f}".format(mean["mae_test"]))
+        else:
+            print("{} estimation, Test loss: {:.4f}, Test metric: {:.4f}".format(task, mean["loss"], mean["metric"]))
+        with open(os.path.join(result_dir, "%s-%s.json" % (mode, args.ds_trainmode)), "w") as f:
+            json.dump({"task": task, "test_mode": mode, "lr": lr_init, "bs": bs, "trials": trials, "mean": mean}, f, indent=1)
+        summary[task] = mean
+    print("Task: ", args.ds_task)
+    for task, mean in summary.items():
+        print(task, " ".join("{}: {:.4f}".format(k, v) for k, v in mean.items()))
 
 
 def main(argv=None):
@@ -33,8 +171,9 @@ def main(argv=None):
 
     if args.no_cuda or not torch.cuda.is_available():
         raise SystemExit("run_downstream.py (sar_ssl_amd) needs an MI355X GPU: the HIP path has no CPU fallback")
-    if not args.ds_train:
-        raise SystemExit("only `--ds-train --simu-exp` is implemented on this path")
+    if not args.simu_exp:
+        raise SystemExit("the real-data branch (--ds-real-sim-ratio, without --simu-exp) is not implemented on this path: "
+                         "`--ds-train --simu-exp` and `--ds-test --simu-exp` are")
     device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
     set_seed(args.seed)
     assert args.source_state == "static", "Source state model unrecognized~"
@@ -49,6 +188,9 @@ def main(argv=None):
                           downstream_head=args.ds_head, downstream_embed=args.ds_embed, downstream_dlabel=1)
     nparam, nparam_sum = get_nparams(net, param_key_list=["spec_encoder", "spat_encoder", "mlp_head"])
     print("duration:", T, "s; nt, nf:", nt, nf, "; # Parameters (M):", round(nparam_sum, 2))
+    if args.ds_test:
+        return ds_test_stage(args, dirs, net, seeds, selecting,
+                          dict(win_len=win_len, win_shift_ratio=win_shift_ratio, nfft=nfft, fre_used_ratio=fre_used_ratio, fs=fs))
 
     log_dir = "log_task_" + args.ds_trainmode
     init_state_dict = copy.deepcopy(net.state_dict())
