@@ -77,6 +77,29 @@ int sarssl_mask_sample(unsigned int* mt, int* pos, int nbatch, int npatch, int n
 long sarssl_istft_workspace_bytes(int nb, int nch, int nt);
 int sarssl_istft(const float* spec, int nb, int nch, int nt, int win_len, int hop, int nfft, int center, float* frames_ws,
                  float* sig, void* stream);
+/* ---- microphone signals from stored RIRs (csrc/rirmix.hip): the per-item CPU work of RandomMicSigFromRIRDataset (code/dataset.py:287-382;
+ *      code/data_generation/utils_simu_rir_sig.py:1203-1237, gen_sig_from_real_rir.py:185-304), a batch per call.
+ *      src (B, ns) f32; rir (B, nch, lmax) f32 with rir_len int[B]; nch 1..8.  Direct path: EITHER rir_dp (B, nch, ldmax) with dp_len int[B],
+ *      OR rir_dp = dp_len = NULL, ldmax = 0 and a window half-width n0 >= 0 - then the direct-path RIR is rir kept where
+ *      nd - n0 <= n <= nd + n0, nd = per channel the first index of the signed maximum of rir[:rir_len] (np.argmax).
+ *      noise (B, ns, nch) f32 or NULL (= zero noise); snr_db, gain f32[B]; out (B, ns, nch) f32:
+ *        clean = src * rir, dp = src * rir_dp (first ns samples), g = sqrt(P_dp / 10^(snr/10)) / (sqrt(P_n) + 1e-10) with P = mean power,
+ *        mic = clean + g noise, out = mic / max(max|mic|, max|dp|) * gain.
+ *      Uniformly partitioned overlap-save (256-sample blocks, 512-point transforms); partitions past rir_len / outside the direct-path
+ *      window are skipped on the device.  ws: sarssl_rir_mix_workspace_bytes(nb, ns, nch, lmax, ldmax) bytes (-1: unsupported shape). */
+long sarssl_rir_mix_workspace_bytes(int nb, long ns, int nch, int lmax, int ldmax);
+int sarssl_rir_mix(const float* src, const float* rir, const int* rir_len, const float* rir_dp, const int* dp_len, int n0,
+                   const float* noise, const float* snr_db, const float* gain, int nb, long ns, int nch, int lmax, int ldmax, void* ws,
+                   float* out, void* stream);
+/*      diffuse noise field (code/data_generation/utils_noise.py:141-253): white (B, ns, M) f32 -> out (B, ns, M) f32 through
+ *      scipy.signal.stft / istft's conventions (periodic Hann 256, hop 64, 128 zeros on both sides, division by the actual window-square
+ *      sum) with the per-bin mix X_n = sum_m C[f][m][n] N_m, then out = noise / (max(noise) + 1e-8) (signed maximum over the item).
+ *      C (B, 129, M, M) f32: real mixing table, row 0 zero.  M 1..8; ns % 64 != 0 is refused (-1) and nothing is launched. */
+long sarssl_diffuse_noise_workspace_bytes(int nb, long ns, int m);
+int sarssl_diffuse_noise(const float* white, const float* C, int nb, long ns, int m, void* ws, float* out, void* stream);
+/*      out (B, ns, M) f32 standard normal values: Box-Muller over the library's counter hash, a pure function of
+ *      (seed, item0 + b, sample, channel).  NOT numpy's stream - for parity with the reference pass host-drawn noise instead. */
+int sarssl_gauss_fill(float* out, int nb, long ns, int m, unsigned long long seed, int item0, void* stream);
 
 /* ---- generic batched MFMA GEMM with fused epilogue: nn.Linear / Conv1d(k=1) / patch conv / attention bmm
  *      (code/common/conformer/modules.py:35-48, feed_forward.py:47-54, attention.py:82-103, convolution.py:138,143,

@@ -1,5 +1,6 @@
 """Seeding, parameter counting and the cosine learning-rate schedule (code/common/utils.py:39-56, 59-72, 108-139)."""
 import json
+import os
 import random
 
 import numpy as np
@@ -48,6 +49,20 @@ def create_learning_rate_schedule(total_steps, base, decay_type, warmup_steps, l
             lr = lr * np.minimum(1.0, step / warmup_steps)
         return np.asarray(lr, dtype=np.float32)
     return step_fn
+
+
+def cross_validation_datadir(data_dir, sort=False):
+    """Leave-one-room-out splits of a directory of rooms (code/common/utils.py:249-277): one trial per room in ``os.listdir`` order with
+    that room as the test set, one of the others drawn with ``random.sample`` as the validation set, the rest for training.
+    sort=True: rooms in sorted order instead of the file system's.  -> [{'train': [dirs], 'val': [dir], 'test': [dir]}]."""
+    room_names = sorted(os.listdir(data_dir)) if sort else os.listdir(data_dir)
+    dirs = []
+    for test_room_name in room_names:
+        trainval = [r for r in room_names if r != test_room_name]
+        val_room_name = random.sample(trainval, 1)[0]
+        dirs += [{"train": [data_dir + "/" + r for r in trainval if r != val_room_name], "val": [data_dir + "/" + val_room_name],
+                  "test": [data_dir + "/" + test_room_name]}]
+    return dirs
 
 
 def vis_TSNE(data, label):

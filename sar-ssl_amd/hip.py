@@ -751,6 +751,69 @@ def istft(spec, center=False, win_len=512, hop=256, nfft=512):
     return sig
 
 
+# ---- microphone signals from stored RIRs (csrc/rirmix.hip) ---------------------------------------------------------------------------
+def _i32(t):
+    assert t.dtype == torch.int32 and t.is_contiguous()
+    return t
+
+
+def rir_mix(src, rir, rir_len, snr_db, gain, *, rir_dp=None, dp_len=None, n0=None, noise=None, out=None):
+    """src (B, Ns), rir (B, nch, Lmax) + rir_len int32 (B), the direct path as (rir_dp (B, nch, Ldmax) + dp_len) or a window half-width
+    ``n0`` around each channel's signed maximum, noise (B, Ns, nch) or None, snr_db / gain f32 (B) -> (B, Ns, nch) f32 (the layout
+    data_preprocess takes).  See include/sarssl_hip.h for the arithmetic."""
+    _need_cuda(src, rir, rir_len, rir_dp, dp_len, noise, snr_db, gain, out)
+    if (rir_dp is None) == (n0 is None):
+        raise _lib.SarsslHipError("rir_mix: give either rir_dp + dp_len or n0")
+    B, Ns = src.shape
+    _, nch, Lmax = rir.shape
+    Ldmax = rir_dp.shape[2] if rir_dp is not None else 0
+    for t in (src, rir, rir_dp, noise, snr_db, gain):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous())
+    assert rir.shape[0] == B and rir_len.shape == (B,) and snr_db.shape == (B,) and gain.shape == (B,)
+    assert noise is None or noise.shape == (B, Ns, nch)
+    assert rir_dp is None or (rir_dp.shape[:2] == (B, nch) and dp_len.shape == (B,))
+    fn = _lib.lib().sarssl_rir_mix_workspace_bytes
+    fn.restype = c_long
+    nbytes = fn(c_int(B), c_long(Ns), c_int(nch), c_int(Lmax), c_int(Ldmax))
+    if nbytes < 0:
+        raise _lib.SarsslHipError("rir_mix: unsupported shape (B=%d, Ns=%d, nch=%d, Lmax=%d)" % (B, Ns, nch, Lmax))
+    ws = workspace(nbytes, src.device, "rir_mix")
+    if out is None:
+        out = torch.empty((B, Ns, nch), dtype=torch.float32, device=src.device)
+    assert out.shape == (B, Ns, nch) and out.dtype == torch.float32 and out.is_contiguous()
+    _lib.call("sarssl_rir_mix", _p(src), _p(rir), _p(_i32(rir_len)), _p(rir_dp), _p(_i32(dp_len) if dp_len is not None else None),
+              c_int(n0 if n0 is not None else 0), _p(noise), _p(snr_db), _p(gain), c_int(B), c_long(Ns), c_int(nch), c_int(Lmax),
+              c_int(Ldmax), _p(ws), _p(out), _stream())
+    return out
+
+
+def diffuse_noise(white, C, out=None):
+    """white (B, Ns, M) f32, C (B, 129, M, M) f32 real mixing table -> the diffuse field (B, Ns, M), divided by its signed maximum + 1e-8.
+    Ns % 64 != 0 raises and leaves ``out`` untouched."""
+    _need_cuda(white, C, out)
+    B, Ns, M = white.shape
+    assert white.dtype == torch.float32 and white.is_contiguous() and C.dtype == torch.float32 and C.is_contiguous()
+    assert C.shape == (B, 129, M, M)
+    if out is None:
+        out = torch.empty_like(white)
+    assert out.shape == white.shape and out.dtype == torch.float32 and out.is_contiguous()
+    fn = _lib.lib().sarssl_diffuse_noise_workspace_bytes
+    fn.restype = c_long
+    nbytes = fn(c_int(B), c_long(Ns), c_int(M))
+    ws = workspace(max(nbytes, 8), white.device, "diffuse_noise")          # (a refused shape: the call below reports it)
+    _lib.call("sarssl_diffuse_noise", _p(white), _p(C), c_int(B), c_long(Ns), c_int(M), _p(ws), _p(out), _stream())
+    return out
+
+
+def gauss_fill(out, seed, item0=0):
+    """Fill out (B, Ns, M) f32 with standard normal values keyed by (seed, item0 + b, sample, channel).  NOT numpy's stream."""
+    _need_cuda(out)
+    B, Ns, M = out.shape
+    assert out.dtype == torch.float32 and out.is_contiguous()
+    _lib.call("sarssl_gauss_fill", _p(out), c_int(B), c_long(Ns), c_int(M), c_ulonglong(seed), c_int(item0), _stream())
+    return out
+
+
 # ------------------------------------------------------------------------------------------------
 # conv stem
 def _f32ws(n, device, tag):

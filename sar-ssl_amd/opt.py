@@ -1,5 +1,6 @@
 """Command-line options and directory layouts of the entry points: same flag names / defaults as ``opt_pretrain``
-(code/opt.py:6-115) and ``opt_downstream`` (code/opt.py:117-320, simulated-data branch) in the reference."""
+(code/opt.py:6-115) and ``opt_downstream`` (code/opt.py:117-320: the simulated-data branch and, for T60 / DRR / C50 / ABS, the real-data
+branch) in the reference."""
 import argparse
 import os
 import time
@@ -59,7 +60,8 @@ class opt_pretrain():
 
 
 class opt_downstream():
-    """Downstream (TDOA / DRR / C50 / T60 / ABS regression on the pretrained encoders) options, simulated-data branch.
+    """Downstream (TDOA / DRR / C50 / T60 / ABS regression on the pretrained encoders) options: the simulated-data branch (--simu-exp) and
+    the real-data branch of the room-acoustics tasks (signals synthesised from stored RIRs, rirsynth.py).
     ``--ds-nepoch/--ds-num/--ds-lr-set/--ds-bs-set/--ds-eval-num`` are build-side overrides of the reference's hard-wired sweep
     (code/opt.py:197-209) so that a short run is possible; left unset, the reference's values apply."""
 
@@ -69,7 +71,7 @@ class opt_downstream():
         self.work_dir_local = self.work_dir
         self.acoustic_setting = {"sound_speed": 343.0, "fs": 16000, "snr_range": [15, 30], "nmic": 2, "mic_dist_range": [0.03, 0.20]}
         self.extra_info, self.ds_token, self.ds_head, self.ds_embed, self.ds_nsimroom = "", "", "", "", 0
-        self.simu_exp, self.ntrail = True, 1
+        self.simu_exp, self.ntrail, self.ds_specifics = True, 1, {}
 
     def parse(self, argv=None):
         p = argparse.ArgumentParser(description="Self-supervised learing for multi-channel audio processing")
@@ -107,10 +109,10 @@ class opt_downstream():
         self.work_dir = os.path.abspath(os.path.expanduser(args.work_dir))
         self.work_dir_local = self.work_dir
         self.ds_token, self.ds_head, self.ds_embed, self.ds_nsimroom = args.ds_token, args.ds_head, args.ds_embed, args.ds_nsimroom
-        args.ds_specifics = {"task": args.ds_task}
+        self.ds_specifics = args.ds_specifics = {"task": args.ds_task}
         args.acoustic_setting = self.acoustic_setting
         if not self.simu_exp:
-            raise SystemExit("only the simulated-data branch (--simu-exp) of the downstream stage is implemented")
+            return self._parse_real(args)
         bs_set = args.ds_bs_set or [8]
         lr_set = args.ds_lr_set or [0.001, 0.0005, 0.0001, 0.00005]
         nepoch = args.ds_nepoch or 200
@@ -122,18 +124,52 @@ class opt_downstream():
         self.extra_info = "R" + str(args.ds_nsimroom)
         return args
 
+    REFUSE_TDOA_REAL = ("the LOCATA TDOA real-data branch (RandomMicSigDataset, code/run_downstream.py:213-230) is not built: it is file "
+                        "loading only and needs its own corpus layout.  Without --simu-exp the tasks T60, DRR, C50 and ABS run (microphone "
+                        "signals synthesised from stored RIRs); TDOA runs with --simu-exp")
+    REFUSE_TEST_REAL = ("--ds-test is simulated-only, as in the reference (code/run_downstream.py:383 asserts --simu-exp): "
+                        "`--ds-test --simu-exp` evaluates what `--ds-train --simu-exp` left")
+
+    def _parse_real(self, args):
+        """The reference's real-data settings (code/opt.py:189-256): batch 16, two learning rates, the training-set size by train mode and
+        real / simulated ratio; the cross-validation trials are counted by run_downstream from the rooms on disk."""
+        if args.ds_test:
+            raise SystemExit(self.REFUSE_TEST_REAL)
+        if "TDOA" in args.ds_task:
+            raise SystemExit(self.REFUSE_TDOA_REAL)
+        ratio = list(args.ds_real_sim_ratio)
+        assert ratio in [[0, 1], [1, 0], [1, 1]], ratio                                          # code/dataset.py:358
+        self.ds_specifics.update(data="real_ace", real_sim_ratio=ratio)
+        table = {"finetune": {(1, 0): 1600, (1, 1): 3200, (0, 1): 32000}, "scratchLOW": {(1, 0): 1600, (1, 1): 16000, (0, 1): 32000}}
+        if args.ds_trainmode not in table:
+            raise Exception("Undefined trainmode for the number of real-world training data")
+        num = args.ds_num if args.ds_num is not None else table[args.ds_trainmode][tuple(ratio)]
+        st = {"nepoch": args.ds_nepoch or 200, "lr_set": args.ds_lr_set or [0.001, 0.0001], "bs_set": args.ds_bs_set or [16], "ntrial": 1}
+        args.ds_setting = {t: dict(st, num=num) for t in ("DRR", "C50", "T60", "ABS")}
+        args.ds_setting["TDOA"] = dict(st, num=args.ds_num if args.ds_num is not None else 80000)
+        return args
+
     def dir(self):
         work_dir = self.work_dir
         dirs = {"code": work_dir + "/SAR-SSL/code", "data": self.work_dir_local + "/data",
                 "gerdata": self.work_dir_local + "/SAR-SSL/data", "exp": work_dir + "/SAR-SSL/exp"}
-        dirs["micsig_train_simu"] = []
-        train_dir = dirs["gerdata"] + "/MicSig/simu_ds/train"
-        for trail_idx in range(self.ntrail):
-            dirs["micsig_train_simu"] += [[os.path.join(train_dir, "R" + str(trail_idx * self.ds_nsimroom + r + 1))
-                                           for r in range(self.ds_nsimroom)]]
-        dirs["micsig_val_simu"] = dirs["gerdata"] + "/MicSig/simu_ds/val"
-        dirs["micsig_test_simu"] = dirs["gerdata"] + "/MicSig/simu_ds/test"
-        flag = "sim_"
+        if self.simu_exp:
+            dirs["micsig_train_simu"] = []
+            train_dir = dirs["gerdata"] + "/MicSig/simu_ds/train"
+            for trail_idx in range(self.ntrail):
+                dirs["micsig_train_simu"] += [[os.path.join(train_dir, "R" + str(trail_idx * self.ds_nsimroom + r + 1))
+                                               for r in range(self.ds_nsimroom)]]
+            dirs["micsig_val_simu"] = dirs["gerdata"] + "/MicSig/simu_ds/val"
+            dirs["micsig_test_simu"] = dirs["gerdata"] + "/MicSig/simu_ds/test"
+            flag = "sim_"
+        else:                                                                                    # code/opt.py:273-275, 298-308
+            dirs["srcsig_train"] = dirs["data"] + "/SrcSig/wsj0/tr"
+            dirs["srcsig_val"] = dirs["data"] + "/SrcSig/wsj0/dt"
+            dirs["srcsig_test"] = dirs["data"] + "/SrcSig/wsj0/et"
+            dirs["rir_real"] = dirs["gerdata"] + "/RIR/real/ACE"
+            dirs["rir_train_simu"] = dirs["gerdata"] + "/RIR/simu/train"
+            r = self.ds_specifics["real_sim_ratio"]
+            flag = "real_train" + str(r[0]) + "real" + str(r[1]) + "sim_valreal"
         dirs["log_pretrain"] = dirs["exp"] + "/pretrain/" + self.time
         dirs["log_task"] = dirs["exp"] + "/TASK/" + self.time
         for mode, name in (("scratchLOW", "scratchlow"), ("finetune", "finetune"), ("lineareval", "lineareval")):

@@ -45,6 +45,16 @@ GATES = {
     "fp32_1pass": dict(loss=2e-3, per_bin_max=3e-2, per_bin_rms=1e-2, grad_norm=6e-2, bn_running=5e-3, curve100=None, measured=dict()),
 }
 
+# The RIR renderer (csrc/rirmix.hip) against the f64 numpy / scipy restatement of an item (rirsynth.restate_*), max |difference| of the
+# peak-normalised outputs = error relative to full scale (tests/test_gpu_rirmix.py).  cap: half a PCM-16 step, the quantisation the
+# simulated branch's stored segments already carry - a condition, not a measurement.  gate: 4x the largest distance measured on an MI355X
+# over the test's shapes, rounded up to one digit (profiles/rirmix.txt).
+# restatement_vs_f20: the same distance between the f64 restatement and fixture F20 of the real reference (mixed f32 / f64 arithmetic, stored
+# as f32), measured on the CPU (tests/test_rirsynth_cpu.py prints it), x4, one digit; the renderer is held to gate + restatement_vs_f20
+# against F20 (triangle inequality).
+RIRMIX = dict(gate=2e-6, cap=1.5e-5, restatement_vs_f20=8e-7,
+              measured=dict(rir_mix=2.8e-7, diffuse_noise=2.9e-7, loader=3.1e-7, restatement_vs_f20=1.9e-7))
+
 
 def parity_class(precision):
     """What bench.py prints for the timed mode."""

@@ -1,7 +1,13 @@
-"""Downstream entry point with the reference's command line (code/run_downstream.py), simulated-data branch, both stages:
+"""Downstream entry point with the reference's command line (code/run_downstream.py): the simulated-data branch in both stages, and
+the real-data training branch of the room-acoustics tasks:
 
     python run_downstream.py --ds-train --simu-exp --ds-trainmode finetune --ds-task TDOA --ds-nsimroom 8 --time <pretrain tag>
     python run_downstream.py --ds-test --simu-exp --test-mode cal_metric --ds-trainmode finetune --ds-task TDOA --ds-nsimroom 8 --time <tag>
+    python run_downstream.py --ds-train --ds-trainmode finetune --ds-task T60 --ds-real-sim-ratio 1 1 --time <pretrain tag>
+
+Without ``--simu-exp`` (T60 / DRR / C50 / ABS) every item is synthesised on the GPU from stored RIRs (``RealData``, rirsynth.py); one
+cross-validation trial per measured room; everything after the loaders is the same sweep.  Out of scope and refused by the option parser:
+the LOCATA TDOA real-data branch and ``--ds-test`` without ``--simu-exp`` (opt.py).
 
 ``--ds-train``.  Per task and per (trial, batch size, learning rate) of the sweep: train / validate / test every epoch, early stopping on the
 smoothed validation loss with one learning-rate decay (code/run_downstream.py:262-308), ensembling of the last five epochs up to
@@ -155,6 +161,43 @@ def ds_test_stage(args, dirs, net, seeds, selecting, stft):
         print(task, " ".join("{}: {:.4f}".format(k, v) for k, v in mean.items()))
 
 
+class RealData:
+    """The real-data branch's datasets (code/run_downstream.py:107-110, 132-134, 191-212) for T60 / DRR / C50 / ABS: per task the
+    cross-validation trials over the rooms of ``dirs['rir_real']``, per (trial, stage) a rirsynth.RirSynthLoader - training at
+    ``--ds-real-sim-ratio`` with the simulated RIRs of ``dirs['rir_train_simu']``, validation and test measured-only, sources from
+    ``dirs['srcsig_<stage>']``, seeds[stage] as the datasets' seed.  Banks are built once per directory set and stay resident."""
+
+    def __init__(self, args, dirs, T, fs, seeds, device):
+        self.args, self.dirs, self.T, self.fs, self.seeds, self.device = args, dirs, T, fs, seeds, device
+        self.ratios = {"train": list(args.ds_specifics["real_sim_ratio"]), "val": [1, 0], "test": [1, 0]}
+        self.rooms, self._measured, self._sources, self._simulated = None, {}, {}, None
+
+    def new_task(self):
+        from sar_ssl_amd.common.utils import cross_validation_datadir
+        self.rooms = cross_validation_datadir(self.dirs["rir_real"])
+        return len(self.rooms)
+
+    def loader(self, trial_idx, stage, dataset_sz, batch_size):
+        from sar_ssl_amd import rirsynth
+        st = stage.split("_")[0]
+        ratio, ac = self.ratios[st], self.args.acoustic_setting
+        measured = simulated = None
+        if ratio[0]:
+            key = tuple(self.rooms[trial_idx][st])
+            if key not in self._measured:
+                self._measured[key] = rirsynth.MeasuredBank(list(key), fs=self.fs)
+            measured = self._measured[key]
+        if ratio[1]:
+            if self._simulated is None:
+                self._simulated = rirsynth.SimulatedBank(self.dirs["rir_" + st + "_simu"], fs=self.fs, c=ac["sound_speed"])
+            simulated = self._simulated
+        if st not in self._sources:
+            self._sources[st] = rirsynth.SourceBank(self.dirs["srcsig_" + st], fs=self.fs)
+        return rirsynth.RirSynthLoader(measured, simulated, self._sources[st], dataset_sz=dataset_sz, batch_size=batch_size, T=self.T, fs=self.fs,
+                                       nmic=ac["nmic"], snr_range=ac["snr_range"], real_sim_ratio=ratio, seed=self.seeds[st],
+                                       noise="device", device=self.device, c=ac["sound_speed"])
+
+
 def main(argv=None):
     from sar_ssl_amd.opt import opt_downstream
     opts = opt_downstream()
@@ -171,9 +214,6 @@ def main(argv=None):
 
     if args.no_cuda or not torch.cuda.is_available():
         raise SystemExit("run_downstream.py (sar_ssl_amd) needs an MI355X GPU: the HIP path has no CPU fallback")
-    if not args.simu_exp:
-        raise SystemExit("the real-data branch (--ds-real-sim-ratio, without --simu-exp) is not implemented on this path: "
-                         "`--ds-train --simu-exp` and `--ds-test --simu-exp` are")
     device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
     set_seed(args.seed)
     assert args.source_state == "static", "Source state model unrecognized~"
@@ -194,11 +234,14 @@ def main(argv=None):
 
     log_dir = "log_task_" + args.ds_trainmode
     init_state_dict = copy.deepcopy(net.state_dict())
+    real = None if args.simu_exp else RealData(args, dirs, T, fs, seeds, device)
     for task in args.ds_task:
         set_seed(args.seed)
         task_time_dir = dirs["log_task"].replace("TASK", task)
         st = args.ds_setting[task]
         nepoch, num, bs_set, lr_set, ntrials = st["nepoch"], st["num"], st["bs_set"], st["lr_set"], st["ntrial"]
+        if real is not None:
+            ntrials = real.new_task()                       # one trial per room (code/run_downstream.py:132-134)
         neval = args.ds_eval_num
         data_num = {"train": num, "val": neval or 1000, "test": neval or 1000, "test_large": neval or 4000}
         stages = ["train", "val", "test", "test_large"]
@@ -219,16 +262,20 @@ def main(argv=None):
                                 .replace("BAS", str(bs)).replace("TRI", str(trial_idx)))
                     os.makedirs(task_dir, exist_ok=True)
                     datasets = {}
-                    for stage in stages:
+                    for stage in stages if real is None else ():
                         key = "micsig_" + stage.split("_")[0] + "_simu"
                         data_dir = dirs[key][trial_idx] if stage == "train" else dirs[key]
                         datasets[stage] = at_dataset.FixMicSigDataset(data_dir=data_dir, load_anno=True, load_dp=False, fs=fs,
                                                                       dataset_sz=data_num[stage], transforms=[selecting])
                     kwargs = {"num_workers": args.workers, "pin_memory": True}
-                    dl_train = torch.utils.data.DataLoader(datasets["train"], batch_size=bs, shuffle=True, **kwargs)
-                    dl_val = torch.utils.data.DataLoader(datasets["val"], batch_size=test_bs, shuffle=False, **kwargs)
-                    dl_test = torch.utils.data.DataLoader(datasets["test"], batch_size=test_bs, shuffle=False, **kwargs)
-                    dl_test_large = torch.utils.data.DataLoader(datasets["test_large"], batch_size=test_bs, shuffle=False, **kwargs)
+                    if real is not None:
+                        dl_train, dl_val, dl_test, dl_test_large = (real.loader(trial_idx, stage, data_num[stage], bs if stage == "train" else test_bs)
+                                                                    for stage in stages)
+                    else:
+                        dl_train = torch.utils.data.DataLoader(datasets["train"], batch_size=bs, shuffle=True, **kwargs)
+                        dl_val = torch.utils.data.DataLoader(datasets["val"], batch_size=test_bs, shuffle=False, **kwargs)
+                        dl_test = torch.utils.data.DataLoader(datasets["test"], batch_size=test_bs, shuffle=False, **kwargs)
+                        dl_test_large = torch.utils.data.DataLoader(datasets["test_large"], batch_size=test_bs, shuffle=False, **kwargs)
 
                     net.load_state_dict(init_state_dict)
                     for p in net.parameters():

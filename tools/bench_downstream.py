@@ -4,7 +4,10 @@ with SARSSL_GRAPH=0 and =1 on ONE learner (same weights, same optimizer semantic
 process.  Times are host wall clock per epoch of --steps batches (an epoch ends in a device synchronise), divided by the steps; the
 batches already sit on the GPU, so a step is the step and not the loader.  Prints one JSON line.
 
-    python tools/bench_downstream.py [--steps 40] [--rounds 5]"""
+    python tools/bench_downstream.py [--steps 40] [--rounds 5] [--task TDOA --frames 64 --batch-train 8 --batch-eval 16]
+
+--task / --frames / --batch-train / --batch-eval time another shape of the same step, e.g. the real-data branch's
+(``--task T60 --frames 256 --batch-train 16``: 4.112 s items, batch 16 - what tools/bench_rirmix.py compares the render against)."""
 import argparse
 import json
 import os
@@ -23,15 +26,19 @@ def main():
     ap.add_argument("--steps", type=int, default=40)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--precision", default="hybrid")
+    ap.add_argument("--task", default="TDOA", choices=["TDOA", "T60", "DRR", "C50", "ABS"])
+    ap.add_argument("--frames", type=int, default=64)
+    ap.add_argument("--batch-train", type=int, default=8)
+    ap.add_argument("--batch-eval", type=int, default=16)
     a = ap.parse_args()
     from sar_ssl_amd import learner, model, runtime, synth
     if not torch.cuda.is_available():
         raise SystemExit("bench_downstream.py measures on the GPU; there is nothing to time without one")
     dev = torch.device("cuda:0")
-    T, B_train, B_eval = 64, 8, 16
+    T, B_train, B_eval = a.frames, a.batch_train, a.batch_eval
     nsample = 512 + 256 * (T - 1)
     rng = np.random.default_rng(0)
-    res = {"tool": "bench_downstream", "task": "TDOA", "T": T, "batch_train": B_train, "batch_eval": B_eval, "precision": a.precision,
+    res = {"tool": "bench_downstream", "task": a.task, "T": T, "batch_train": B_train, "batch_eval": B_eval, "precision": a.precision,
            "steps_per_epoch": a.steps, "rounds": a.rounds, "device": torch.cuda.get_device_name(0)}
     for mode in ("finetune", "lineareval"):
         torch.manual_seed(0)
@@ -41,14 +48,14 @@ def main():
             for k, v in net.named_parameters():
                 if k.startswith(("spec_encoder.", "spat_encoder.")):
                     v.requires_grad = False
-        lrn = learner.STFTLearner(net, win_len=512, win_shift_ratio=0.5, nfft=512, fre_used_ratio=1, fs=16000, task="TDOA", ch_mode="M")
+        lrn = learner.STFTLearner(net, win_len=512, win_shift_ratio=0.5, nfft=512, fre_used_ratio=1, fs=16000, task=a.task, ch_mode="M")
         lrn.cuda()
         lrn.amp(a.precision)
 
         def loader(B):
             sig = torch.from_numpy(synth.make_batch(1, B, nsample=nsample)).to(dev)
             tdoa = torch.from_numpy(rng.uniform(-5e-4, 5e-4, B).astype(np.float32)).to(dev)
-            return [(sig, {"TDOA": tdoa})] * a.steps
+            return [(sig, {a.task: tdoa if a.task == "TDOA" else tdoa * 1000 + 0.5})] * a.steps
         train, evalb = loader(B_train), loader(B_eval)
 
         def epoch(kind, graph):
