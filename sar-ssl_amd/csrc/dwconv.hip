@@ -200,17 +200,15 @@ __global__ __launch_bounds__(256) void dwglu_wgrad_kernel(const T* __restrict__ 
     }
 }
 
-// out[i] += sum_p partial[p][i]
+// out[i] += sum_p partial[p][i], the partials added in slice order p = 0, 1, ... - the order of splitk_reduce_multi_kernel (gemm.hip),
+// which folds the same partials when the call is made inside a split-K batch (dw == null): both ways give the same bits.  (The former
+// four-slot fold agreed with it up to three partials only.)  nparts <= 64, n = 31 d: a few microseconds either way.
 __global__ __launch_bounds__(256) void dw_partial_reduce_kernel(const float* __restrict__ partial, int nparts, long n, float* __restrict__ out) {
-    __shared__ float sred[4][64];
-    const int col = threadIdx.x & 63, slot = threadIdx.x >> 6;
-    const long i = (long)blockIdx.x * 64 + col;
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
     float s = 0.f;
-    if (i < n)
-        for (int p = slot; p < nparts; p += 4) s += partial[(long)p * n + i];
-    sred[slot][col] = s;
-    __syncthreads();
-    if (slot == 0 && i < n) out[i] += (sred[0][col] + sred[1][col]) + (sred[2][col] + sred[3][col]);
+    for (int p = 0; p < nparts; ++p) s += partial[(long)p * n + i];
+    out[i] += s;
 }
 
 #define ST ((hipStream_t)stream)
@@ -263,7 +261,7 @@ extern "C" int sarssl_dwglu_wgrad(const void* dc, const void* h, int nb, int Tn,
     dim3 grid((d + DTC - 1) / DTC, parts);
     DW_DISPATCH_GA(dtype, (dwglu_wgrad_kernel<T, TA><<<grid, 256, 0, ST>>>((const T*)dc, (const TA*)h, nb, Tn, d, partial)));
     const long n = (long)d * DWK;
-    if (dw) dw_partial_reduce_kernel<<<(int)((n + 63) / 64), 256, 0, ST>>>(partial, parts, n, dw);    // (dw == null: the caller folds the partials)
+    if (dw) dw_partial_reduce_kernel<<<(int)((n + 255) / 256), 256, 0, ST>>>(partial, parts, n, dw);    // (dw == null: the caller folds the partials)
     SARSSL_CHECK_LAUNCH("dwglu_wgrad_kernel");
     return 0;
 }
