@@ -23,11 +23,18 @@ everything else: one graph per step - at world size 1 (the form that has run on 
 more ranks the native exchange is issued between the segment graphs like torch.distributed's until a captured RCCL kernel has run on a
 multi-GPU node.  The segmented replay is the data-parallel default since round 5 (bit-equal to the eager step at world 2 and 4).
 """
+from collections import namedtuple
+
 import numpy as np
 import torch
 
 from . import hip, runtime, _lib
 from .runtime import RT
+
+
+def _nframes(nsample):
+    """STFT frames of an ``nsample``-long segment (window 512, hop 256, no padding)."""
+    return (nsample - 512) // 256 + 1
 
 
 class _Ctx:
@@ -254,21 +261,20 @@ class PretrainStepGraph(_StepGraph):
             self.reducer.finish(guard=self.guard if world > 1 else None)      # (world 1: closes the step's hook record, see FlatGradAllReduce.strict)
         self._adam(guard, world)                           # (guarded by the step's loss, see _StepGraph._adam)
 
-    def step_eager(self, x=None, pcm=None):
+    def step_eager(self, x=None, pcm=None, full_pred=False):
         """The same step enqueued launch by launch (inputs whose shape differs from the captured one, e.g. a ragged last batch):
-        shares the Adam moments / step count / accumulators with the captured step."""
+        shares the Adam moments / step count / accumulators with the captured step.  full_pred: as in step()."""
         assert (x is None) != (pcm is None)
         src = pcm if pcm is not None else x
-        if pcm is not None:
-            B, T = pcm.shape[0], (pcm.shape[1] - 512) // 256 + 1
-        else:
-            B, T = x.shape[0], x.shape[3]
+        B, T = (pcm.shape[0], _nframes(pcm.shape[1])) if pcm is not None else (x.shape[0], x.shape[3])
         if not hasattr(self, "out"):
             self.out = torch.zeros(2, dtype=torch.float32, device=self.dev)
             self.one = torch.ones((), dtype=torch.float32, device=self.dev)
         self.flat._fresh = False
         self.flat.ensure_shadow()
         idx, ch, mp = self.net._masks(B, T, self.dev)
+        if full_pred:
+            self.net.__dict__["_full_pred_once"] = True     # (popped by the forward pass: decoder and block tails on every frame)
         self._body(None, src, idx, ch, mp, pcm is not None, with_adam=True)
         runtime.bump_version()
         self.nsteps += 1
@@ -364,6 +370,11 @@ class PretrainStepGraph(_StepGraph):
         return LazyVis(pred, self.xin.clone(), self.vis_masks[0].clone(), self.vis_masks[1].clone())
 
 
+# One captured variant of the downstream step: its plan, what it was captured for, the fixed buffers it reads and fills, and the lo shadow
+# its Adam launch rewrites (None: the evaluation variant, or captured before the shadow existed)
+_DownstreamPlan = namedtuple("_DownstreamPlan", "plan key src tgt pred pooled lo")
+
+
 class DownstreamStepGraph(_StepGraph):
     """The downstream (fine-tuning) step of ``SARSSL(pretrain=False)`` - code/learner.py:168-269 - as two captured variants that share the
     input buffer, the target buffer and the loss words:
@@ -392,9 +403,8 @@ class DownstreamStepGraph(_StepGraph):
         self.requires_grad = tuple(p.requires_grad for p in flat.params)
         self.frozen = flat.frozen_ranges()
         self.precision = runtime.get_precision()
-        self._plans = {}          # training (bool) -> (plan, key, src, tgt, pred, pooled)
+        self._plans = {}          # training (bool) -> _DownstreamPlan
         self._bufs = {}           # (input shape, dtype) -> (input buffer, target buffer): one pair when both variants see the same shape
-        self._plan_lo = {}
         self._seed_base = 1 << 20     # RT._ctr at the start of every body: captured and eager launches draw with the same static seeds
         self.pred = self.pooled = None
 
@@ -407,7 +417,7 @@ class DownstreamStepGraph(_StepGraph):
         from . import engine
         net, dev = self.net, self.dev
         assert net.training == train, "step() needs the model in train mode, eval_step() in eval mode"
-        B, T, F = src.shape[0], (src.shape[1] - 512) // 256 + 1, 256
+        B, T, F = src.shape[0], _nframes(src.shape[1]), 256
         spe, spa = net.spec_encoder, net.spat_encoder
         use = {"spec": (spe,), "spat": (spa,), "spec_spat": (spe, spa)}[net.embed_use4ds]
         reads = [any(e is u for u in use) for e in (spe, spa)]
@@ -471,7 +481,7 @@ class DownstreamStepGraph(_StepGraph):
     def matches(self, pcm, train=True):
         """True when ``pcm`` can take the captured variant (not captured yet, or captured for this shape / dtype / numeric mode)."""
         ent = self._plans.get(bool(train))
-        return self.net.training == bool(train) and (ent is None or ent[1] == self._key(pcm, train))
+        return self.net.training == bool(train) and (ent is None or ent.key == self._key(pcm, train))
 
     def _target(self, target, B):
         return target.to(device=self.dev, dtype=torch.float32).reshape(B, -1).contiguous()
@@ -511,15 +521,15 @@ class DownstreamStepGraph(_StepGraph):
         def body(seg, with_adam):
             res["out"] = self._body(train, src, tgt, with_adam=with_adam)
         seg = self._capture_segments(body, [self.acc, self.acc_eval])
-        self._plans[train] = (seg.plan, self._key(pcm, train), src, tgt) + res["out"]
-        self._plan_lo[train] = getattr(self, "_adam_lo", None) if train else None
+        self._plans[train] = _DownstreamPlan(seg.plan, self._key(pcm, train), src, tgt, *res["out"],
+                                             lo=self._adam_lo if train else None)      # (_adam_lo: left by the captured Adam launch)
 
     def _replay(self, train, pcm, target):
         assert RT.replay is None, "replayed dropout masks (parity tests) need the eager step"
         assert self.net.training == train, "step() needs the model in train mode, eval_step() in eval mode"
         if train not in self._plans:
             self._capture(train, pcm, target)
-        plan, key, src, tgt, pred, pooled = self._plans[train]
+        plan, key, src, tgt, pred, pooled, plan_lo = self._plans[train]
         if key != self._key(pcm, train):
             raise ValueError("DownstreamStepGraph was captured for %r, got %r" % (key, self._key(pcm, train)))
         if src.data_ptr() != pcm.data_ptr():
@@ -531,7 +541,7 @@ class DownstreamStepGraph(_StepGraph):
             g.replay()
         self.pred, self.pooled = pred, pooled
         if train:
-            self._after_replay(self._plan_lo[train])
+            self._after_replay(plan_lo)
         return self.out
 
     def step(self, pcm, target):

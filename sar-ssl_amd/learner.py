@@ -177,21 +177,11 @@ class Learner(ABC):
             # round 5 took this batch launch by launch: ~450 host launches once per epoch); a batch of another shape takes the step eagerly
             if self._graph_takes_raw_batch(mic_sig_batch):                                  # STFT front-end inside the replay
                 sig = mic_sig_batch.to(self.device, non_blocking=True).contiguous()
-                if g.matches(pcm=sig):
-                    g.step(pcm=sig, full_pred=last)
-                else:
-                    if last:
-                        self.model.__dict__["_full_pred_once"] = True
-                    g.step_eager(pcm=sig)
+                (g.step if g.matches(pcm=sig) else g.step_eager)(pcm=sig, full_pred=last)
                 continue
             in_batch, = self.data_preprocess(mic_sig_batch, None)
             in_batch = in_batch.contiguous().float()
-            if g.matches(x=in_batch):
-                g.step(x=in_batch, full_pred=last)
-            else:
-                if last:
-                    self.model.__dict__["_full_pred_once"] = True
-                g.step_eager(x=in_batch)
+            (g.step if g.matches(x=in_batch) else g.step_eager)(x=in_batch, full_pred=last)
         vis_batch = g.vis() if g.nsteps else None
         nskip = g.skipped_steps() - skipped0
         self._report_skipped(nskip, g.nsteps)

@@ -118,8 +118,7 @@ def test_full_prediction_variant_of_the_captured_step(prec):
             for k, x in enumerate(xs):
                 full = k in (2, 5)
                 if full and form == "eager_for_full":
-                    net.__dict__["_full_pred_once"] = True
-                    out = g.step_eager(x=x)
+                    out = g.step_eager(x=x, full_pred=True)
                 else:
                     out = g.step(x=x, full_pred=full)
                 losses.append(float(out[0]))
