@@ -100,6 +100,26 @@ int sarssl_diffuse_noise(const float* white, const float* C, int nb, long ns, in
 /*      out (B, ns, M) f32 standard normal values: Box-Muller over the library's counter hash, a pure function of
  *      (seed, item0 + b, sample, channel).  NOT numpy's stream - for parity with the reference pass host-drawn noise instead. */
 int sarssl_gauss_fill(float* out, int nb, long ns, int m, unsigned long long seed, int item0, void* stream);
+/* ---- image-source room impulse responses (csrc/ism.hip): what RoomImpulseResponse.generate_rir (code/data_generation/
+ *      utils_simu_rir_sig.py:475-508) asks a CUDA-only library for - a batch of static, single-source, omnidirectional RIRs of ragged length.
+ *      Every per-item quantity is a device array and nothing is read back: room (B, 3) f64, beta (B, 6) f32 in the order x0, x1, y0, y1, z0, z1,
+ *      src (B, 3) f64, mic (B, nch, 3) f64, nb_img int (B, 3), n_ism / n_len int[B], tail_slope f32[B] in dB/s, noise (B, nch, lmax) f32 or NULL;
+ *      out (B, nch, lmax) f32.  Host bounds: nch 1..8, lmax >= every n_len, nism_max >= every n_ism, nimg_max >= every product of nb_img
+ *      (at most 2^20); per-item values beyond a bound are clamped on the device.
+ *        n < n_ism: Allen-Berkley images; per axis i = 0..N-1, n = i - N/2, q = n & 1, k = (n + q) / 2, coordinate (1 - 2q) s + 2 k L, wall
+ *        factor beta0^|k - q| beta1^|k|; an image at distance d adds A 0.5 (1 + cos(2 pi x / W)) sinc(x) at the integer samples with
+ *        |x| <= W / 2, x = n - d / c fs, A = factors / (4 pi d), W = 128, clipped at sample 0 and at n_ism.  Position, distance and delay in
+ *        f64, taps in f32, summed in image order (row-major over x, y, z): bit-reproducible, also across batch positions.
+ *        n_ism <= n < n_len: noise[n] 10^((tail_slope n / fs + level) / 20); level per channel = mean over the frames of
+ *        (10 log10(mean power + 1e-30) - tail_slope t), frames = the 128-sample stretches of the image part that start at the first multiple
+ *        of 128 at least 128 samples behind the first index of max |h| and end inside n_ism, t = the frame's centre (start + 63.5) / fs.
+ *        Fewer than two frames: the tail is zero.  n >= n_len: zero.
+ *      roomsim.restate_ism is this in f64 numpy, and the authority.  Refused (-1, nothing launched; the workspace query returns -1): nch > 8,
+ *      nimg_max > 2^20, lmax > nism_max (some n_len > n_ism) without noise.  ws: sarssl_ism_workspace_bytes(...) bytes. */
+long sarssl_ism_workspace_bytes(int nb, int nch, int lmax, int nism_max, int nimg_max);
+int sarssl_ism_rir(const double* room, const float* beta, const double* src, const double* mic, const int* nb_img, const int* n_ism,
+                   const int* n_len, const float* tail_slope, const float* noise, double fs, double c, int nb, int nch, int lmax,
+                   int nism_max, int nimg_max, void* ws, float* out, void* stream);
 
 /* ---- generic batched MFMA GEMM with fused epilogue: nn.Linear / Conv1d(k=1) / patch conv / attention bmm
  *      (code/common/conformer/modules.py:35-48, feed_forward.py:47-54, attention.py:82-103, convolution.py:138,143,

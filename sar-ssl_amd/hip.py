@@ -814,6 +814,42 @@ def gauss_fill(out, seed, item0=0):
     return out
 
 
+# ---- image-source room impulse responses (csrc/ism.hip) -------------------------------------------------------------------------------
+def ism_workspace_bytes(B, nch, lmax, nism_max, nimg_max):
+    """Bytes of scratch sarssl_ism_rir needs, -1 for a shape it refuses (nch > 8, more than 2^20 images, nism_max > lmax)."""
+    fn = _lib.lib().sarssl_ism_workspace_bytes
+    fn.restype = c_long
+    return fn(c_int(B), c_int(nch), c_int(lmax), c_int(nism_max), c_int(nimg_max))
+
+
+def ism_rir(room, beta, src, mic, nb_img, n_ism, n_len, tail_slope, *, lmax, nism_max, nimg_max, noise=None, fs=16000.0, c=343.0, out=None):
+    """A batch of static single-source omnidirectional image-source RIRs: room (B, 3) f64, beta (B, 6) f32, src (B, 3) f64,
+    mic (B, nch, 3) f64, nb_img int32 (B, 3), n_ism / n_len int32 (B), tail_slope f32 (B) in dB/s, noise (B, nch, lmax) f32 or None ->
+    (B, nch, lmax) f32, zero from n_len on.  lmax / nism_max / nimg_max: host bounds of n_len / n_ism / prod(nb_img).  A refused shape
+    raises and leaves ``out`` untouched.  See include/sarssl_hip.h for the arithmetic (roomsim.restate_ism is its f64 statement)."""
+    _need_cuda(room, beta, src, mic, nb_img, n_ism, n_len, tail_slope, noise, out)
+    B, nch = mic.shape[0], mic.shape[1]
+    for t in (room, src, mic):
+        assert t.dtype == torch.float64 and t.is_contiguous()
+    for t in (beta, tail_slope, noise):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous())
+    assert room.shape == (B, 3) and beta.shape == (B, 6) and src.shape == (B, 3) and mic.shape == (B, nch, 3) and nb_img.shape == (B, 3)
+    assert n_ism.shape == (B,) and n_len.shape == (B,) and tail_slope.shape == (B,)
+    assert noise is None or noise.shape == (B, nch, lmax)
+    if out is not None:
+        assert out.shape == (B, nch, lmax) and out.dtype == torch.float32 and out.is_contiguous()
+    nbytes = ism_workspace_bytes(B, nch, lmax, nism_max, nimg_max)
+    if nbytes < 0:
+        raise _lib.SarsslHipError("ism_rir: unsupported shape (B=%d, nch=%d, lmax=%d, nism_max=%d, nimg_max=%d)" % (B, nch, lmax, nism_max, nimg_max))
+    ws = workspace(nbytes, mic.device, "ism_rir")
+    if out is None:
+        out = torch.empty((B, nch, lmax), dtype=torch.float32, device=mic.device)
+    _lib.call("sarssl_ism_rir", _p(room), _p(beta), _p(src), _p(mic), _p(_i32(nb_img)), _p(_i32(n_ism)), _p(_i32(n_len)), _p(tail_slope),
+              _p(noise), _lib.c_double(fs), _lib.c_double(c), c_int(B), c_int(nch), c_int(lmax), c_int(nism_max), c_int(nimg_max), _p(ws),
+              _p(out), _stream())
+    return out
+
+
 # ------------------------------------------------------------------------------------------------
 # conv stem
 def _f32ws(n, device, tag):

@@ -56,6 +56,14 @@ RIRMIX = dict(gate=2e-6, cap=1.5e-5, restatement_vs_f20=8e-7,
               measured=dict(rir_mix=2.8e-7, diffuse_noise=2.9e-7, loader=3.1e-7, restatement_vs_f20=1.9e-7))
 
 
+# The image-source renderer (csrc/ism.hip) against the f64 numpy restatement roomsim.restate_ism: max |difference| over an RIR relative to
+# the RIR's absolute peak (tests/test_gpu_ism.py).  cap: half a PCM-16 step of full scale, as for RIRMIX - a condition, not a measurement.
+# gate: 4x the largest distance measured on an MI355X over the test's shapes, rounded up to one digit (profiles/ism.txt).  t60_gate: the same
+# for |T60_edc(GPU RIR) - T60_edc(restatement)| in seconds; t60_cap 5e-3 s, a tenth of the window the reference's accept test allows.
+# (tools/bench_ism.py measures 4.9e-7 over rooms idx 0..7 of stage train: rooms with more images than the test's two sit closer to the gate.)
+ISM = dict(gate=7e-7, cap=1.5e-5, t60_gate=7e-8, t60_cap=5e-3,
+           measured=dict(ragged=1.4e-7, tail=1.4e-7, full_size=1.5e-7, direct_path=1.3e-7, t60_edc=1.6e-8))
+
 # The row / elementwise kernels (csrc/elementwise.hip, the row kernels of csrc/dwconv.hip, csrc/head.hip) against the f64 restatements of
 # tests/rowkernel_refs.py on the operands as stored: max |got - ref| / max |ref| (tests/test_gpu_rowkernels.py).  Keyed by kernel family,
 # then by the storage dtype of a forward kernel or the (gradient, saved activation) pairing of a backward kernel: f32, bf16, fp16,
