@@ -67,6 +67,10 @@ int sarssl_stft_raw(const void* sig, int sig_dtype, int nb, long nsample, int nc
  *      buffer) with samples [offset, offset+nsample) of each file using nthreads positional readers. */
 int sarssl_wav_probe(const char* path, int* nch, int* fs, long* nsample);
 int sarssl_wav_read_batch(const char* const* paths, int n, long nsample, int nch, int fs, long offset, short* out, int nthreads);
+/*      the counterpart: paths[i] = a 44-byte-header PCM-16 file of in[i][nsample][nch], byte for byte what dataset.write_wav_pcm16 writes.
+ *      Each file is written as `<path>.tmp` by nthreads positional writers and renamed when complete; non-zero on an error, after which
+ *      no path names a half-written file. */
+int sarssl_wav_write_batch(const char* const* paths, int n, long nsample, int nch, int fs, const short* in, int nthreads);
 /* ---- host-side mask RNG: PatchMask.forward / gen_mask_idx (code/common/utils_module.py:255-273, 305-308) with Python's own
  *      MT19937 state (random.getstate()[1]: 624 words + position) - bit-identical index / channel stream, no interpreter loop.
  *      idx: int64[nbatch][nmasked], ch: int64[nbatch]. */
@@ -120,6 +124,24 @@ long sarssl_ism_workspace_bytes(int nb, int nch, int lmax, int nism_max, int nim
 int sarssl_ism_rir(const double* room, const float* beta, const double* src, const double* mic, const int* nb_img, const int* n_ism,
                    const int* n_len, const float* tail_slope, const float* noise, double fs, double c, int nb, int nch, int lmax,
                    int nism_max, int nimg_max, void* ws, float* out, void* stream);
+/* ---- the accept test and the annotations of simulated RIRs (csrc/rirlabel.hip): check_rir, check_rir_envelope and generate_annotation
+ *      (code/data_generation/utils_simu_rir_sig.py:510-614, 863-994) as roomsim.labels restates them, in f64 on the f32 values as stored,
+ *      a batch per call and nothing read back.  rir (B, nch, lmax) f32 with n_len int[B]; rir_dp (B, nch, ldmax) f32 with dp_len int[B];
+ *      t60_specify f64[B]; fs in Hz.  Out: t60, corr f64 (B, nch) - per channel the T60 and the correlation of the best-correlated of the
+ *      80 line fits to the Schroeder curve -, t60_edc f64[B] their mean over the channels, drr, c50 f64[B] in dB of channel 0, nd int[B]
+ *      the first signed maximum of the direct path's channel 0, flags int[B]: bit 0 rir_ok (no NaN, no Inf, not all zero, in both),
+ *      bit 1 env_ok (|t60_edc - t60_specify| < 0.05 and |corr of the LAST channel| > 0.5).  Without rir_ok t60, corr and t60_edc are NaN.
+ *      Among the fits a NaN correlation wins, as it does in numpy's argmax.  An item's outputs depend neither on its batch position nor
+ *      on lmax.  Refused (-1, nothing launched; the workspace query returns -1): nch > 8, lmax or ldmax outside 1..32768.
+ *      ws: sarssl_rir_labels_workspace_bytes(...) bytes. */
+long sarssl_rir_labels_workspace_bytes(int nb, int nch, int lmax, int ldmax);
+int sarssl_rir_labels(const float* rir, const int* n_len, const float* rir_dp, const int* dp_len, const double* t60_specify, double fs,
+                      int nb, int nch, int lmax, int ldmax, void* ws, double* t60, double* corr, double* t60_edc, double* drr, double* c50,
+                      int* nd, int* flags, void* stream);
+/*      float -> PCM-16 of the signal generator: out[i] = rint(double(in[i]) 32767), ties to even, saturated to +-32767; NaN gives 0.  This
+ *      is libsndfile's float -> PCM-16 rule with normalisation on AS THIS PROJECT READS IT: soundfile is not available to pin it against
+ *      (UNPINNED).  The product is exact in f64, so the result is bit-equal to numpy's.  in 16-byte, out 8-byte aligned. */
+int sarssl_pcm16_pack(const float* in, long n, short* out, void* stream);
 
 /* ---- generic batched MFMA GEMM with fused epilogue: nn.Linear / Conv1d(k=1) / patch conv / attention bmm
  *      (code/common/conformer/modules.py:35-48, feed_forward.py:47-54, attention.py:82-103, convolution.py:138,143,

@@ -8,6 +8,7 @@
 #include "common.h"
 #include <fcntl.h>
 #include <stdint.h>
+#include <stdio.h>
 #include <string.h>
 #include <sys/stat.h>
 #include <unistd.h>
@@ -99,6 +100,60 @@ extern "C" int sarssl_wav_read_batch(const char* const* paths, int n, long nsamp
             }
             close(fd);
             if (rc) { errs[tid] = err; failed = 1; return; }
+        }
+    };
+    if (nthreads == 1) work(0);
+    else {
+        std::vector<std::thread> th;
+        for (int t = 0; t < nthreads; ++t) th.emplace_back(work, t);
+        for (auto& t : th) t.join();
+    }
+    if (failed.load()) {
+        for (auto& e : errs) if (!e.empty()) { sarssl_set_error("%s", e.c_str()); break; }
+        return -1;
+    }
+    return 0;
+}
+
+// The counterpart of the reader, for the signal generator (roomsim.simulate_signals): paths[i] = a 44-byte-header PCM-16 file of
+// in[i][0..nsample)[0..nch), byte for byte what dataset.write_wav_pcm16 writes.  Every file is written as `<path>.tmp` with positional
+// writes and renamed when complete, so no path ever names a half-written file; on an error the call returns non-zero, the failing
+// file's .tmp is removed and the files not yet started are not written.  nthreads <= 0 -> min(n, 8).
+static void wr32(unsigned char* p, uint32_t v) { p[0] = v & 255; p[1] = (v >> 8) & 255; p[2] = (v >> 16) & 255; p[3] = (v >> 24) & 255; }
+static void wr16(unsigned char* p, uint32_t v) { p[0] = v & 255; p[1] = (v >> 8) & 255; }
+extern "C" int sarssl_wav_write_batch(const char* const* paths, int n, long nsample, int nch, int fs, const int16_t* in, int nthreads) {
+    SARSSL_REQUIRE(n >= 0 && nsample > 0 && nch > 0 && nch <= 65535 && fs > 0 && in && (n == 0 || paths), "sarssl_wav_write_batch");
+    SARSSL_REQUIRE((double)nsample * nch * 2 + 36 <= 4294967295.0, "sarssl_wav_write_batch(a RIFF file holds less than 4 GiB)");
+    if (n == 0) return 0;
+    if (nthreads <= 0) nthreads = n < 8 ? n : 8;
+    if (nthreads > n) nthreads = n;
+    std::atomic<int> next(0), failed(0);
+    std::vector<std::string> errs(nthreads);
+    const size_t bytes = (size_t)nsample * nch * 2;
+    unsigned char hdr[44];
+    memcpy(hdr, "RIFF", 4); wr32(hdr + 4, (uint32_t)(36 + bytes)); memcpy(hdr + 8, "WAVEfmt ", 8); wr32(hdr + 16, 16); wr16(hdr + 20, 1);
+    wr16(hdr + 22, (uint32_t)nch); wr32(hdr + 24, (uint32_t)fs); wr32(hdr + 28, (uint32_t)fs * nch * 2); wr16(hdr + 32, (uint32_t)nch * 2);
+    wr16(hdr + 34, 16); memcpy(hdr + 36, "data", 4); wr32(hdr + 40, (uint32_t)bytes);
+    auto put = [](int fd, const char* src, size_t len, long off) {
+        size_t done = 0;
+        while (done < len) {
+            const ssize_t r = pwrite(fd, src + done, len - done, off + (long)done);
+            if (r <= 0) return false;
+            done += (size_t)r;
+        }
+        return true;
+    };
+    auto work = [&](int tid) {
+        for (;;) {
+            const int i = next.fetch_add(1);
+            if (i >= n || failed.load()) return;
+            const std::string tmp = std::string(paths[i]) + ".tmp";
+            const int fd = open(tmp.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+            if (fd < 0) { errs[tid] = tmp + ": cannot create"; failed = 1; return; }
+            bool ok = put(fd, (const char*)hdr, 44, 0) && put(fd, (const char*)in + (size_t)i * bytes, bytes, 44);
+            ok = (close(fd) == 0) && ok;
+            if (ok && rename(tmp.c_str(), paths[i]) != 0) ok = false;
+            if (!ok) { unlink(tmp.c_str()); errs[tid] = std::string(paths[i]) + ": write failed"; failed = 1; return; }
         }
     };
     if (nthreads == 1) work(0);

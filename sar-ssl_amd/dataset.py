@@ -129,6 +129,20 @@ def read_wav_batch(paths, nsample, nch, fs=0, offset=0, out=None, nthreads=0):
     return out[:n] if out.shape[0] != n else out
 
 
+def write_wav_batch(paths, pcm, fs=16000, nthreads=0):
+    """pcm: int16 host tensor or array (len(paths), nsample, nch) -> one 44-byte-header PCM-16 file per path, byte for byte what
+    ``write_wav_pcm16`` writes, by the threaded writer of the C-ABI library (csrc/wavio.hip, ``sarssl_wav_write_batch``; the GIL is
+    released during the call).  Files appear under their names only when complete (written as ``<path>.tmp``, then renamed)."""
+    from . import _lib
+    if isinstance(pcm, np.ndarray):
+        pcm = torch.from_numpy(np.ascontiguousarray(pcm))
+    n = len(paths)
+    assert pcm.dtype == torch.int16 and pcm.is_contiguous() and not pcm.is_cuda and pcm.dim() == 3 and pcm.shape[0] >= n
+    arr = (ctypes.c_char_p * n)(*[str(p).encode() for p in paths])
+    _lib.call("sarssl_wav_write_batch", arr, ctypes.c_int(n), ctypes.c_long(pcm.shape[1]), ctypes.c_int(pcm.shape[2]), ctypes.c_int(fs),
+              ctypes.c_void_p(pcm.data_ptr()), ctypes.c_int(nthreads))
+
+
 def wav_probe(path):
     """-> (nch, fs, nsample) of a PCM-16 WAV file."""
     from . import _lib

@@ -850,6 +850,62 @@ def ism_rir(room, beta, src, mic, nb_img, n_ism, n_len, tail_slope, *, lmax, nis
     return out
 
 
+# ---- accept test and annotations of simulated RIRs, float -> PCM-16 (csrc/rirlabel.hip) -------------------------------------------------
+def rir_labels_workspace_bytes(B, nch, lmax, ldmax):
+    """Bytes of scratch sarssl_rir_labels needs, -1 for a shape it refuses (nch > 8, lmax or ldmax outside 1..32768)."""
+    fn = _lib.lib().sarssl_rir_labels_workspace_bytes
+    fn.restype = c_long
+    return fn(c_int(B), c_int(nch), c_int(lmax), c_int(ldmax))
+
+
+def rir_labels(rir, n_len, rir_dp, dp_len, t60_specify, fs=16000.0):
+    """roomsim.labels of a batch on the device: rir (B, nch, lmax) f32 + n_len int32 (B), rir_dp (B, nch, ldmax) f32 + dp_len int32 (B),
+    t60_specify f64 (B) -> dict of device tensors t60, corr f64 (B, nch), t60_edc, drr, c50 f64 (B), nd, flags int32 (B; bit 0 rir_ok,
+    bit 1 env_ok).  Nothing is read back.  A refused shape raises.  See include/sarssl_hip.h for the arithmetic."""
+    _need_cuda(rir, n_len, rir_dp, dp_len, t60_specify)
+    B, nch, lmax = rir.shape
+    ldmax = rir_dp.shape[2]
+    for t in (rir, rir_dp):
+        assert t.dtype == torch.float32 and t.is_contiguous()
+    assert rir_dp.shape[:2] == (B, nch) and n_len.shape == (B,) and dp_len.shape == (B,)
+    assert t60_specify.dtype == torch.float64 and t60_specify.is_contiguous() and t60_specify.shape == (B,)
+    nbytes = rir_labels_workspace_bytes(B, nch, lmax, ldmax)
+    if nbytes < 0:
+        raise _lib.SarsslHipError("rir_labels: unsupported shape (B=%d, nch=%d, lmax=%d, ldmax=%d)" % (B, nch, lmax, ldmax))
+    ws = workspace(nbytes, rir.device, "rir_labels")
+    n = 2 * B * nch + 3 * B
+    f64 = torch.empty((n + B,), dtype=torch.float64, device=rir.device)             # one allocation: the f64 labels, then 2 B int32
+    i32 = f64[n:].view(torch.int32)
+    out = dict(t60=f64[:B * nch].view(B, nch), corr=f64[B * nch:2 * B * nch].view(B, nch), t60_edc=f64[2 * B * nch:2 * B * nch + B],
+               drr=f64[2 * B * nch + B:2 * B * nch + 2 * B], c50=f64[2 * B * nch + 2 * B:n], nd=i32[:B], flags=i32[B:])
+    _lib.call("sarssl_rir_labels", _p(rir), _p(_i32(n_len)), _p(rir_dp), _p(_i32(dp_len)), _p(t60_specify), _lib.c_double(fs), c_int(B),
+              c_int(nch), c_int(lmax), c_int(ldmax), _p(ws), _p(out["t60"]), _p(out["corr"]), _p(out["t60_edc"]), _p(out["drr"]),
+              _p(out["c50"]), _p(out["nd"]), _p(out["flags"]), _stream())
+    out["_all"] = f64                            # the allocation behind the views: one copy reads every label back (rir_labels_host)
+    return out
+
+
+def rir_labels_host(lab):
+    """The result of ``rir_labels`` as numpy arrays, read back with one copy (synchronises)."""
+    h = lab["_all"].cpu()
+    B, nch = lab["t60"].shape
+    n = 2 * B * nch + 3 * B
+    f, i = h[:n].numpy(), h[n:].view(torch.int32).numpy()
+    return dict(t60=f[:B * nch].reshape(B, nch), corr=f[B * nch:2 * B * nch].reshape(B, nch), t60_edc=f[2 * B * nch:2 * B * nch + B],
+                drr=f[2 * B * nch + B:2 * B * nch + 2 * B], c50=f[2 * B * nch + 2 * B:n], nd=i[:B], flags=i[B:])
+
+
+def pcm16_pack(x, out=None):
+    """f32 tensor -> int16 tensor of the same shape: rint(double(x) * 32767), ties to even, saturated to +-32767 (NaN -> 0)."""
+    _need_cuda(x, out)
+    assert x.dtype == torch.float32 and x.is_contiguous()
+    if out is None:
+        out = torch.empty(x.shape, dtype=torch.int16, device=x.device)
+    assert out.shape == x.shape and out.dtype == torch.int16 and out.is_contiguous()
+    _lib.call("sarssl_pcm16_pack", _p(x), c_long(x.numel()), _p(out), _stream())
+    return out
+
+
 # ------------------------------------------------------------------------------------------------
 # conv stem
 def _f32ws(n, device, tag):

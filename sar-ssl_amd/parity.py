@@ -64,6 +64,28 @@ RIRMIX = dict(gate=2e-6, cap=1.5e-5, restatement_vs_f20=8e-7,
 ISM = dict(gate=7e-7, cap=1.5e-5, t60_gate=7e-8, t60_cap=5e-3,
            measured=dict(ragged=1.4e-7, tail=1.4e-7, full_size=1.5e-7, direct_path=1.3e-7, t60_edc=1.6e-8))
 
+# The labels kernel (csrc/rirlabel.hip: sarssl_rir_labels) against roomsim.labels on identical f32 input (tests/test_gpu_simsig.py):
+# largest |device - host| of the per-channel T60 in seconds, of the fit's correlation, of DRR and of C50 in dB, over the synthetic cases
+# of tests/simsig_cases.py at 1, 2 and 3 channels.  Both sides are f64; they differ in the order of the sums and in the closed-form fits
+# from centred suffix sums instead of scipy.stats.linregress per stretch.
+#   cap       a condition, not a measurement: t60 = ISM's t60_cap (a tenth of the accept test's window; every test item sits at least
+#             0.029 s inside it, so the decision cannot flip); DRR / C50 1e-3 dB, far below a float16 step at their magnitude; corr 1e-9 -
+#             what the cancellation in sum y^2 - (sum y)^2 / N can cost at most: N 2^-53 relative on sums below N 74^2 (E lies in
+#             [-100, 0] dB, centred at -26) over a variance of at least 8 dB^2 (a 10 dB stretch) = 1e-9 at N = 14 000
+#   measured  on an MI355X (profiles/simsig.txt)
+#   gate      4x measured, rounded up to one digit; the tolerance of a test is min(gate, cap)
+RIRLABELS = dict(cap=dict(t60=5e-3, corr=1e-9, drr=1e-3, c50=1e-3),
+                 measured=dict(t60=1.5e-14, corr=3.5e-14, drr=3.6e-15, c50=1.8e-15),
+                 gate=dict(t60=6e-14, corr=2e-13, drr=2e-14, c50=8e-15))
+
+# The signal generator (roomsim.simulate_signals) against roomsim.restate_sig of the same plan, in PCM-16 steps (tests/test_gpu_simsig.py).
+#   pcm_step     derived, not measured: the mix gate RIRMIX['gate'] = 2e-6 of full scale is 0.066 of a PCM step, below one half, so the
+#                rounded values differ by at most one step
+#   share_bound  derived: a sample can differ only where the f64 value lies within the gate of a rounding boundary, a share of
+#                2 gate 32767 = 0.131 of all samples
+#   measured     the largest share of differing samples of an item on an MI355X (recorded, not gated below the bound)
+SIMSIG = dict(pcm_step=1, share_bound=2 * RIRMIX["gate"] * 32767, measured=dict(share=3.3e-3, max_step=1))
+
 # The row / elementwise kernels (csrc/elementwise.hip, the row kernels of csrc/dwconv.hip, csrc/head.hip) against the f64 restatements of
 # tests/rowkernel_refs.py on the operands as stored: max |got - ref| / max |ref| (tests/test_gpu_rowkernels.py).  Keyed by kernel family,
 # then by the storage dtype of a forward kernel or the (gradient, saved activation) pairing of a backward kernel: f32, bf16, fp16,

@@ -1,4 +1,4 @@
-"""Simulated RIR banks: image-source room simulation on the GPU.
+"""Simulated RIR banks and the simulated pretraining corpus: image-source room simulation on the GPU.
 
 The reference writes ``data/RIR/simu/<stage>/{idx}.npy``, ``{idx}_dp.npy`` and ``{idx}_info.npz`` with ``gen_simu.py --mode rir``
 (GenerateRandomRIR -> MicrophoneSignalOrRIR.generate_rir, code/data_generation/utils_simu_rir_sig.py:672-747) and takes the RIR itself
@@ -6,6 +6,12 @@ from gpuRIR, a CUDA-only third-party library that is neither part of the referen
 the host restates everything around the call (``random_spatial_acoustics``: the random room, array and source, draw for draw;
 ``labels``: check_rir, check_rir_envelope, generate_annotation) and the GPU sums the image sources (hip.ism_rir, csrc/ism.hip).
 ``restate_ism`` is the f64 numpy statement of one RIR that the kernel is tested against.
+
+``gen_simu.py --mode sig`` (GenerateRandomMicSig -> generate_microphone_signal, utils_simu_rir_sig.py:749-861) is ``simulate_signals``:
+the same RIRs judged on the device (hip.rir_labels, csrc/rirlabel.hip - ``labels_twin`` is its arithmetic in numpy), convolved with a
+WSJ0-style source, mixed with the diffuse white-noise field at a drawn SNR, converted to PCM-16 and written as ``{idx}.wav`` +
+``{idx}_info.npz`` without the RIR leaving the GPU; ``plan_sig`` restates the reference's draws and ``restate_sig`` one item in f64
+(fixture F22, tools/make_golden_simsig.py).  The float -> PCM-16 rule is this project's reading of libsndfile's and UNPINNED (``pcm16``).
 
 PARITY WITH gpuRIR IS UNPINNED: the library cannot be run or read, so the RIR is this project's own image-source model (Allen-Berkley
 images, 8 ms Hann-windowed sinc fractional delays, an exponentially decaying noise tail at the Sabine slope).  What is pinned against the
@@ -323,6 +329,135 @@ def labels(rir, rir_dp, cfg, fs=FS, c=343.0):
     return out
 
 
+def tdoa(cfg, c=343.0):
+    """The TDOA annotation alone (geometry only): float32, as ``annotations`` returns it."""
+    mic, src = np.asarray(cfg["mic_pos"], np.float64), np.asarray(cfg["src_traj_pts"], np.float64)[0, :, 0]
+    dist = np.sqrt(np.sum((src[None, :] - mic) ** 2, axis=1))
+    return ((dist[1] - dist[0]) / c).astype(np.float32)
+
+
+LABEL_TARGETS = -5.0 - 2.0 * np.arange(22)          # the 22 distinct dB levels of the 80 stretches: -5, -7 .. -47
+
+
+def labels_twin(rir, rir_dp, T60_specify, fs=FS):
+    """The arithmetic of csrc/rirlabel.hip (sarssl_rir_labels) in numpy on rir (nch, L), rir_dp (nch, Ld): what ``labels`` computes, by
+    the kernel's route - the 80 line fits in closed form from suffix sums of (E + 26), (E + 26)^2 and (n - L / 2)(E + 26) and the variance
+    of consecutive integers instead of 80 calls of scipy.stats.linregress - and with the kernel's outputs: dict(t60, corr (nch,), t60_edc,
+    drr, c50, nd, flags; bit 0 rir_ok, bit 1 env_ok), DRR / C50 unrounded.  Agrees with ``labels`` to rounding (tests/test_simsig_cpu.py)."""
+    rir, rir_dp = np.asarray(rir, np.float64), np.asarray(rir_dp, np.float64)
+    nch, L = rir.shape
+    Ld = rir_dp.shape[1]
+    fs = float(fs)
+
+    def ok(x):
+        return bool(np.isfinite(x).all() and (x != 0).any())
+    rir_ok = ok(rir) and ok(rir_dp)
+    t60, corr = np.full(nch, np.nan), np.full(nch, np.nan)
+    for m in range(nch if rir_ok else 0):
+        h = rir[m]
+        S = np.cumsum(h[::-1] ** 2)[::-1]
+        E = 10.0 * np.log10(S / (S[np.argmax(h)] + 1e-10) + 1e-10)
+        near = [int(np.argmin(np.abs(E - v))) for v in LABEL_TARGETS]
+        y = E + 26.0
+        xc = 0.5 * L
+
+        def suffix(v):
+            return np.concatenate([np.cumsum(v[::-1])[::-1], [0.0]])
+        Q0, Q1, Q2 = suffix(y), suffix(y * y), suffix((np.arange(L) - xc) * y)
+        rs, ts = [], []
+        for a in range(8):
+            for d in range(10):
+                st, ed = near[a], near[a + 5 + d]
+                if abs(st - ed) > 1 and ed > st:
+                    N = float(ed - st)
+                    sy, syy, sxy = Q0[st] - Q0[ed], Q1[st] - Q1[ed], Q2[st] - Q2[ed]
+                    xm = 0.5 * (st + ed - 1) - xc
+                    ssxm, ssym, ssxym = (N * N - 1.0) / 12.0 / (fs * fs), (syy - sy * sy / N) / N, (sxy - xm * sy) / N / fs
+                    r = 0.0
+                    if ssxm != 0.0 and ssym != 0.0:
+                        with np.errstate(invalid="ignore"):
+                            r = ssxym / np.sqrt(ssxm * ssym)
+                        r = 1.0 if r > 1.0 else -1.0 if r < -1.0 else r
+                    rs.append(r)
+                    ts.append(-60.0 / (ssxym / ssxm + 1e-10))
+                else:
+                    rs.append(0.0)
+                    ts.append(np.nan)
+        i = int(np.argmax(np.abs(np.array(rs))))                # (a NaN wins, as on the host and in the kernel)
+        t60[m], corr[m] = ts[i], rs[i]
+    t60_edc = np.mean(t60) if rir_ok else np.nan
+    env_ok = bool(rir_ok and abs(t60_edc - T60_specify) < 0.05 and abs(corr[-1]) > 0.5)
+    nd = int(np.argmax(rir_dp[0]))
+    if rir_dp[0, nd] < 0 and L > Ld:
+        nd = Ld
+    p = rir[0] ** 2
+    n = np.arange(L)
+    eps = 1e-8
+    in_dp, early = (n >= nd - int(fs * 2.5 / 1000)) & (n <= nd + int(fs * 2.5 / 1000)), n <= nd + int(fs * 50 / 1000)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        fin = bool(np.isfinite(rir[0]).all())
+        drr = 10.0 * np.log10(p[in_dp].sum() / (p[~in_dp].sum() + eps) + eps) if fin else np.nan
+        c50 = 10.0 * np.log10(p[early].sum() / (p[~early].sum() + eps) + eps) if fin else np.nan
+    return dict(t60=t60, corr=corr, t60_edc=t60_edc, drr=drr, c50=c50, nd=nd, flags=int(rir_ok) | (int(env_ok) << 1))
+
+
+# ---------------------------------------------------------------------------------------------------------------- microphone signals
+PCM_GAIN = 0.9                   # utils_simu_rir_sig.py:824
+SIG_STAGE_SEEDS = {"pretrain": 1, "preval": 2000000, "pretest": 3000000}        # gen_simu.py:216-231; 'pretest_ins*' takes pretest's
+SIG_SRC_SUBDIR = {"pretrain": "tr", "preval": "dt", "pretest": "et"}            # gen_simu.py:282-289
+
+
+def sig_stage(stage):
+    """'pretrain' | 'preval' | 'pretest' for a stage name of --mode sig ('pretest_ins*' counts as pretest), else ValueError with the
+    reference's assertion (gen_simu.py:216)."""
+    if stage in SIG_STAGE_SEEDS:
+        return stage
+    if "pretest_ins" in stage:
+        return "pretest"
+    raise ValueError("--stage %s: only --mode rir generates stages train / val / test; --mode sig takes pretrain | preval | pretest | "
+                     "pretest_ins*, as the reference asserts" % stage)
+
+
+def pcm16(x):
+    """float -> PCM-16 as the generator writes it: rint(x 32767) in f64, ties to even, saturated to +-32767.  This is libsndfile's rule
+    for float input with normalisation on AS THIS PROJECT READS IT; soundfile is not available to pin it against (UNPINNED)."""
+    return np.clip(np.rint(np.asarray(x, np.float64) * 32767.0), -32767.0, 32767.0).astype(np.int16)
+
+
+def plan_sig(rs, idx, seed, cfg, sources, T, snr_range=(15, 30), nmic=2, draw_white=True, fs=FS):
+    """generate_microphone_signal's draws (utils_simu_rir_sig.py:749-816) on the RandomState ``rs`` after seed + idx: speaker index,
+    SourceBank.draw (utterance, same-speaker padding, crop, mean removal), the white noise (int(T fs), nmic) - left out with
+    draw_white=False: the device draws its own -, the SNR."""
+    rs.seed(seed + idx)
+    src_idx = int(rs.randint(0, len(sources)))
+    src, rec = sources.draw(rs, src_idx, int(T * fs))
+    white = rs.standard_normal((int(T * fs), nmic)) if draw_white else None
+    snr = float(rs.uniform(*snr_range))
+    return dict(rec, idx=idx, cfg=cfg, src_idx=src_idx, src=src, white=white, snr=snr)
+
+
+def restate_sig(plan, tail_noise=None, rir=None, rir_dp=None, pcm=True, fs=FS, c=343.0, ism_db=12):
+    """One item of the generator in f64 from the existing restatements: the RIR and the direct path of plan['cfg'] (restate_cfg; or the
+    given ``rir`` / ``rir_dp`` (nch, L)), the diffuse field of the plan's white noise, the mix at gain 0.9, and with pcm=True the PCM
+    rule -> (Ns, nch) int16 (float64 with pcm=False).  The authority for the GPU tests."""
+    from . import rirsynth
+    cfg = plan["cfg"]
+    if rir is None:
+        rir = restate_cfg(cfg, tail_noise, fs, c, ism_db)
+    if rir_dp is None:
+        rir_dp = restate_cfg(cfg, None, fs, c, ism_db, dp=True)
+    noise = rirsynth.restate_diffuse(plan["white"], rirsynth.mixing_table(cfg["mic_pos"], fs, c))
+    mic = rirsynth.restate_mix(plan["src"], rir, rir_dp=rir_dp, noise=noise, snr_db=plan["snr"], gain=PCM_GAIN)
+    return pcm16(mic) if pcm else mic
+
+
+def sig_info(cfg, plan, T60_edc, DRR, C50, c=343.0):
+    """The dictionary of ``{idx}_info.npz`` (utils_simu_rir_sig.py:798-861): the configuration with T60_edc, src_idx and SNR, and the
+    annotations with the reference's dtypes (TDOA float32, DRR and C50 float16)."""
+    return dict(cfg, T60_edc=np.float64(T60_edc), src_idx=plan["src_idx"], SNR=plan["snr"], TDOA=tdoa(cfg, c),
+                DRR=np.asarray(DRR, np.float64).astype(np.float16), C50=np.asarray(C50, np.float64).astype(np.float16))
+
+
 # ---------------------------------------------------------------------------------------------------------------- GPU render
 def _check_tail_frames(p, fs, c):
     """The refusal of restate_ism, before a launch: the direct sound's arrival bounds the peak."""
@@ -337,16 +472,17 @@ def _check_tail_frames(p, fs, c):
                              % (p["n_ism"], W, peak))
 
 
-def render(plans, device, noise=None, fs=FS, c=343.0):
+def render(plans, device, noise=None, fs=FS, c=343.0, lmax=None):
     """One hip.ism_rir launch for a list of ``plan_rir`` results -> (B, nch, lmax) f32 on the device.  noise: (B, nch, lmax) f32 device
-    tensor, or None when no plan has a tail."""
+    tensor, or None when no plan has a tail.  lmax: the row length, at least every n_len (default: the longest of the batch)."""
     import torch
     from . import hip
     B, nch = len(plans), plans[0]["mic"].shape[0]
     for p in plans:
         assert p["mic"].shape == (nch, 3)
         _check_tail_frames(p, fs, c)
-    lmax, nism_max = max(p["n_len"] for p in plans), max(p["n_ism"] for p in plans)
+    nism_max = max(p["n_ism"] for p in plans)
+    lmax = _row_length(plans, lmax)
     nimg_max = max(int(np.prod(p["nb_img"])) for p in plans)
     if nimg_max > MAX_IMAGES:
         raise ValueError("%d image sources in one RIR, at most %d are rendered" % (nimg_max, MAX_IMAGES))
@@ -358,23 +494,30 @@ def render(plans, device, noise=None, fs=FS, c=343.0):
                        nimg_max=nimg_max, noise=noise, fs=float(fs), c=float(c))
 
 
-def device_noise(plans, ids, seed, attempt, device):
+def _row_length(plans, lmax=None):
+    longest = max(p["n_len"] for p in plans)
+    if lmax is not None and lmax < longest:
+        raise ValueError("lmax = %d is shorter than an RIR of %d samples" % (lmax, longest))
+    return longest if lmax is None else int(lmax)
+
+
+def device_noise(plans, ids, seed, attempt, device, lmax=None):
     """(B, nch, lmax) f32 standard normal values on the device: item b from sarssl_gauss_fill keyed by (seed, ids[b], attempt).  Drawn in
     gauss_fill's own (sample, channel) order and transposed, so that the value at (channel, sample) of an item is a function of that key
     alone - not of the longest item of the batch it is rendered in."""
     import torch
     from . import hip
-    nch, lmax = plans[0]["mic"].shape[0], max(p["n_len"] for p in plans)
+    nch, lmax = plans[0]["mic"].shape[0], _row_length(plans, lmax)
     white = torch.empty((len(plans), lmax, nch), dtype=torch.float32, device=device)
     for b, idx in enumerate(ids):
         hip.gauss_fill(white[b:b + 1], (int(seed) & 0xffffffff) | (int(attempt) << 32), int(idx))
     return white.transpose(1, 2).contiguous()
 
 
-def host_noise(plans, ids, seed, attempt, device):
+def host_noise(plans, ids, seed, attempt, device, lmax=None):
     """The same from ``numpy_noise``, uploaded."""
     import torch
-    nch, lmax = plans[0]["mic"].shape[0], max(p["n_len"] for p in plans)
+    nch, lmax = plans[0]["mic"].shape[0], _row_length(plans, lmax)
     noise = np.zeros((len(plans), nch, lmax), np.float32)
     for b, (p, idx) in enumerate(zip(plans, ids)):
         noise[b, :, :p["n_len"]] = numpy_noise(seed, idx, attempt, nch, p["n_len"])
@@ -382,25 +525,51 @@ def host_noise(plans, ids, seed, attempt, device):
 
 
 # ---------------------------------------------------------------------------------------------------------------- the generator
-def simulate_bank(save_to, stage="train", data_num=1024, mic_array_cfg=None, device="cuda", noise="device", batch=16, log=None, **ranges):
+def judge_on_device(rir, n_len, rir_dp, dp_len, T60_specify, ids=None, attempt=0, fs=FS):
+    """The accept test and the annotations of a rendered batch on the GPU (hip.rir_labels, csrc/rirlabel.hip), read back with one small
+    copy: rir (B, nch, lmax) and rir_dp (B, nch, ldmax) device tensors, n_len / dp_len / T60_specify sequences -> numpy dict(t60, corr
+    (B, nch), t60_edc, drr, c50 (B) f64, nd, flags (B) int32; an item is accepted when flags == 3).  ids / attempt name the items (the
+    generators pass them; nothing here depends on them)."""
+    import torch
+    from . import hip
+    dev = rir.device
+    lab = hip.rir_labels(rir, torch.tensor(list(n_len), dtype=torch.int32, device=dev), rir_dp,
+                         torch.tensor(list(dp_len), dtype=torch.int32, device=dev),
+                         torch.tensor([float(t) for t in T60_specify], dtype=torch.float64, device=dev), float(fs))
+    return hip.rir_labels_host(lab)
+
+
+_host_labels = labels            # (simulate_bank has a parameter of that name)
+
+
+def _generator_args(ranges, noise):
+    assert noise in ("device", "numpy")
+    unknown = set(ranges) - set(DEFAULTS)
+    if unknown:
+        raise TypeError("unknown arguments: %s" % sorted(unknown))
+    args = dict(DEFAULTS, **ranges)
+    if args["fs"] != FS:
+        raise ValueError("fs = %s: the renderer's window and frames are defined at %d Hz only" % (args["fs"], FS))
+    return args
+
+
+def simulate_bank(save_to, stage="train", data_num=1024, mic_array_cfg=None, device="cuda", noise="device", batch=16, log=None,
+                  labels="host", **ranges):
     """GenerateRandomRIR (gen_simu.py:38-176): ``data_num`` random configurations of ``stage`` (its seed as there), their RIRs and direct
-    paths rendered in batches on ``device``, the reference's accept test on the host, and per accepted item ``{idx}.npy`` (1, nch, L, 1)
+    paths rendered in batches on ``device``, the reference's accept test, and per accepted item ``{idx}.npy`` (1, nch, L, 1)
     float32, ``{idx}_dp.npy`` and ``{idx}_info.npz`` (configuration, annotations, fs) under ``save_to/stage``, with ``all_info.npz``.
 
+    labels="host": every RIR is read back and judged by ``labels`` on the host; "device": the batch is judged on the GPU
+    (``judge_on_device``) and only accepted RIRs are read back - the same files, T60_edc / DRR / C50 to within parity.RIRLABELS.
     The tail's noise is keyed by (seed, idx, attempt): noise="device" - sarssl_gauss_fill, "numpy" - an uploaded host draw.  An item that
     fails the accept test is rendered again with the next attempt; the reference retries forever, here an item is skipped after
     MAX_ATTEMPTS with a logged line and listed in all_info.npz (SimulatedBank globs ``*_dp.npy``, so a gap is harmless).
     ranges: room_sz_range, T60_range, abs_weights_range, array_pos_ratio_range, num_source_range, source_state, min_src_array_dist,
     min_src_boundary_dist, fs, c, ism_db (DEFAULTS).  -> dict(written=[idx], skipped=[idx], attempts={idx: n})."""
     import torch
-    assert noise in ("device", "numpy")
-    unknown = set(ranges) - set(DEFAULTS)
-    if unknown:
-        raise TypeError("unknown arguments: %s" % sorted(unknown))
-    args = dict(DEFAULTS, **ranges)
+    assert labels in ("host", "device")
+    args = _generator_args(ranges, noise)
     fs, c, ism_db = args["fs"], args["c"], args["ism_db"]
-    if fs != FS:
-        raise ValueError("fs = %s: the renderer's window and frames are defined at %d Hz only" % (fs, FS))
     if stage not in STAGE_SEEDS:
         raise ValueError("unknown stage %r (one of %s)" % (stage, sorted(STAGE_SEEDS)))
     log = log or (lambda s: print(s, file=sys.stderr, flush=True))
@@ -418,6 +587,12 @@ def simulate_bank(save_to, stage="train", data_num=1024, mic_array_cfg=None, dev
         h = t.cpu().numpy()
         return [h[b, :, :p["n_len"]] for b, p in enumerate(plans)]
 
+    def save(idx, rir, T60_edc, TDOA, DRR, C50):
+        np.save(os.path.join(out_dir, "%d.npy" % idx), rir[None, :, :, None].astype(np.float32))
+        np.save(os.path.join(out_dir, "%d_dp.npy" % idx), dps[idx][None, :, :, None].astype(np.float32))
+        np.savez(os.path.join(out_dir, "%d_info.npz" % idx), **dict(cfgs[idx], T60_edc=T60_edc), TDOA=TDOA, DRR=DRR, C50=C50, fs=fs)
+        written.append(idx)
+
     dps = {}
     for i0 in range(0, data_num, batch):
         ids = list(range(i0, min(i0 + batch, data_num)))
@@ -430,18 +605,30 @@ def simulate_bank(save_to, stage="train", data_num=1024, mic_array_cfg=None, dev
             ids = pending[i0:i0 + batch]
             plans = [plan_rir(cfgs[i], fs, c, ism_db) for i in ids]
             has_tail = any(p["n_len"] > p["n_ism"] for p in plans)
-            rirs = read_back(render(plans, dev, make_noise(plans, ids, seed, attempt, dev) if has_tail else None, fs, c), plans)
-            for idx, rir in zip(ids, rirs):
-                lab = labels(rir, dps[idx], cfgs[idx], fs, c)
+            rir_dev = render(plans, dev, make_noise(plans, ids, seed, attempt, dev) if has_tail else None, fs, c)
+            for idx in ids:
                 attempts[idx] = attempt + 1
-                if not lab["ok"]:
-                    failed.append(idx)
-                    continue
-                cfg = dict(cfgs[idx], T60_edc=lab["T60_edc"])
-                np.save(os.path.join(out_dir, "%d.npy" % idx), rir[None, :, :, None].astype(np.float32))
-                np.save(os.path.join(out_dir, "%d_dp.npy" % idx), dps[idx][None, :, :, None].astype(np.float32))
-                np.savez(os.path.join(out_dir, "%d_info.npz" % idx), **cfg, TDOA=lab["TDOA"], DRR=lab["DRR"], C50=lab["C50"], fs=fs)
-                written.append(idx)
+            if labels == "host":
+                for idx, rir in zip(ids, read_back(rir_dev, plans)):
+                    lab = _host_labels(rir, dps[idx], cfgs[idx], fs, c)
+                    if lab["ok"]:
+                        save(idx, rir, lab["T60_edc"], lab["TDOA"], lab["DRR"], lab["C50"])
+                    else:
+                        failed.append(idx)
+                continue
+            ldmax = max(dps[i].shape[1] for i in ids)
+            dp_host = np.zeros((len(ids), rir_dev.shape[1], ldmax), np.float32)
+            for b, i in enumerate(ids):
+                dp_host[b, :, :dps[i].shape[1]] = dps[i]
+            lab = judge_on_device(rir_dev, [p["n_len"] for p in plans], torch.from_numpy(dp_host).to(dev), [dps[i].shape[1] for i in ids],
+                                  [cfgs[i]["T60_specify"] for i in ids], ids, attempt, fs)
+            acc = [b for b in range(len(ids)) if lab["flags"][b] == 3]
+            failed += [ids[b] for b in range(len(ids)) if lab["flags"][b] != 3]
+            if acc:
+                h = rir_dev.index_select(0, torch.tensor(acc, device=dev)).cpu().numpy()          # only accepted RIRs cross the bus
+                for j, b in enumerate(acc):
+                    save(ids[b], h[j, :, :plans[b]["n_len"]], np.float64(lab["t60_edc"][b]), tdoa(cfgs[ids[b]], c),
+                         lab["drr"][b].astype(np.float16), lab["c50"][b].astype(np.float16))
         pending = failed
         if not pending:
             break
@@ -452,16 +639,158 @@ def simulate_bank(save_to, stage="train", data_num=1024, mic_array_cfg=None, dev
     return dict(written=sorted(written), skipped=pending, attempts=attempts)
 
 
+WHITE_STREAM = 1 << 63           # seed bit of the white noise of --mode sig: apart from the RIR tails' (seed | attempt << 32, idx) keys
+
+
+def sig_lmax(T60_range, fs=FS):
+    """The fixed row length --mode sig renders every RIR at: n_len = ceil(40 / 60 T60_sabine fs) of the largest T60_sabine the accepted
+    rooms can have (the room draw keeps |T60_sabine - T60_specify| < 0.005)."""
+    return int(math.ceil(att2t(40, float(max(T60_range)) + 0.005) * fs)) + 1
+
+
+def simulate_signals(save_to, stage="pretrain", data_num=1, src_dir="", mic_array_cfg=None, device="cuda", noise="device", batch=16,
+                     T=4.112, snr_range=(15, 30), sort_sources=False, nthreads=0, log=None, **ranges):
+    """GenerateRandomMicSig (gen_simu.py:178-360) with generate_microphone_signal (utils_simu_rir_sig.py:749-861): ``data_num`` items of
+    ``stage`` (pretrain | preval | pretest | pretest_ins*: its seed, and src_dir + /tr | /dt | /et, as there) as ``{idx}.wav`` PCM-16
+    (int(T fs), nch) and ``{idx}_info.npz`` (configuration, T60_edc, SNR, src_idx, TDOA / DRR / C50 with the reference's dtypes) under
+    ``save_to/stage``, with ``all_info.npz`` as in ``simulate_bank``.
+
+    Per batch, on a side stream and without the RIR ever leaving the device: ``render`` of the direct paths and the RIRs (tail noise
+    keyed by (seed, idx, attempt)), ``judge_on_device``, one small read-back of the labels, a gather of the accepted items, the white
+    noise (noise="device": sarssl_gauss_fill keyed by (seed, idx); "numpy": the reference's host draw, uploaded), hip.diffuse_noise with
+    the item's mixing table, hip.rir_mix against the direct path at gain 0.9, hip.pcm16_pack, a copy to a pinned buffer.  A writer thread
+    then writes the batch's files (dataset.write_wav_batch, np.savez) while the next batch renders.  Rejected items go to the next
+    attempt; after MAX_ATTEMPTS an item is skipped with a logged line and listed in all_info.npz.
+
+    An item's files are a function of (seed, idx, attempt, the source files) alone, not of the batch it was rendered in: hip.rir_mix
+    partitions its RIRs by the row length it is given, so every batch is rendered at the one row length ``sig_lmax(T60_range)``.
+    The host plans an item once (plan_sig: it reads the utterances) while the GPU renders, and keeps the plan across attempts.
+    -> dict(written=[idx], skipped=[idx], attempts={idx: n})."""
+    import torch
+    from concurrent.futures import ThreadPoolExecutor
+    from . import hip, rirsynth
+    from .dataset import write_wav_batch
+    args = _generator_args(ranges, noise)
+    fs, c, ism_db = args["fs"], args["c"], args["ism_db"]
+    base = sig_stage(stage)
+    seed = SIG_STAGE_SEEDS[base]
+    ns = int(T * fs)
+    if ns <= 0 or ns % 64 != 0:
+        raise ValueError("T = %s: int(T fs) = %d samples is not a multiple of 64, which the diffuse-noise kernel's frames need" % (T, ns))
+    log = log or (lambda s: print(s, file=sys.stderr, flush=True))
+    mic_array_cfg = MIC_ARRAY_CFG_2CH if mic_array_cfg is None else mic_array_cfg
+    nmic = mic_array_cfg["mic_pos_relative"].shape[0]
+    sources = rirsynth.SourceBank(src_dir + "/" + SIG_SRC_SUBDIR[base], fs, sort=sort_sources)
+    out_dir = os.path.join(save_to, stage)
+    os.makedirs(out_dir, exist_ok=True)
+    rs = np.random.RandomState()
+    draw = {k: args[k] for k in DEFAULTS if k != "fs"}
+    cfgs = [random_spatial_acoustics(rs, seed, idx, mic_array_cfg=mic_array_cfg, **draw) for idx in range(data_num)]
+    dev = torch.device(device)
+    make_noise = device_noise if noise == "device" else host_noise
+    lmax = sig_lmax(args["T60_range"], fs)
+    side = torch.cuda.Stream(dev)
+    pinned = [torch.empty((batch, ns, nmic), dtype=torch.int16, pin_memory=True) for _ in range(2)]
+    busy = [None, None]                                       # the writer job that still reads each pinned buffer
+    sig_plans, written, attempts = {}, [], {}
+
+    def plan(idx):
+        if idx not in sig_plans:
+            p = plan_sig(rs, idx, seed, cfgs[idx], sources, T, snr_range, nmic, draw_white=noise == "numpy", fs=fs)
+            p["C"] = rirsynth.mixing_table(cfgs[idx]["mic_pos"], fs, c).astype(np.float32)
+            sig_plans[idx] = p
+        return sig_plans[idx]
+
+    def write(ev, buf, ids, infos):
+        ev.synchronize()
+        write_wav_batch([os.path.join(out_dir, "%d.wav" % i) for i in ids], buf[:len(ids)], fs, nthreads)
+        for i, info in zip(ids, infos):
+            np.savez(os.path.join(out_dir, "%d_info.npz" % i), **info)
+
+    pending, nbatch = list(range(data_num)), 0
+    with ThreadPoolExecutor(max_workers=1) as writer, torch.cuda.stream(side):
+        for attempt in range(MAX_ATTEMPTS):
+            failed = []
+            for i0 in range(0, len(pending), batch):
+                ids = pending[i0:i0 + batch]
+                plans_dp = [plan_rir(cfgs[i], fs, c, ism_db, dp=True) for i in ids]
+                plans = [plan_rir(cfgs[i], fs, c, ism_db) for i in ids]
+                has_tail = any(p["n_len"] > p["n_ism"] for p in plans)
+                dp_dev = render(plans_dp, dev, None, fs, c)
+                rir_dev = render(plans, dev, make_noise(plans, ids, seed, attempt, dev, lmax) if has_tail else None, fs, c, lmax)
+                for idx in ids:
+                    attempts[idx] = attempt + 1
+                    plan(idx)                                 # (host work while the GPU renders)
+                lab = judge_on_device(rir_dev, [p["n_len"] for p in plans], dp_dev, [p["n_len"] for p in plans_dp],
+                                      [cfgs[i]["T60_specify"] for i in ids], ids, attempt, fs)
+                acc = [b for b in range(len(ids)) if lab["flags"][b] == 3]
+                failed += [ids[b] for b in range(len(ids)) if lab["flags"][b] != 3]
+                if not acc:
+                    continue
+                A, aids = len(acc), [ids[b] for b in acc]
+                if A < len(ids):
+                    sel = torch.tensor(acc, device=dev)
+                    rir_dev, dp_dev = rir_dev.index_select(0, sel), dp_dev.index_select(0, sel)
+                host = torch.empty((A, ns + 129 * nmic * nmic + 1), dtype=torch.float32, pin_memory=True)      # src | C | snr of each item
+                hn = host.numpy()
+                for j, i in enumerate(aids):
+                    hn[j, :ns], hn[j, ns:-1], hn[j, -1] = sig_plans[i]["src"], sig_plans[i]["C"].reshape(-1), sig_plans[i]["snr"]
+                up = host.to(dev, non_blocking=True)
+                if noise == "numpy":
+                    white = torch.from_numpy(np.stack([sig_plans[i]["white"] for i in aids]).astype(np.float32)).to(dev)
+                else:
+                    white = torch.empty((A, ns, nmic), dtype=torch.float32, device=dev)
+                    for j, i in enumerate(aids):
+                        hip.gauss_fill(white[j:j + 1], (int(seed) & 0xffffffff) | WHITE_STREAM, int(i))
+                field = hip.diffuse_noise(white, up[:, ns:-1].reshape(A, 129, nmic, nmic).contiguous(), out=white)
+                mic = hip.rir_mix(up[:, :ns].contiguous(), rir_dev, torch.tensor([plans[b]["n_len"] for b in acc], dtype=torch.int32, device=dev),
+                                  up[:, -1].contiguous(), torch.full((A,), PCM_GAIN, dtype=torch.float32, device=dev), rir_dp=dp_dev,
+                                  dp_len=torch.tensor([plans_dp[b]["n_len"] for b in acc], dtype=torch.int32, device=dev), noise=field)
+                pcm = hip.pcm16_pack(mic)
+                k = nbatch % 2
+                nbatch += 1
+                if busy[k] is not None:
+                    busy[k].result()                          # the buffer's previous batch is on disk
+                pinned[k][:A].copy_(pcm, non_blocking=True)
+                ev = torch.cuda.Event()
+                ev.record(side)
+                infos = [sig_info(cfgs[ids[b]], sig_plans[ids[b]], lab["t60_edc"][b], lab["drr"][b], lab["c50"][b], c) for b in acc]
+                busy[k] = writer.submit(write, ev, pinned[k], aids, infos)
+                written += aids
+                for i in aids:
+                    del sig_plans[i]
+            pending = failed
+            if not pending:
+                break
+        for f in busy:
+            if f is not None:
+                f.result()
+    for idx in pending:
+        log("simulate_signals: item %d of stage %s failed the accept test %d times and is skipped" % (idx, stage, MAX_ATTEMPTS))
+    np.savez_compressed(os.path.join(out_dir, "all_info.npz"),
+                        args=dict(args, stage=stage, data_num=data_num, seed=seed, noise=noise, T=T, snr_range=tuple(snr_range), src_dir=src_dir),
+                        cfgs=cfgs, skipped=np.array(pending, np.int64))
+    return dict(written=sorted(written), skipped=pending, attempts=attempts)
+
+
 # ---------------------------------------------------------------------------------------------------------------- command line
 def _literal(text):
     import ast
     return ast.literal_eval(text)
 
 
+def _flag(text):
+    if text in ("True", "true", "1"):
+        return True
+    if text in ("False", "false", "0"):
+        return False
+    raise ValueError(text)
+
+
 def main(argv=None):
-    """``gen_simu.py --mode rir`` with the reference's flag names (argparse; lists are written as Python literals, e.g. --gpus [0])."""
+    """``gen_simu.py --mode rir | sig`` with the reference's flag names (argparse; lists are written as Python literals, e.g. --gpus [0])."""
     import argparse
-    ap = argparse.ArgumentParser(description="Generate simulated RIRs (image-source model on the GPU)")
+    ap = argparse.ArgumentParser(description="Generate simulated RIRs or microphone signals (image-source model on the GPU)")
     ap.add_argument("--mode", type=str, default="rir")
     ap.add_argument("--stage", type=str, default="train")
     ap.add_argument("--data_num", type=int, default=1024)
@@ -482,9 +811,32 @@ def main(argv=None):
     ap.add_argument("--mic_array", type=str, default="2ch", choices=sorted(MIC_ARRAYS))
     ap.add_argument("--noise", type=str, default="device", choices=("device", "numpy"))
     ap.add_argument("--batch", type=int, default=16)
+    ap.add_argument("--labels", type=str, default="host", choices=("host", "device"), help="--mode rir: where the accept test runs")
+    # --mode sig
+    ap.add_argument("--src_dir", type=str, default="")
+    ap.add_argument("--snr_range", type=_literal, default=(15, 30))
+    ap.add_argument("--noise_type", type=str, default="diffuse_white")
+    ap.add_argument("--T", type=float, default=4.112)
+    ap.add_argument("--save_dp", type=_flag, default=False)
+    ap.add_argument("--gpu_conv", type=_flag, default=False)
     a = ap.parse_args(argv)
-    if a.mode != "rir":
-        ap.error("--mode %s: only --mode rir is built (microphone signals come from run_downstream.py's loader, not from files)" % a.mode)
+    if a.mode not in ("rir", "sig"):
+        ap.error("--mode %s: only --mode rir and --mode sig are built" % a.mode)
+    if a.mode == "sig":
+        try:
+            sig_stage(a.stage)
+        except ValueError as e:
+            ap.error(str(e))
+        if a.save_dp:
+            ap.error("--save_dp True: the direct-path signal is not written (the mix kernel never stores it)")
+        if a.noise_type != "diffuse_white":
+            ap.error("--noise_type %s: diffuse_white only" % a.noise_type)
+        if a.gpu_conv:
+            ap.error("--gpu_conv True: the trajectory convolution of moving sources is not built; static sources are convolved on the GPU anyway")
+        if int(a.T * a.fs) <= 0 or int(a.T * a.fs) % 64 != 0:
+            ap.error("--T %s: int(T fs) = %d samples is not a multiple of 64, which the diffuse-noise kernel's frames need" % (a.T, int(a.T * a.fs)))
+        if not a.src_dir:
+            ap.error("--src_dir is required with --mode sig")
     if "moving" in a.source_state or a.source_state != "static":
         ap.error("--source_state %s: static sources only" % a.source_state)
     if tuple(a.num_source_range) != (1, 1):
@@ -498,9 +850,15 @@ def main(argv=None):
     gpus = a.gpus if isinstance(a.gpus, (list, tuple)) else [a.gpus]
     import torch
     torch.cuda.set_device(int(gpus[0]))                  # one process on the first listed GPU
+    ranges = dict(room_sz_range=a.room_sz_range, T60_range=a.T60_range, abs_weights_range=a.abs_weights_range,
+                  array_pos_ratio_range=a.array_pos_ratio_range, num_source_range=a.num_source_range, source_state=a.source_state,
+                  min_src_array_dist=a.min_src_array_dist, min_src_boundary_dist=a.min_src_boundary_dist, c=a.c, ism_db=a.ism_db)
+    if a.mode == "sig":
+        res = simulate_signals(a.save_to, a.stage, a.data_num, a.src_dir, MIC_ARRAYS[a.mic_array], device="cuda:%d" % int(gpus[0]),
+                               noise=a.noise, batch=a.batch, T=a.T, snr_range=tuple(a.snr_range), **ranges)
+        print("%d microphone signals written to %s, %d skipped" % (len(res["written"]), os.path.join(a.save_to, a.stage), len(res["skipped"])))
+        return 0
     res = simulate_bank(a.save_to, a.stage, a.data_num, MIC_ARRAYS[a.mic_array], device="cuda:%d" % int(gpus[0]), noise=a.noise, batch=a.batch,
-                        room_sz_range=a.room_sz_range, T60_range=a.T60_range, abs_weights_range=a.abs_weights_range,
-                        array_pos_ratio_range=a.array_pos_ratio_range, num_source_range=a.num_source_range, source_state=a.source_state,
-                        min_src_array_dist=a.min_src_array_dist, min_src_boundary_dist=a.min_src_boundary_dist, c=a.c, ism_db=a.ism_db)
+                        labels=a.labels, **ranges)
     print("%d RIRs written to %s, %d skipped" % (len(res["written"]), os.path.join(a.save_to, a.stage), len(res["skipped"])))
     return 0
