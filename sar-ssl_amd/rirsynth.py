@@ -3,9 +3,9 @@
 The reference builds every training item of its real-world room-acoustics experiment on the fly in DataLoader workers
 (RandomMicSigFromRIRDataset, code/dataset.py:287-382): a source utterance convolved with a measured or a simulated RIR, noise scaled
 to a drawn SNR against the direct-path power, peak normalisation.  Here the host only picks files and draws scalars (``plan_*``: the
-reference's numpy draw order, call for call) and the GPU renders whole batches (hip.rir_mix / diffuse_noise / gauss_fill,
-csrc/rirmix.hip).  ``restate_*`` are the f64 numpy / scipy restatement of one item that the kernels and the reference fixture are
-checked against.
+reference's numpy draw order, call for call; ``draw_item`` is the part all items share, roomsim.plan_sig's too) and the GPU renders whole
+batches (hip.rir_mix / diffuse_noise / gauss_fill, csrc/rirmix.hip; ``mix_simulated`` is also roomsim.simulate_signals' mix).
+``restate_*`` are the f64 numpy / scipy restatement of one item that the kernels and the reference fixture are checked against.
 """
 import math
 import os
@@ -263,9 +263,19 @@ class SimulatedBank:
 
 
 # ---------------------------------------------------------------------------------------------------------------- host plans
+def draw_item(rs, sources, T, fs=FS, snr_range=(15, 30), nmic=2, draw_white=False):
+    """The draws every kind of item ends with, on ``rs`` where it stands: source index, SourceBank.draw (utterance index, crop start), with
+    draw_white=True the white noise (int(T fs), nmic), the SNR -> SourceBank.draw's record with src_idx, src, white (or None) and snr."""
+    src_idx = int(rs.randint(0, len(sources)))
+    src, rec = sources.draw(rs, src_idx, int(T * fs))
+    white = rs.standard_normal((int(T * fs), nmic)) if draw_white else None
+    snr = float(rs.uniform(*snr_range))
+    return dict(rec, src_idx=src_idx, src=src, white=white, snr=snr)
+
+
 def plan_measured(rs, idx, seed, bank, sources, T, fs=FS, snr_range=(15, 30)):
     """real_dataset.MicSigFromRIRDataset.__getitem__'s draws (gen_sig_from_real_rir.py:215-236) on the RandomState ``rs``: seed + idx,
-    RIR index, noise file and its start sample, source index, utterance index, crop start, SNR."""
+    RIR index, noise file and its start sample, then ``draw_item`` without white noise."""
     rs.seed(seed + idx)
     rir_idx = int(rs.randint(0, len(bank)))
     noise_file, noise_start = None, 0
@@ -276,24 +286,17 @@ def plan_measured(rs, idx, seed, bank, sources, T, fs=FS, snr_range=(15, 30)):
         nsample_noise, want = int(frames / nfs * nfs), int(T * nfs)
         assert nsample_noise >= want, "the sample number of noise signal is smaller than desired duration~"
         noise_start = int(rs.randint(0, nsample_noise - want + 1))
-    src_idx = int(rs.randint(0, len(sources)))
-    src, rec = sources.draw(rs, src_idx, int(T * fs))
-    snr = float(rs.uniform(*snr_range))
-    return dict(rec, variant="measured", idx=idx, rir_idx=rir_idx, rir_file=bank.files[rir_idx], noise_file=noise_file,
-                noise_start=noise_start, src_idx=src_idx, src=src, snr=snr, white=None, labels=bank.labels[rir_idx])
+    return dict(draw_item(rs, sources, T, fs, snr_range), variant="measured", idx=idx, rir_idx=rir_idx, rir_file=bank.files[rir_idx],
+                noise_file=noise_file, noise_start=noise_start, labels=bank.labels[rir_idx])
 
 
 def plan_simulated(rs, idx, seed, bank, sources, T, fs=FS, snr_range=(15, 30), nmic=2, draw_white=True):
-    """simu_dataset.MicSigFromRIRDataset.__getitem__'s draws (utils_simu_rir_sig.py:1203-1223): seed + idx, RIR index, source index,
-    utterance index, crop start, the white noise (left out with draw_white=False: the device draws its own), SNR."""
+    """simu_dataset.MicSigFromRIRDataset.__getitem__'s draws (utils_simu_rir_sig.py:1203-1223): seed + idx, RIR index, then ``draw_item``
+    (the white noise is left out with draw_white=False: the device draws its own)."""
     rs.seed(seed + idx)
     rir_idx = int(rs.randint(0, len(bank)))
-    src_idx = int(rs.randint(0, len(sources)))
-    src, rec = sources.draw(rs, src_idx, int(T * fs))
-    white = rs.standard_normal((int(T * fs), nmic)) if draw_white else None
-    snr = float(rs.uniform(*snr_range))
-    return dict(rec, variant="simulated", idx=idx, rir_idx=rir_idx, rir_file=bank.files[rir_idx], noise_file=None, noise_start=0,
-                src_idx=src_idx, src=src, snr=snr, white=white, labels=bank.labels[rir_idx])
+    return dict(draw_item(rs, sources, T, fs, snr_range, nmic, draw_white), variant="simulated", idx=idx, rir_idx=rir_idx,
+                rir_file=bank.files[rir_idx], noise_file=None, noise_start=0, labels=bank.labels[rir_idx])
 
 
 def variants_of(real_sim_ratio):
@@ -333,6 +336,15 @@ def read_noise(path, start, nsample, nch, fs=FS):
 
 
 # ---------------------------------------------------------------------------------------------------------------- batch loader
+def mix_simulated(src, rir, rir_len, dp, dp_len, white, C, snr, gain, out=None):
+    """The mix of a batch of simulated items on the current stream: ``white`` (B, Ns, nch) becomes, in place, the diffuse field of the
+    mixing tables C (B, 129, nch, nch), and hip.rir_mix adds it to src * rir at snr dB against the direct path dp -> (B, Ns, nch).
+    Where ``white`` comes from stays with the caller: the loader and roomsim.simulate_signals key their device draws differently."""
+    from . import hip
+    field = hip.diffuse_noise(white, C, out=white)
+    return hip.rir_mix(src, rir, rir_len, snr, gain, rir_dp=dp, dp_len=dp_len, noise=field, out=out)
+
+
 class RirSynthLoader:
     """Batches of RandomMicSigFromRIRDataset items, rendered on the GPU: yields ``(mic_sig (B, Ns, nch) f32 on the device,
     {task: (B,) f32 tensor})`` in the shape Learner.train_epoch / test_epoch iterate.
@@ -442,10 +454,9 @@ class RirSynthLoader:
                     white = h["white"].to(dev, non_blocking=True)
                 else:
                     white = hip.gauss_fill(torch.empty((len(ids), self.nsample, self.nmic), dtype=torch.float32, device=dev), self.seed, item0)
-                noise = hip.diffuse_noise(white, bank.dev_C.index_select(0, r).contiguous(), out=white)
                 ldmax = int(max(bank.dps[h["plans"][i]["rir_idx"]].shape[1] for i in ids))
-                hip.rir_mix(pick(src), rir, lens, pick(scal[0]), pick(scal[1]), rir_dp=bank.dev_dp.index_select(0, r)[:, :, :ldmax].contiguous(),
-                            dp_len=bank.dev_dplen.index_select(0, r), noise=noise, out=dst)
+                mix_simulated(pick(src), rir, lens, bank.dev_dp.index_select(0, r)[:, :, :ldmax].contiguous(), bank.dev_dplen.index_select(0, r),
+                              white, bank.dev_C.index_select(0, r).contiguous(), pick(scal[0]), pick(scal[1]), out=dst)
             if not whole:
                 out.index_copy_(0, sel, dst)
         labels = {k: v.to(dev, non_blocking=True) for k, v in h["labels"].items()}

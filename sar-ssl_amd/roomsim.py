@@ -12,11 +12,13 @@ the same RIRs judged on the device (hip.rir_labels, csrc/rirlabel.hip - ``labels
 WSJ0-style source, mixed with the diffuse white-noise field at a drawn SNR, converted to PCM-16 and written as ``{idx}.wav`` +
 ``{idx}_info.npz`` without the RIR leaving the GPU; ``plan_sig`` restates the reference's draws and ``restate_sig`` one item in f64
 (fixture F22, tools/make_golden_simsig.py).  The float -> PCM-16 rule is this project's reading of libsndfile's and UNPINNED (``pcm16``).
+Both generators are one loop (``_generate``: ``render_items``, the judge on the host or the device, retries) with their own sink.
 
 PARITY WITH gpuRIR IS UNPINNED: the library cannot be run or read, so the RIR is this project's own image-source model (Allen-Berkley
 images, 8 ms Hann-windowed sinc fractional delays, an exponentially decaying noise tail at the Sabine slope).  What is pinned against the
 reference is its own code around the call (fixture F21, tools/make_golden_ism.py).
 """
+import collections
 import math
 import os
 import sys
@@ -298,9 +300,7 @@ def annotations(rir, rir_dp, cfg, fs=FS, c=343.0, eps=1e-8):
     """generate_annotation(TDOA, DRR, C50, src_single_static=True) (utils_simu_rir_sig.py:863-994) for rir (nch, L), rir_dp (nch, Ld):
     TDOA float32, DRR and C50 float16, of the reference channel."""
     rir, rir_dp = np.asarray(rir, np.float64), np.asarray(rir_dp, np.float64)
-    mic, src = np.asarray(cfg["mic_pos"], np.float64), np.asarray(cfg["src_traj_pts"], np.float64)[0, :, 0]
-    dist = np.sqrt(np.sum((src[None, :] - mic) ** 2, axis=1))
-    out = {"TDOA": ((dist[1] - dist[0]) / c).astype(np.float32)}
+    out = {"TDOA": tdoa(cfg, c)}
     nsamp = max(rir.shape[1], rir_dp.shape[1])
     h = np.concatenate([rir[0], np.zeros(nsamp - rir.shape[1])])
     nd = np.argmax(np.concatenate([rir_dp[0], np.zeros(nsamp - rir_dp.shape[1])]))
@@ -425,15 +425,20 @@ def pcm16(x):
 
 
 def plan_sig(rs, idx, seed, cfg, sources, T, snr_range=(15, 30), nmic=2, draw_white=True, fs=FS):
-    """generate_microphone_signal's draws (utils_simu_rir_sig.py:749-816) on the RandomState ``rs`` after seed + idx: speaker index,
-    SourceBank.draw (utterance, same-speaker padding, crop, mean removal), the white noise (int(T fs), nmic) - left out with
-    draw_white=False: the device draws its own -, the SNR."""
+    """generate_microphone_signal's draws (utils_simu_rir_sig.py:749-816) on the RandomState ``rs`` after seed + idx: rirsynth.draw_item
+    - speaker index, SourceBank.draw (utterance, same-speaker padding, crop, mean removal), the white noise (int(T fs), nmic), left out
+    with draw_white=False: the device draws its own, and the SNR."""
+    from . import rirsynth
     rs.seed(seed + idx)
-    src_idx = int(rs.randint(0, len(sources)))
-    src, rec = sources.draw(rs, src_idx, int(T * fs))
-    white = rs.standard_normal((int(T * fs), nmic)) if draw_white else None
-    snr = float(rs.uniform(*snr_range))
-    return dict(rec, idx=idx, cfg=cfg, src_idx=src_idx, src=src, white=white, snr=snr)
+    return dict(rirsynth.draw_item(rs, sources, T, fs, snr_range, nmic, draw_white), idx=idx, cfg=cfg)
+
+
+def sig_samples(T, fs=FS, name="T ="):
+    """int(T fs), the samples of an item of --mode sig, or ValueError where the diffuse-noise kernel's frames cannot take it."""
+    ns = int(T * fs)
+    if ns <= 0 or ns % 64 != 0:
+        raise ValueError("%s %s: int(T fs) = %d samples is not a multiple of 64, which the diffuse-noise kernel's frames need" % (name, T, ns))
+    return ns
 
 
 def restate_sig(plan, tail_noise=None, rir=None, rir_dp=None, pcm=True, fs=FS, c=343.0, ism_db=12):
@@ -524,6 +529,24 @@ def host_noise(plans, ids, seed, attempt, device, lmax=None):
     return torch.from_numpy(noise).to(device)
 
 
+Rendered = collections.namedtuple("Rendered", "ids plans plans_dp rir dp")
+
+
+def render_items(cfgs, ids, seed, attempt, device, noise="device", lmax=None, fs=FS, c=343.0, ism_db=12):
+    """The render batch of the image-source model, enqueued on the current stream: ``plan_rir`` of cfgs[i] and of its direct path for
+    every i of ``ids``, the tail's noise keyed by (seed, i, attempt) - noise="device": ``device_noise``, "numpy": ``host_noise``; drawn
+    only when some plan has a tail - and the two ``render`` calls -> Rendered(ids, plans, plans_dp, rir (B, nch, lmax), dp (B, nch, 1600)),
+    both tensors on the device.  lmax: the RIRs' row length (default: the longest of the batch)."""
+    assert noise in ("device", "numpy")
+    ids = list(ids)
+    plans_dp = [plan_rir(cfgs[i], fs, c, ism_db, dp=True) for i in ids]
+    plans = [plan_rir(cfgs[i], fs, c, ism_db) for i in ids]
+    dp = render(plans_dp, device, None, fs, c)
+    has_tail = any(p["n_len"] > p["n_ism"] for p in plans)
+    tail = (device_noise if noise == "device" else host_noise)(plans, ids, seed, attempt, device, lmax) if has_tail else None
+    return Rendered(ids, plans, plans_dp, render(plans, device, tail, fs, c, lmax), dp)
+
+
 # ---------------------------------------------------------------------------------------------------------------- the generator
 def judge_on_device(rir, n_len, rir_dp, dp_len, T60_specify, ids=None, attempt=0, fs=FS):
     """The accept test and the annotations of a rendered batch on the GPU (hip.rir_labels, csrc/rirlabel.hip), read back with one small
@@ -539,7 +562,15 @@ def judge_on_device(rir, n_len, rir_dp, dp_len, T60_specify, ids=None, attempt=0
     return hip.rir_labels_host(lab)
 
 
-_host_labels = labels            # (simulate_bank has a parameter of that name)
+def judge_on_host(batch, cfgs, fs=FS, c=343.0):
+    """The same of a ``render_items`` batch by ``labels`` on the host -> numpy dict(flags (B) int32, t60_edc (B) f64, drr, c50 (B) float16
+    as ``labels`` rounds them) with the read-back batch beside them: rir (B, nch, lmax), dp (B, nch, 1600)."""
+    rir, dp = batch.rir.cpu().numpy(), batch.dp.cpu().numpy()
+    labs = [labels(rir[b, :, :p["n_len"]], dp[b, :, :pd["n_len"]], cfgs[idx], fs, c)
+            for b, (idx, p, pd) in enumerate(zip(batch.ids, batch.plans, batch.plans_dp))]
+    return dict(flags=np.array([int(lab["rir_ok"]) | (int(lab["env_ok"]) << 1) for lab in labs], np.int32),
+                t60_edc=np.array([lab["T60_edc"] for lab in labs], np.float64), drr=np.array([lab["DRR"] for lab in labs], np.float16),
+                c50=np.array([lab["C50"] for lab in labs], np.float16), rir=rir, dp=dp)
 
 
 def _generator_args(ranges, noise):
@@ -553,90 +584,91 @@ def _generator_args(ranges, noise):
     return args
 
 
+def _rooms(save_to, stage, seed, data_num, mic_array_cfg, args):
+    """The output directory of a stage, created, and its ``data_num`` room draws -> (out_dir, cfgs)."""
+    out_dir = os.path.join(save_to, stage)
+    os.makedirs(out_dir, exist_ok=True)
+    rs = np.random.RandomState()
+    draw = {k: args[k] for k in DEFAULTS if k != "fs"}
+    return out_dir, [random_spatial_acoustics(rs, seed, idx, mic_array_cfg=mic_array_cfg, **draw) for idx in range(data_num)]
+
+
+def read_back_accepted(batch, acc, lab):
+    """The RIRs and direct paths at the positions ``acc`` of a batch as numpy (A, nch, lmax), (A, nch, 1600): from the judge's read-back
+    where it judged on the host; else gathered on the device, so that only accepted items cross the bus."""
+    if "rir" in lab:
+        return lab["rir"][acc], lab["dp"][acc]
+    return batch.rir[acc].cpu().numpy(), batch.dp[acc].cpu().numpy()
+
+
+def _generate(who, out_dir, stage, cfgs, seed, args, device, noise, batch, where, sink, log=None, prepare=None, lmax=None, **recorded):
+    """The loop of both generators: the pending items are rendered in batches (``render_items``), judged (where="host": ``judge_on_host``,
+    "device": ``judge_on_device``) and, where accepted (flags == 3), handed to ``sink(batch, accepted positions, labels) -> ids written``;
+    the others are rendered again with the next attempt's noise and skipped with a logged line after MAX_ATTEMPTS.  ``prepare(ids)`` runs
+    between the enqueue of a batch's renders and the wait for its labels: host work there overlaps the render.  all_info.npz (``args``,
+    the stage's and ``recorded``; every configuration; the skipped ids) is written unless out_dir is None.  -> dict(written, skipped, attempts)."""
+    fs, c = args["fs"], args["c"]
+    log = log or (lambda s: print(s, file=sys.stderr, flush=True))
+    pending, written, attempts = list(range(len(cfgs))), [], {}
+    for attempt in range(MAX_ATTEMPTS):
+        failed = []
+        for i0 in range(0, len(pending), batch):
+            b = render_items(cfgs, pending[i0:i0 + batch], seed, attempt, device, noise, lmax, fs, c, args["ism_db"])
+            attempts.update((idx, attempt + 1) for idx in b.ids)
+            if prepare is not None:
+                prepare(b.ids)
+            if where == "host":
+                lab = judge_on_host(b, cfgs, fs, c)
+            else:
+                lab = judge_on_device(b.rir, [p["n_len"] for p in b.plans], b.dp, [p["n_len"] for p in b.plans_dp],
+                                      [cfgs[idx]["T60_specify"] for idx in b.ids], b.ids, attempt, fs)
+            acc = [j for j in range(len(b.ids)) if lab["flags"][j] == 3]
+            failed += [b.ids[j] for j in range(len(b.ids)) if lab["flags"][j] != 3]
+            if acc:
+                written += sink(b, acc, lab)
+        pending = failed
+        if not pending:
+            break
+    for idx in pending:
+        log("%s: item %d of stage %s failed the accept test %d times and is skipped" % (who, idx, stage, MAX_ATTEMPTS))
+    if out_dir is not None:
+        info = dict(args, stage=stage, data_num=len(cfgs), seed=seed, noise=noise, **recorded)
+        np.savez_compressed(os.path.join(out_dir, "all_info.npz"), args=info, cfgs=cfgs, skipped=np.array(pending, np.int64))
+    return dict(written=sorted(written), skipped=pending, attempts=attempts)
+
+
 def simulate_bank(save_to, stage="train", data_num=1024, mic_array_cfg=None, device="cuda", noise="device", batch=16, log=None,
                   labels="host", **ranges):
     """GenerateRandomRIR (gen_simu.py:38-176): ``data_num`` random configurations of ``stage`` (its seed as there), their RIRs and direct
     paths rendered in batches on ``device``, the reference's accept test, and per accepted item ``{idx}.npy`` (1, nch, L, 1)
     float32, ``{idx}_dp.npy`` and ``{idx}_info.npz`` (configuration, annotations, fs) under ``save_to/stage``, with ``all_info.npz``.
 
-    labels="host": every RIR is read back and judged by ``labels`` on the host; "device": the batch is judged on the GPU
-    (``judge_on_device``) and only accepted RIRs are read back - the same files, T60_edc / DRR / C50 to within parity.RIRLABELS.
+    labels="host": the batch is read back and judged by ``labels`` on the host (``judge_on_host``); "device": it is judged on the GPU
+    (``judge_on_device``) and only accepted items are read back - the same files, T60_edc / DRR / C50 to within parity.RIRLABELS.
     The tail's noise is keyed by (seed, idx, attempt): noise="device" - sarssl_gauss_fill, "numpy" - an uploaded host draw.  An item that
     fails the accept test is rendered again with the next attempt; the reference retries forever, here an item is skipped after
     MAX_ATTEMPTS with a logged line and listed in all_info.npz (SimulatedBank globs ``*_dp.npy``, so a gap is harmless).
     ranges: room_sz_range, T60_range, abs_weights_range, array_pos_ratio_range, num_source_range, source_state, min_src_array_dist,
     min_src_boundary_dist, fs, c, ism_db (DEFAULTS).  -> dict(written=[idx], skipped=[idx], attempts={idx: n})."""
-    import torch
     assert labels in ("host", "device")
     args = _generator_args(ranges, noise)
-    fs, c, ism_db = args["fs"], args["c"], args["ism_db"]
+    fs, c = args["fs"], args["c"]
     if stage not in STAGE_SEEDS:
         raise ValueError("unknown stage %r (one of %s)" % (stage, sorted(STAGE_SEEDS)))
-    log = log or (lambda s: print(s, file=sys.stderr, flush=True))
     seed = STAGE_SEEDS[stage]
-    mic_array_cfg = MIC_ARRAY_CFG_2CH if mic_array_cfg is None else mic_array_cfg
-    out_dir = os.path.join(save_to, stage)
-    os.makedirs(out_dir, exist_ok=True)
-    rs = np.random.RandomState()
-    draw = {k: args[k] for k in DEFAULTS if k != "fs"}
-    cfgs = [random_spatial_acoustics(rs, seed, idx, mic_array_cfg=mic_array_cfg, **draw) for idx in range(data_num)]
-    dev = torch.device(device)
-    make_noise = device_noise if noise == "device" else host_noise
+    out_dir, cfgs = _rooms(save_to, stage, seed, data_num, mic_array_cfg, args)
 
-    def read_back(t, plans):
-        h = t.cpu().numpy()
-        return [h[b, :, :p["n_len"]] for b, p in enumerate(plans)]
+    def sink(batch, acc, lab):
+        rir, dp = read_back_accepted(batch, acc, lab)
+        for j, b in enumerate(acc):
+            idx = batch.ids[b]
+            np.save(os.path.join(out_dir, "%d.npy" % idx), rir[j, :, :batch.plans[b]["n_len"]][None, :, :, None].astype(np.float32))
+            np.save(os.path.join(out_dir, "%d_dp.npy" % idx), dp[j, :, :batch.plans_dp[b]["n_len"]][None, :, :, None].astype(np.float32))
+            np.savez(os.path.join(out_dir, "%d_info.npz" % idx), **dict(cfgs[idx], T60_edc=np.float64(lab["t60_edc"][b])), TDOA=tdoa(cfgs[idx], c),
+                     DRR=lab["drr"][b].astype(np.float16), C50=lab["c50"][b].astype(np.float16), fs=fs)
+        return [batch.ids[b] for b in acc]
 
-    def save(idx, rir, T60_edc, TDOA, DRR, C50):
-        np.save(os.path.join(out_dir, "%d.npy" % idx), rir[None, :, :, None].astype(np.float32))
-        np.save(os.path.join(out_dir, "%d_dp.npy" % idx), dps[idx][None, :, :, None].astype(np.float32))
-        np.savez(os.path.join(out_dir, "%d_info.npz" % idx), **dict(cfgs[idx], T60_edc=T60_edc), TDOA=TDOA, DRR=DRR, C50=C50, fs=fs)
-        written.append(idx)
-
-    dps = {}
-    for i0 in range(0, data_num, batch):
-        ids = list(range(i0, min(i0 + batch, data_num)))
-        plans = [plan_rir(cfgs[i], fs, c, ism_db, dp=True) for i in ids]
-        dps.update(zip(ids, read_back(render(plans, dev, None, fs, c), plans)))
-    pending, written, attempts = list(range(data_num)), [], {}
-    for attempt in range(MAX_ATTEMPTS):
-        failed = []
-        for i0 in range(0, len(pending), batch):
-            ids = pending[i0:i0 + batch]
-            plans = [plan_rir(cfgs[i], fs, c, ism_db) for i in ids]
-            has_tail = any(p["n_len"] > p["n_ism"] for p in plans)
-            rir_dev = render(plans, dev, make_noise(plans, ids, seed, attempt, dev) if has_tail else None, fs, c)
-            for idx in ids:
-                attempts[idx] = attempt + 1
-            if labels == "host":
-                for idx, rir in zip(ids, read_back(rir_dev, plans)):
-                    lab = _host_labels(rir, dps[idx], cfgs[idx], fs, c)
-                    if lab["ok"]:
-                        save(idx, rir, lab["T60_edc"], lab["TDOA"], lab["DRR"], lab["C50"])
-                    else:
-                        failed.append(idx)
-                continue
-            ldmax = max(dps[i].shape[1] for i in ids)
-            dp_host = np.zeros((len(ids), rir_dev.shape[1], ldmax), np.float32)
-            for b, i in enumerate(ids):
-                dp_host[b, :, :dps[i].shape[1]] = dps[i]
-            lab = judge_on_device(rir_dev, [p["n_len"] for p in plans], torch.from_numpy(dp_host).to(dev), [dps[i].shape[1] for i in ids],
-                                  [cfgs[i]["T60_specify"] for i in ids], ids, attempt, fs)
-            acc = [b for b in range(len(ids)) if lab["flags"][b] == 3]
-            failed += [ids[b] for b in range(len(ids)) if lab["flags"][b] != 3]
-            if acc:
-                h = rir_dev.index_select(0, torch.tensor(acc, device=dev)).cpu().numpy()          # only accepted RIRs cross the bus
-                for j, b in enumerate(acc):
-                    save(ids[b], h[j, :, :plans[b]["n_len"]], np.float64(lab["t60_edc"][b]), tdoa(cfgs[ids[b]], c),
-                         lab["drr"][b].astype(np.float16), lab["c50"][b].astype(np.float16))
-        pending = failed
-        if not pending:
-            break
-    for idx in pending:
-        log("simulate_bank: item %d of stage %s failed the accept test %d times and is skipped" % (idx, stage, MAX_ATTEMPTS))
-    np.savez_compressed(os.path.join(out_dir, "all_info.npz"), args=dict(args, stage=stage, data_num=data_num, seed=seed, noise=noise),
-                        cfgs=cfgs, skipped=np.array(pending, np.int64))
-    return dict(written=sorted(written), skipped=pending, attempts=attempts)
+    return _generate("simulate_bank", out_dir, stage, cfgs, seed, args, device, noise, batch, labels, sink, log)
 
 
 WHITE_STREAM = 1 << 63           # seed bit of the white noise of --mode sig: apart from the RIR tails' (seed | attempt << 32, idx) keys
@@ -655,12 +687,12 @@ def simulate_signals(save_to, stage="pretrain", data_num=1, src_dir="", mic_arra
     (int(T fs), nch) and ``{idx}_info.npz`` (configuration, T60_edc, SNR, src_idx, TDOA / DRR / C50 with the reference's dtypes) under
     ``save_to/stage``, with ``all_info.npz`` as in ``simulate_bank``.
 
-    Per batch, on a side stream and without the RIR ever leaving the device: ``render`` of the direct paths and the RIRs (tail noise
-    keyed by (seed, idx, attempt)), ``judge_on_device``, one small read-back of the labels, a gather of the accepted items, the white
-    noise (noise="device": sarssl_gauss_fill keyed by (seed, idx); "numpy": the reference's host draw, uploaded), hip.diffuse_noise with
-    the item's mixing table, hip.rir_mix against the direct path at gain 0.9, hip.pcm16_pack, a copy to a pinned buffer.  A writer thread
-    then writes the batch's files (dataset.write_wav_batch, np.savez) while the next batch renders.  Rejected items go to the next
-    attempt; after MAX_ATTEMPTS an item is skipped with a logged line and listed in all_info.npz.
+    The generator loop (``_generate``: ``render_items``, ``judge_on_device``, one small read-back of the labels, retries) on a side
+    stream, with a sink that never takes the RIR off the device: a gather of the accepted items, the white noise (noise="device":
+    sarssl_gauss_fill keyed by (seed, idx); "numpy": the reference's host draw, uploaded), rirsynth.mix_simulated with the item's mixing
+    table against the direct path at gain 0.9, hip.pcm16_pack, a copy to a pinned buffer.  A writer thread then writes the batch's files
+    (dataset.write_wav_batch, np.savez) while the next batch renders.  Rejected items go to the next attempt; after MAX_ATTEMPTS an item
+    is skipped with a logged line and listed in all_info.npz.
 
     An item's files are a function of (seed, idx, attempt, the source files) alone, not of the batch it was rendered in: hip.rir_mix
     partitions its RIRs by the row length it is given, so every batch is rendered at the one row length ``sig_lmax(T60_range)``.
@@ -671,35 +703,27 @@ def simulate_signals(save_to, stage="pretrain", data_num=1, src_dir="", mic_arra
     from . import hip, rirsynth
     from .dataset import write_wav_batch
     args = _generator_args(ranges, noise)
-    fs, c, ism_db = args["fs"], args["c"], args["ism_db"]
+    fs, c = args["fs"], args["c"]
     base = sig_stage(stage)
     seed = SIG_STAGE_SEEDS[base]
-    ns = int(T * fs)
-    if ns <= 0 or ns % 64 != 0:
-        raise ValueError("T = %s: int(T fs) = %d samples is not a multiple of 64, which the diffuse-noise kernel's frames need" % (T, ns))
-    log = log or (lambda s: print(s, file=sys.stderr, flush=True))
+    ns = sig_samples(T, fs)
     mic_array_cfg = MIC_ARRAY_CFG_2CH if mic_array_cfg is None else mic_array_cfg
     nmic = mic_array_cfg["mic_pos_relative"].shape[0]
     sources = rirsynth.SourceBank(src_dir + "/" + SIG_SRC_SUBDIR[base], fs, sort=sort_sources)
-    out_dir = os.path.join(save_to, stage)
-    os.makedirs(out_dir, exist_ok=True)
+    out_dir, cfgs = _rooms(save_to, stage, seed, data_num, mic_array_cfg, args)
     rs = np.random.RandomState()
-    draw = {k: args[k] for k in DEFAULTS if k != "fs"}
-    cfgs = [random_spatial_acoustics(rs, seed, idx, mic_array_cfg=mic_array_cfg, **draw) for idx in range(data_num)]
     dev = torch.device(device)
-    make_noise = device_noise if noise == "device" else host_noise
-    lmax = sig_lmax(args["T60_range"], fs)
     side = torch.cuda.Stream(dev)
     pinned = [torch.empty((batch, ns, nmic), dtype=torch.int16, pin_memory=True) for _ in range(2)]
     busy = [None, None]                                       # the writer job that still reads each pinned buffer
-    sig_plans, written, attempts = {}, [], {}
+    sig_plans, nbatch = {}, 0
 
-    def plan(idx):
-        if idx not in sig_plans:
-            p = plan_sig(rs, idx, seed, cfgs[idx], sources, T, snr_range, nmic, draw_white=noise == "numpy", fs=fs)
-            p["C"] = rirsynth.mixing_table(cfgs[idx]["mic_pos"], fs, c).astype(np.float32)
-            sig_plans[idx] = p
-        return sig_plans[idx]
+    def prepare(ids):                                         # (host work while the GPU renders)
+        for idx in ids:
+            if idx not in sig_plans:
+                p = plan_sig(rs, idx, seed, cfgs[idx], sources, T, snr_range, nmic, draw_white=noise == "numpy", fs=fs)
+                p["C"] = rirsynth.mixing_table(cfgs[idx]["mic_pos"], fs, c).astype(np.float32)
+                sig_plans[idx] = p
 
     def write(ev, buf, ids, infos):
         ev.synchronize()
@@ -707,70 +731,47 @@ def simulate_signals(save_to, stage="pretrain", data_num=1, src_dir="", mic_arra
         for i, info in zip(ids, infos):
             np.savez(os.path.join(out_dir, "%d_info.npz" % i), **info)
 
-    pending, nbatch = list(range(data_num)), 0
+    def sink(b, acc, lab):
+        nonlocal nbatch
+        A, aids = len(acc), [b.ids[j] for j in acc]
+        rir_dev, dp_dev = b.rir, b.dp
+        if A < len(b.ids):
+            sel = torch.tensor(acc, device=dev)
+            rir_dev, dp_dev = rir_dev.index_select(0, sel), dp_dev.index_select(0, sel)
+        host = torch.empty((A, ns + 129 * nmic * nmic + 1), dtype=torch.float32, pin_memory=True)      # src | C | snr of each item
+        hn = host.numpy()
+        for j, i in enumerate(aids):
+            hn[j, :ns], hn[j, ns:-1], hn[j, -1] = sig_plans[i]["src"], sig_plans[i]["C"].reshape(-1), sig_plans[i]["snr"]
+        up = host.to(dev, non_blocking=True)
+        if noise == "numpy":
+            white = torch.from_numpy(np.stack([sig_plans[i]["white"] for i in aids]).astype(np.float32)).to(dev)
+        else:
+            white = torch.empty((A, ns, nmic), dtype=torch.float32, device=dev)
+            for j, i in enumerate(aids):
+                hip.gauss_fill(white[j:j + 1], (int(seed) & 0xffffffff) | WHITE_STREAM, int(i))
+        mic = rirsynth.mix_simulated(up[:, :ns].contiguous(), rir_dev, torch.tensor([b.plans[j]["n_len"] for j in acc], dtype=torch.int32, device=dev),
+                                     dp_dev, torch.tensor([b.plans_dp[j]["n_len"] for j in acc], dtype=torch.int32, device=dev), white,
+                                     up[:, ns:-1].reshape(A, 129, nmic, nmic).contiguous(), up[:, -1].contiguous(),
+                                     torch.full((A,), PCM_GAIN, dtype=torch.float32, device=dev))
+        pcm = hip.pcm16_pack(mic)
+        k = nbatch % 2
+        nbatch += 1
+        if busy[k] is not None:
+            busy[k].result()                                  # the buffer's previous batch is on disk
+        pinned[k][:A].copy_(pcm, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(side)
+        infos = [sig_info(cfgs[i], sig_plans.pop(i), lab["t60_edc"][j], lab["drr"][j], lab["c50"][j], c) for i, j in zip(aids, acc)]
+        busy[k] = writer.submit(write, ev, pinned[k], aids, infos)
+        return aids
+
     with ThreadPoolExecutor(max_workers=1) as writer, torch.cuda.stream(side):
-        for attempt in range(MAX_ATTEMPTS):
-            failed = []
-            for i0 in range(0, len(pending), batch):
-                ids = pending[i0:i0 + batch]
-                plans_dp = [plan_rir(cfgs[i], fs, c, ism_db, dp=True) for i in ids]
-                plans = [plan_rir(cfgs[i], fs, c, ism_db) for i in ids]
-                has_tail = any(p["n_len"] > p["n_ism"] for p in plans)
-                dp_dev = render(plans_dp, dev, None, fs, c)
-                rir_dev = render(plans, dev, make_noise(plans, ids, seed, attempt, dev, lmax) if has_tail else None, fs, c, lmax)
-                for idx in ids:
-                    attempts[idx] = attempt + 1
-                    plan(idx)                                 # (host work while the GPU renders)
-                lab = judge_on_device(rir_dev, [p["n_len"] for p in plans], dp_dev, [p["n_len"] for p in plans_dp],
-                                      [cfgs[i]["T60_specify"] for i in ids], ids, attempt, fs)
-                acc = [b for b in range(len(ids)) if lab["flags"][b] == 3]
-                failed += [ids[b] for b in range(len(ids)) if lab["flags"][b] != 3]
-                if not acc:
-                    continue
-                A, aids = len(acc), [ids[b] for b in acc]
-                if A < len(ids):
-                    sel = torch.tensor(acc, device=dev)
-                    rir_dev, dp_dev = rir_dev.index_select(0, sel), dp_dev.index_select(0, sel)
-                host = torch.empty((A, ns + 129 * nmic * nmic + 1), dtype=torch.float32, pin_memory=True)      # src | C | snr of each item
-                hn = host.numpy()
-                for j, i in enumerate(aids):
-                    hn[j, :ns], hn[j, ns:-1], hn[j, -1] = sig_plans[i]["src"], sig_plans[i]["C"].reshape(-1), sig_plans[i]["snr"]
-                up = host.to(dev, non_blocking=True)
-                if noise == "numpy":
-                    white = torch.from_numpy(np.stack([sig_plans[i]["white"] for i in aids]).astype(np.float32)).to(dev)
-                else:
-                    white = torch.empty((A, ns, nmic), dtype=torch.float32, device=dev)
-                    for j, i in enumerate(aids):
-                        hip.gauss_fill(white[j:j + 1], (int(seed) & 0xffffffff) | WHITE_STREAM, int(i))
-                field = hip.diffuse_noise(white, up[:, ns:-1].reshape(A, 129, nmic, nmic).contiguous(), out=white)
-                mic = hip.rir_mix(up[:, :ns].contiguous(), rir_dev, torch.tensor([plans[b]["n_len"] for b in acc], dtype=torch.int32, device=dev),
-                                  up[:, -1].contiguous(), torch.full((A,), PCM_GAIN, dtype=torch.float32, device=dev), rir_dp=dp_dev,
-                                  dp_len=torch.tensor([plans_dp[b]["n_len"] for b in acc], dtype=torch.int32, device=dev), noise=field)
-                pcm = hip.pcm16_pack(mic)
-                k = nbatch % 2
-                nbatch += 1
-                if busy[k] is not None:
-                    busy[k].result()                          # the buffer's previous batch is on disk
-                pinned[k][:A].copy_(pcm, non_blocking=True)
-                ev = torch.cuda.Event()
-                ev.record(side)
-                infos = [sig_info(cfgs[ids[b]], sig_plans[ids[b]], lab["t60_edc"][b], lab["drr"][b], lab["c50"][b], c) for b in acc]
-                busy[k] = writer.submit(write, ev, pinned[k], aids, infos)
-                written += aids
-                for i in aids:
-                    del sig_plans[i]
-            pending = failed
-            if not pending:
-                break
+        res = _generate("simulate_signals", out_dir, stage, cfgs, seed, args, dev, noise, batch, "device", sink, log, prepare,
+                        sig_lmax(args["T60_range"], fs), T=T, snr_range=tuple(snr_range), src_dir=src_dir)
         for f in busy:
             if f is not None:
                 f.result()
-    for idx in pending:
-        log("simulate_signals: item %d of stage %s failed the accept test %d times and is skipped" % (idx, stage, MAX_ATTEMPTS))
-    np.savez_compressed(os.path.join(out_dir, "all_info.npz"),
-                        args=dict(args, stage=stage, data_num=data_num, seed=seed, noise=noise, T=T, snr_range=tuple(snr_range), src_dir=src_dir),
-                        cfgs=cfgs, skipped=np.array(pending, np.int64))
-    return dict(written=sorted(written), skipped=pending, attempts=attempts)
+    return res
 
 
 # ---------------------------------------------------------------------------------------------------------------- command line
@@ -833,8 +834,10 @@ def main(argv=None):
             ap.error("--noise_type %s: diffuse_white only" % a.noise_type)
         if a.gpu_conv:
             ap.error("--gpu_conv True: the trajectory convolution of moving sources is not built; static sources are convolved on the GPU anyway")
-        if int(a.T * a.fs) <= 0 or int(a.T * a.fs) % 64 != 0:
-            ap.error("--T %s: int(T fs) = %d samples is not a multiple of 64, which the diffuse-noise kernel's frames need" % (a.T, int(a.T * a.fs)))
+        try:
+            sig_samples(a.T, a.fs, "--T")
+        except ValueError as e:
+            ap.error(str(e))
         if not a.src_dir:
             ap.error("--src_dir is required with --mode sig")
     if "moving" in a.source_state or a.source_state != "static":

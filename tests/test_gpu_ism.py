@@ -162,11 +162,8 @@ def _fullsize():
     from sar_ssl_amd import roomsim
     ids = [0, 5]
     cfgs = [_cfg("cfg2/%d" % i) for i in ids]
-    plans = [roomsim.plan_rir(c) for c in cfgs]
-    dev = torch.device("cuda:0")
-    got = roomsim.render(plans, dev, roomsim.host_noise(plans, ids, SEED, 0, dev)).cpu().numpy()
-    dps = [roomsim.plan_rir(c, dp=True) for c in cfgs]
-    got_dp = roomsim.render(dps, dev).cpu().numpy()
+    batch = roomsim.render_items(dict(zip(ids, cfgs)), ids, SEED, 0, torch.device("cuda:0"), noise="numpy")
+    plans, got, got_dp = batch.plans, batch.rir.cpu().numpy(), batch.dp.cpu().numpy()
     want = [roomsim.restate_cfg(c, roomsim.numpy_noise(SEED, i, 0, 2, p["n_len"])) for c, i, p in zip(cfgs, ids, plans)]
     want_dp = [roomsim.restate_cfg(c, dp=True) for c in cfgs]
     return ids, cfgs, plans, got, got_dp, want, want_dp

@@ -164,11 +164,9 @@ def test_small_rooms_info_files(e2e):
     dev = torch.device(DEV)
     ids = list(range(8))
     lmax = roomsim.sig_lmax(sc.SMALL["T60_range"])
-    rp = [roomsim.plan_rir(plans[i]["cfg"]) for i in ids]
-    dpp = [roomsim.plan_rir(plans[i]["cfg"], dp=True) for i in ids]
+    batch = roomsim.render_items({i: plans[i]["cfg"] for i in ids}, ids, 1, 0, dev, noise="numpy", lmax=lmax)
+    rp, dpp, rir, dp = batch.plans, batch.plans_dp, batch.rir.cpu().numpy(), batch.dp.cpu().numpy()
     assert max(p["n_len"] for p in rp) <= 4094 < lmax
-    rir = roomsim.render(rp, dev, roomsim.host_noise(rp, ids, 1, 0, dev, lmax), lmax=lmax).cpu().numpy()
-    dp = roomsim.render(dpp, dev).cpu().numpy()
     tol = _tol()
     for i in ids:
         info = dict(np.load(out / ("%d_info.npz" % i), allow_pickle=True))
@@ -275,6 +273,49 @@ def test_simulate_bank_with_device_labels_writes_the_same_bank(tmp_path):
                 assert d[k].dtype == h[k].dtype
             else:
                 assert h[k].dtype == d[k].dtype and np.array_equal(h[k], d[k]), (i, k, h[k], d[k])
+
+
+@pytest.mark.parametrize("where", ["host", "device"])
+def test_simulate_bank_renders_a_rejected_item_again(tmp_path, monkeypatch, where):
+    """The retry path of --mode rir: item 1, rejected once (rir_ok without env_ok), is rendered again with attempt 1's noise and written
+    once; the others, and every direct path, are attempt 0's.  Each file against a render of that item alone."""
+    from sar_ssl_amd import roomsim
+    seed, dev = roomsim.STAGE_SEEDS["train"], torch.device(DEV)
+    judge, calls = getattr(roomsim, "judge_on_" + where), []
+
+    def reject(lab, ids, attempt):
+        calls.append((list(ids), attempt))
+        if attempt == 0:
+            lab["flags"][list(ids).index(1)] = 1
+        return lab
+
+    def on_host(batch, cfgs, fs=sc.FS, c=343.0):
+        return reject(judge(batch, cfgs, fs, c), batch.ids, len(calls))        # (one batch per attempt here: the call count is the attempt)
+
+    def on_device(rir, n_len, rir_dp, dp_len, T60_specify, ids=None, attempt=0, fs=sc.FS):
+        return reject(judge(rir, n_len, rir_dp, dp_len, T60_specify, ids, attempt, fs), ids, attempt)
+
+    monkeypatch.setattr(roomsim, "judge_on_" + where, on_host if where == "host" else on_device)
+    res = roomsim.simulate_bank(str(tmp_path), "train", 3, device=DEV, noise="numpy", batch=3, labels=where, **sc.SMALL)
+    assert calls == [([0, 1, 2], 0), ([1], 1)]
+    assert res["written"] == [0, 1, 2] and res["skipped"] == [] and res["attempts"] == {0: 1, 1: 2, 2: 1}
+    out = tmp_path / "train"
+    assert sorted(os.listdir(out)) == sorted(["%d%s" % (i, s) for i in range(3) for s in (".npy", "_dp.npy", "_info.npz")] + ["all_info.npz"])
+    cfgs = np.load(out / "all_info.npz", allow_pickle=True)["cfgs"]
+
+    def alone(i, attempt=None):
+        """Item i rendered by itself, read back in the files' layout: the RIR with ``attempt``'s uploaded noise, or the direct path."""
+        plan = [roomsim.plan_rir(cfgs[i], dp=attempt is None)]
+        noise = None if attempt is None else roomsim.host_noise(plan, [i], seed, attempt, dev)
+        return roomsim.render(plan, dev, noise).cpu().numpy()[:, :, :, None]
+
+    def same(name, want):
+        got = np.load(out / name)
+        return got.dtype == want.dtype == np.float32 and got.shape == want.shape and got.tobytes() == want.tobytes()
+
+    assert same("1.npy", alone(1, 1)) and not same("1.npy", alone(1, 0))
+    assert same("0.npy", alone(0, 0)) and same("2.npy", alone(2, 0))
+    assert all(same("%d_dp.npy" % i, alone(i)) for i in range(3))
 
 
 # ---------------------------------------------------------------------------------------------------------------- the product

@@ -2,8 +2,8 @@
 
     python tools/bench_ism.py [--items 32] [--batches 1,4,16] [--out profiles/ism.txt]
 
-Per batch size: RIRs/s of the render alone (hip.ism_rir with device noise, event-timed), of render + read-back, and of render + read-back +
-labels (roomsim.labels on the host).  Beside it the f64 numpy restatement (roomsim.restate_cfg) on the same host in the same run: gpuRIR
+Per batch size: RIRs/s of the render alone (roomsim.render_items: both plans, device noise, hip.ism_rir for the RIR and the direct path,
+event-timed), of render + read-back, and of render + read-back + labels (roomsim.labels on the host).  Beside it the f64 numpy restatement (roomsim.restate_cfg) on the same host in the same run: gpuRIR
 cannot be run, so the restatement is the baseline.  Also the distances of parity.ISM, measured against the restatement.
 """
 import argparse
@@ -31,7 +31,6 @@ def main():
     rs = np.random.RandomState()
     cfgs = [roomsim.random_spatial_acoustics(rs, seed, i) for i in range(a.items)]
     plans = [roomsim.plan_rir(c) for c in cfgs]
-    dps = [roomsim.plan_rir(c, dp=True) for c in cfgs]
     nimg = [int(np.prod(p["nb_img"])) for p in plans]
     lines = ["image-source RIR generator, stage train idx 0..%d, default ranges: %d .. %d images per RIR (mean %.0f), n_ism <= %d, n_len <= %d"
              % (a.items - 1, min(nimg), max(nimg), np.mean(nimg), max(p["n_ism"] for p in plans), max(p["n_len"] for p in plans)), ""]
@@ -49,14 +48,11 @@ def main():
         for rep in range(2):                                  # the first pass warms up (allocations, first launches) and is dropped
             tk = tr = tl = 0.0
             for i0 in range(0, a.items, bs):
-                ids = list(range(i0, min(i0 + bs, a.items)))
-                pl, dp = [plans[i] for i in ids], [dps[i] for i in ids]
                 torch.cuda.synchronize()
                 w0 = time.perf_counter()
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record()
-                rir = roomsim.render(pl, dev, roomsim.device_noise(pl, ids, seed, 0, dev))
-                rdp = roomsim.render(dp, dev)
+                ids, pl, _, rir, rdp = roomsim.render_items(cfgs, range(i0, min(i0 + bs, a.items)), seed, 0, dev)
                 e1.record()
                 h, hd = rir.cpu().numpy(), rdp.cpu().numpy()
                 w1 = time.perf_counter()

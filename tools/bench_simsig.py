@@ -2,9 +2,9 @@
 
     python tools/bench_simsig.py [--items 32] [--sig-items 64] [--out profiles/simsig.txt]
 
-1. gen_simu.py --mode rir at batch 1 / 4 / 16, default ranges, stage train: RIRs/s of a whole pass (render, accept test, read-back; no
-   file is written) with roomsim.labels on the host against roomsim.judge_on_device (csrc/rirlabel.hip), the two interleaved pass by pass
-   on the same box, median of --reps passes each; the labels kernel alone, event-timed.
+1. gen_simu.py --mode rir at batch 1 / 4 / 16, default ranges, stage train: RIRs/s of a whole pass of the generator's own loop (plan,
+   render, accept test, read-back; one attempt, no file is written) with roomsim.judge_on_host against roomsim.judge_on_device
+   (csrc/rirlabel.hip), the two interleaved pass by pass on the same box, median of --reps passes each; the labels kernel alone, event-timed.
 2. gen_simu.py --mode sig at batch 16, default ranges, T = 4.112 s, device noise, on a synthetic speech tree: items/s of
    roomsim.simulate_signals as a whole, and in a second, profiled pass the time per item of every stage - the GPU stages between events
    (hip.profile_start(all_calls=True): every C-ABI call under its entry point's name), the host stages by wall clock.
@@ -24,27 +24,19 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import sarssl_boot  # noqa: E402,F401
 
 
-def rir_pass(roomsim, torch, dev, cfgs, plans, dps, seed, bs, where):
-    """One pass of simulate_bank's loop over all items without the file writes -> seconds."""
-    n = len(cfgs)
+def rir_pass(roomsim, torch, dev, cfgs, seed, bs, where):
+    """One pass of the generator's own loop (roomsim._generate, as simulate_bank runs it) over all items, with a sink that reads back what
+    simulate_bank's reads back and writes nothing -> seconds.  One attempt: every item is rendered once, a rejected one not again."""
+    def sink(batch, acc, lab):
+        roomsim.read_back_accepted(batch, acc, lab)
+        return [batch.ids[b] for b in acc]
+
+    attempts, roomsim.MAX_ATTEMPTS = roomsim.MAX_ATTEMPTS, 1
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for i0 in range(0, n, bs):
-        ids = list(range(i0, min(i0 + bs, n)))
-        pl, dp = [plans[i] for i in ids], [dps[i] for i in ids]
-        rir = roomsim.render(pl, dev, roomsim.device_noise(pl, ids, seed, 0, dev))
-        rdp = roomsim.render(dp, dev)
-        if where == "host":
-            h, hd = rir.cpu().numpy(), rdp.cpu().numpy()
-            for b, i in enumerate(ids):
-                roomsim.labels(h[b, :, :pl[b]["n_len"]], hd[b], cfgs[i])
-        else:
-            hd = rdp.cpu().numpy()                              # (the direct paths are written for every accepted item)
-            lab = roomsim.judge_on_device(rir, [p["n_len"] for p in pl], rdp, [p["n_len"] for p in dp], [cfgs[i]["T60_specify"] for i in ids])
-            acc = [b for b in range(len(ids)) if lab["flags"][b] == 3]
-            if acc:
-                rir.index_select(0, torch.tensor(acc, device=dev)).cpu().numpy()
+    roomsim._generate("bench", None, "train", cfgs, seed, roomsim.DEFAULTS, dev, "device", bs, where, sink, log=lambda s: None)
     torch.cuda.synchronize()
+    roomsim.MAX_ATTEMPTS = attempts
     return time.perf_counter() - t0
 
 
@@ -90,26 +82,22 @@ def main():
     t0 = time.perf_counter()
     cfgs = [roomsim.random_spatial_acoustics(rs, seed, i) for i in range(a.items)]
     t_cfg = (time.perf_counter() - t0) / a.items
-    plans = [roomsim.plan_rir(c) for c in cfgs]
-    dps = [roomsim.plan_rir(c, dp=True) for c in cfgs]
     lines = ["accept test and labels on the device (csrc/rirlabel.hip), stage train idx 0..%d, default ranges, n_len <= %d" %
-             (a.items - 1, max(p["n_len"] for p in plans)), "",
+             (a.items - 1, max(roomsim.plan_rir(c)["n_len"] for c in cfgs)), "",
              "--mode rir, a whole pass (render, accept test, read-back; no files), RIRs/s, median of %d interleaved passes" % a.reps,
              "batch   host labels   device labels   ratio"]
     ratio16 = None
     for bs in (1, 4, 16):
-        rir_pass(roomsim, torch, dev, cfgs, plans, dps, seed, bs, "device")            # warm-up (allocations, first launches)
+        rir_pass(roomsim, torch, dev, cfgs, seed, bs, "device")                        # warm-up (allocations, first launches)
         th, td = [], []
         for _ in range(a.reps):
-            th.append(rir_pass(roomsim, torch, dev, cfgs, plans, dps, seed, bs, "host"))
-            td.append(rir_pass(roomsim, torch, dev, cfgs, plans, dps, seed, bs, "device"))
+            th.append(rir_pass(roomsim, torch, dev, cfgs, seed, bs, "host"))
+            td.append(rir_pass(roomsim, torch, dev, cfgs, seed, bs, "device"))
         h, d = a.items / np.median(th), a.items / np.median(td)
         ratio16 = d / h
         lines.append("%5d   %11.1f   %13.1f   %5.1f" % (bs, h, d, d / h))
     # the kernel alone
-    pl, dp = plans[:16], dps[:16]
-    rir = roomsim.render(pl, dev, roomsim.device_noise(pl, range(16), seed, 0, dev))
-    rdp = roomsim.render(dp, dev)
+    ids, pl, dp, rir, rdp = roomsim.render_items(cfgs, range(16), seed, 0, dev)
     nl = torch.tensor([p["n_len"] for p in pl], dtype=torch.int32, device=dev)
     dl = torch.tensor([p["n_len"] for p in dp], dtype=torch.int32, device=dev)
     ts = torch.tensor([c["T60_specify"] for c in cfgs[:16]], dtype=torch.float64, device=dev)
