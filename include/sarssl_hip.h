@@ -104,6 +104,14 @@ int sarssl_diffuse_noise(const float* white, const float* C, int nb, long ns, in
 /*      out (B, ns, M) f32 standard normal values: Box-Muller over the library's counter hash, a pure function of
  *      (seed, item0 + b, sample, channel).  NOT numpy's stream - for parity with the reference pass host-drawn noise instead. */
 int sarssl_gauss_fill(float* out, int nb, long ns, int m, unsigned long long seed, int item0, void* stream);
+/*      the mixing table sarssl_diffuse_noise reads, formed on the device (utils_noise.py:178-232: _desired_spatial_coherence, _mix_matrix):
+ *      mic (B, M, 3) f64 microphone positions in m -> out (B, 129, M, M) f32.  Row 0 is zero; row k >= 1 is the upper Cholesky factor U
+ *      (U^T U = G) of G_pq = sinc(w_k d_pq / (c pi)) with unit diagonal, w_k = 2 pi fs k / 256, sinc(x) = sin(pi x) / (pi x) as numpy forms
+ *      it - what rirsynth.mixing_table(...).astype(float32) returns, and that function stays the authority.  f64 throughout, rounded to f32
+ *      at the store; one thread per (item, bin), the factor in registers.  A pivot <= 0 makes the whole M x M block of that bin NaN
+ *      (LAPACK refuses at the same condition); other bins and items are unaffected.  M outside 1..8 is refused (-1) and nothing is
+ *      launched. */
+int sarssl_mixing_table(const double* mic, int nb, int m, double fs, double c, float* out, void* stream);
 /* ---- image-source room impulse responses (csrc/ism.hip): what RoomImpulseResponse.generate_rir (code/data_generation/
  *      utils_simu_rir_sig.py:475-508) asks a CUDA-only library for - a batch of static, single-source, omnidirectional RIRs of ragged length.
  *      Every per-item quantity is a device array and nothing is read back: room (B, 3) f64, beta (B, 6) f32 in the order x0, x1, y0, y1, z0, z1,

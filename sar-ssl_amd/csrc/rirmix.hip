@@ -475,3 +475,84 @@ extern "C" int sarssl_gauss_fill(float* out, int nb, long ns, int m, unsigned lo
     SARSSL_CHECK_LAUNCH("gauss_fill_kernel");
     return 0;
 }
+
+// ------------------------------------------------------------------------------------------------ mixing table
+// NoiseDataset._desired_spatial_coherence + _mix_matrix (utils_noise.py:178-232) as rirsynth.mixing_table states them: per (item, bin k)
+// the upper Cholesky factor U (U^T U = G) of the spherical coherence G_pq = sinc(w_k d_pq / (c pi)), w_k = 2 pi fs k / 256, unit
+// diagonal; bin 0 is zero.  One thread owns one (item, bin): G and then U live in registers (every index below is a compile-time
+// constant after unrolling), all arithmetic is f64 and the M x M block is rounded to f32 at its contiguous store.  A pivot <= 0 (or NaN)
+// makes the whole block NaN - LAPACK's dpotrf refuses at the same condition.
+template <int M>
+__global__ __launch_bounds__(64) void mixing_table_kernel(const double* __restrict__ mic, int total, double fs, double c, float* __restrict__ out) {
+    const int t = blockIdx.x * 64 + threadIdx.x;
+    if (t >= total) return;
+    const int b = t / 129, k = t - b * 129;
+    float* o = out + (long)t * (M * M);
+    if (k == 0) {
+#pragma unroll
+        for (int e = 0; e < M * M; ++e) o[e] = 0.0f;
+        return;
+    }
+    const double pi = 3.141592653589793;
+    const double w = 2.0 * pi * fs * (double)k / 256.0;
+    const double cpi = c * pi;
+    double pos[M][3];
+#pragma unroll
+    for (int m = 0; m < M; ++m)
+#pragma unroll
+        for (int a = 0; a < 3; ++a) pos[m][a] = mic[((long)b * M + m) * 3 + a];
+    double U[M][M];
+#pragma unroll
+    for (int p = 0; p < M; ++p)
+#pragma unroll
+        for (int q = p; q < M; ++q) {
+            if (q == p) { U[p][q] = 1.0; continue; }
+            const double dx = pos[p][0] - pos[q][0], dy = pos[p][1] - pos[q][1], dz = pos[p][2] - pos[q][2];
+            const double d = sqrt(dx * dx + dy * dy + dz * dz);
+            const double x = w * d / cpi;
+            const double y = pi * (x == 0.0 ? 1.0e-20 : x);               // numpy.sinc
+            U[p][q] = sin(y) / y;
+        }
+    bool ok = true;
+#pragma unroll
+    for (int j = 0; j < M; ++j) {
+        double s = U[j][j];
+#pragma unroll
+        for (int r = 0; r < j; ++r) s -= U[r][j] * U[r][j];
+        ok = ok && (s > 0.0);
+        const double piv = sqrt(s);
+        U[j][j] = piv;
+#pragma unroll
+        for (int i = j + 1; i < M; ++i) {
+            double v = U[j][i];
+#pragma unroll
+            for (int r = 0; r < j; ++r) v -= U[r][j] * U[r][i];
+            U[j][i] = v / piv;
+        }
+    }
+    const float nanv = __uint_as_float(0x7fc00000u);
+#pragma unroll
+    for (int p = 0; p < M; ++p)
+#pragma unroll
+        for (int q = 0; q < M; ++q) o[p * M + q] = !ok ? nanv : q < p ? 0.0f : (float)U[p][q];
+}
+
+// mic: (B, M, 3) f64; out: (B, 129, M, M) f32
+extern "C" int sarssl_mixing_table(const double* mic, int nb, int m, double fs, double c, float* out, void* stream) {
+    SARSSL_REQUIRE(m >= 1 && m <= 8, "sarssl_mixing_table(1 to 8 microphones)");
+    SARSSL_REQUIRE(mic && out && nb > 0 && nb <= (1 << 20), "sarssl_mixing_table");
+    const int total = nb * 129, grid = (total + 63) / 64;
+    hipStream_t st = (hipStream_t)stream;
+    switch (m) {
+        case 1: mixing_table_kernel<1><<<grid, 64, 0, st>>>(mic, total, fs, c, out); break;
+        case 2: mixing_table_kernel<2><<<grid, 64, 0, st>>>(mic, total, fs, c, out); break;
+        case 3: mixing_table_kernel<3><<<grid, 64, 0, st>>>(mic, total, fs, c, out); break;
+        case 4: mixing_table_kernel<4><<<grid, 64, 0, st>>>(mic, total, fs, c, out); break;
+        case 5: mixing_table_kernel<5><<<grid, 64, 0, st>>>(mic, total, fs, c, out); break;
+        case 6: mixing_table_kernel<6><<<grid, 64, 0, st>>>(mic, total, fs, c, out); break;
+        case 7: mixing_table_kernel<7><<<grid, 64, 0, st>>>(mic, total, fs, c, out); break;
+        default: mixing_table_kernel<8><<<grid, 64, 0, st>>>(mic, total, fs, c, out); break;
+    }
+    SARSSL_CHECK_LAUNCH("mixing_table_kernel");
+    return 0;
+}

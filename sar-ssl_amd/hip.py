@@ -805,6 +805,20 @@ def diffuse_noise(white, C, out=None):
     return out
 
 
+def mixing_table(mic, fs=16000.0, c=343.0, out=None):
+    """mic (B, M, 3) f64 microphone positions -> the mixing tables (B, 129, M, M) f32 ``diffuse_noise`` reads: what
+    rirsynth.mixing_table(mic[b], fs, c).astype(float32) returns, formed on the device (a bin whose factorisation meets a pivot <= 0 is
+    NaN).  M outside 1..8 raises and leaves ``out`` untouched."""
+    _need_cuda(mic, out)
+    assert mic.dtype == torch.float64 and mic.is_contiguous() and mic.dim() == 3 and mic.shape[2] == 3
+    B, M = mic.shape[0], mic.shape[1]
+    if out is None:
+        out = torch.empty((B, 129, M, M), dtype=torch.float32, device=mic.device)
+    assert out.shape == (B, 129, M, M) and out.dtype == torch.float32 and out.is_contiguous()
+    _lib.call("sarssl_mixing_table", _p(mic), c_int(B), c_int(M), _lib.c_double(fs), _lib.c_double(c), _p(out), _stream())
+    return out
+
+
 def gauss_fill(out, seed, item0=0):
     """Fill out (B, Ns, M) f32 with standard normal values keyed by (seed, item0 + b, sample, channel).  NOT numpy's stream."""
     _need_cuda(out)

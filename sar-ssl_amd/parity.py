@@ -86,6 +86,15 @@ RIRLABELS = dict(cap=dict(t60=5e-3, corr=1e-9, drr=1e-3, c50=1e-3),
 #   measured     the largest share of differing samples of an item on an MI355X (recorded, not gated below the bound)
 SIMSIG = dict(pcm_step=1, share_bound=2 * RIRMIX["gate"] * 32767, measured=dict(share=3.3e-3, max_step=1))
 
+# The mixing-table kernel (csrc/rirmix.hip: sarssl_mixing_table) against rirsynth.mixing_table(...).astype(float32): max |device - host|
+# over the geometries of tests/certainroom_cases.py at B = 1 and B = 5 (tests/test_gpu_certainroom.py).  Both sides factor in f64 and round
+# to f32 once; they differ in the library's sin and in the order of the factorisation's sums.
+#   cap       a condition, not a measurement: two f32 units at the entries' largest magnitude 1 (2^-22)
+#   measured  on an MI355X (profiles/certainroom.txt)
+#   gate      4x measured, rounded up to one digit, never above the cap; the tolerance of the test is min(gate, cap)
+#             (0: the f32 tables are bit-identical for every geometry of the test, so the test asserts equality)
+MIXTABLE = dict(cap=2.0 ** -22, measured=0.0, gate=0.0)
+
 # The row / elementwise kernels (csrc/elementwise.hip, the row kernels of csrc/dwconv.hip, csrc/head.hip) against the f64 restatements of
 # tests/rowkernel_refs.py on the operands as stored: max |got - ref| / max |ref| (tests/test_gpu_rowkernels.py).  Keyed by kernel family,
 # then by the storage dtype of a forward kernel or the (gradient, saved activation) pairing of a backward kernel: f32, bf16, fp16,

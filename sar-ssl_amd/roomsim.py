@@ -14,6 +14,12 @@ WSJ0-style source, mixed with the diffuse white-noise field at a drawn SNR, conv
 (fixture F22, tools/make_golden_simsig.py).  The float -> PCM-16 rule is this project's reading of libsndfile's and UNPINNED (``pcm16``).
 Both generators are one loop (``_generate``: ``render_items``, the judge on the host or the device, retries) with their own sink.
 
+``gen_simu_certain_room.py --mode rir | sig`` (GenerateRandomRIROfCertainRoom / GenerateRandomMicSigOfCertainRoom) is ``simulate_room_bank``
+/ ``simulate_room_signals``: a fixed number of rooms drawn once each (``random_room``), placements on each room
+(``random_spatial_acoustics(room_cfg=...)``), signals per placement, written as ``<stage>/R{n}/...`` - the corpus of the downstream
+sweep.  All rooms' items share one id space and the same loop and sinks; the diffuse field's mixing table is formed on the device
+(hip.mixing_table).  Fixture F23 (tools/make_golden_certainroom.py) pins the reference's seed and directory arithmetic.
+
 PARITY WITH gpuRIR IS UNPINNED: the library cannot be run or read, so the RIR is this project's own image-source model (Allen-Berkley
 images, 8 ms Hann-windowed sinc fractional delays, an exponentially decaying noise tail at the Sabine slope).  What is pinned against the
 reference is its own code around the call (fixture F21, tools/make_golden_ism.py).
@@ -196,22 +202,15 @@ def _t60_is_valid(room_sz, T60, alpha, c, ism_db, th=0.005, eps=1e-4):
     return valid_flag & bool(beta_prod != 0) & bool(ism_time >= 3 * max_dist / c), T60_sabine
 
 
-def random_spatial_acoustics(rs, seed, idx, mic_array_cfg=None, room_sz_range=None, T60_range=None, abs_weights_range=None,
-                             array_pos_ratio_range=None, num_source_range=(1, 1), source_state="static", min_src_array_dist=0.3,
-                             min_src_boundary_dist=0.3, c=343.0, ism_db=12):
-    """SpatialAcoustics.generate_random_spatial_acoustics (utils_simu_rir_sig.py:23-131, 143-378) on the RandomState ``rs``, draw for
-    draw: the room with its T60 / abs_weights retry loop, the array, one static source.  Returns the reference's dictionary."""
-    mic_array_cfg = MIC_ARRAY_CFG_2CH if mic_array_cfg is None else mic_array_cfg
-    room_sz_range = DEFAULTS["room_sz_range"] if room_sz_range is None else room_sz_range
-    T60_range = DEFAULTS["T60_range"] if T60_range is None else T60_range
-    abs_weights_range = DEFAULTS["abs_weights_range"] if abs_weights_range is None else abs_weights_range
-    array_pos_ratio_range = DEFAULTS["array_pos_ratio_range"] if array_pos_ratio_range is None else array_pos_ratio_range
-    if source_state != "static":
-        raise ValueError("static sources only (source_state %r): moving sources are out of scope" % (source_state,))
-    if mic_array_cfg["array_type"] != "planar_linear":
-        raise ValueError("Undefined array type~")
-    rs.seed(seed + idx)
-    # random_room
+def _draw_ranges(room_sz_range, T60_range, abs_weights_range):
+    return (DEFAULTS["room_sz_range"] if room_sz_range is None else room_sz_range, DEFAULTS["T60_range"] if T60_range is None else T60_range,
+            DEFAULTS["abs_weights_range"] if abs_weights_range is None else abs_weights_range)
+
+
+def random_room(rs, room_sz_range=None, T60_range=None, abs_weights_range=None, c=343.0, ism_db=12):
+    """SpatialAcoustics.random_room with room_cfg=None (utils_simu_rir_sig.py:74-98) on the RandomState ``rs`` where it stands, draw for
+    draw: the room size, then the T60 / abs_weights retry loop -> dict(room_sz, T60_sabine, beta, T60_specify)."""
+    room_sz_range, T60_range, abs_weights_range = _draw_ranges(room_sz_range, T60_range, abs_weights_range)
     room_sz = [rs.uniform(*r) for r in room_sz_range]
     valid = False
     while not valid:
@@ -219,6 +218,25 @@ def random_spatial_acoustics(rs, seed, idx, mic_array_cfg=None, room_sz_range=No
         abs_weights = [rs.uniform(*r) for r in abs_weights_range]
         beta = _beta_sabine_estimation(room_sz, T60_specify, abs_weights)
         valid, T60_sabine = _t60_is_valid(room_sz, T60_specify, 1 - beta ** 2, c, ism_db)
+    return {"room_sz": room_sz, "T60_sabine": T60_sabine, "beta": beta, "T60_specify": T60_specify}
+
+
+def random_spatial_acoustics(rs, seed, idx, mic_array_cfg=None, room_sz_range=None, T60_range=None, abs_weights_range=None,
+                             array_pos_ratio_range=None, num_source_range=(1, 1), source_state="static", min_src_array_dist=0.3,
+                             min_src_boundary_dist=0.3, c=343.0, ism_db=12, room_cfg=None):
+    """SpatialAcoustics.generate_random_spatial_acoustics (utils_simu_rir_sig.py:23-131, 143-378) on the RandomState ``rs``, draw for
+    draw, after seed + idx: the room (``random_room``; with a ``room_cfg`` that room is taken and only what follows is drawn, :43-70),
+    the array, one static source.  Returns the reference's dictionary."""
+    mic_array_cfg = MIC_ARRAY_CFG_2CH if mic_array_cfg is None else mic_array_cfg
+    array_pos_ratio_range = DEFAULTS["array_pos_ratio_range"] if array_pos_ratio_range is None else array_pos_ratio_range
+    if source_state != "static":
+        raise ValueError("static sources only (source_state %r): moving sources are out of scope" % (source_state,))
+    if mic_array_cfg["array_type"] != "planar_linear":
+        raise ValueError("Undefined array type~")
+    rs.seed(seed + idx)
+    if room_cfg is None:
+        room_cfg = random_room(rs, room_sz_range, T60_range, abs_weights_range, c, ism_db)
+    room_sz = room_cfg["room_sz"]
     # random_mic_array
     array_pos = np.array([rs.uniform(array_pos_ratio_range[i][0] * room_sz[i], array_pos_ratio_range[i][1] * room_sz[i]) for i in range(3)])
     array_scale = rs.uniform(*mic_array_cfg["array_scale_range"])
@@ -246,7 +264,7 @@ def random_spatial_acoustics(rs, seed, idx, mic_array_cfg=None, room_sz_range=No
         assert src_pos_min[i] <= src_pos_max[i], "Src postion range error: " + str(src_pos_min[i]) + ">" + str(src_pos_max[i])
     src_pos = src_pos_min + rs.random_sample(3) * (src_pos_max - src_pos_min)
     traj_pts = np.array([np.ones((1, 1)) * src_pos]).transpose(1, 2, 0)                     # (1, 3, 1)
-    return {"room_sz": room_sz, "T60_sabine": T60_sabine, "beta": beta, "T60_specify": T60_specify,
+    return {"room_sz": room_sz, "T60_sabine": room_cfg["T60_sabine"], "beta": room_cfg["beta"], "T60_specify": room_cfg["T60_specify"],
             "array_type": mic_array_cfg["array_type"], "mic_pos": mic_pos, "array_scale": array_scale, "array_rotate_azi": array_rotate,
             "mic_orV": mic_orV, "mic_pattern": mic_array_cfg["mic_pattern"], "array_orV": orV, "array_pos": array_pos,
             "src_traj_pts": traj_pts}
@@ -441,17 +459,35 @@ def sig_samples(T, fs=FS, name="T ="):
     return ns
 
 
-def restate_sig(plan, tail_noise=None, rir=None, rir_dp=None, pcm=True, fs=FS, c=343.0, ism_db=12):
+NOISE_TYPES = ("diffuse_white", "spatial_white")
+
+
+def check_noise_type(noise_type):
+    """The noise types that are built, else ValueError.  'white' - the default of the reference's gen_simu_certain_room.py - is not in the
+    list NoiseSignal accepts (utils_noise.py:45), so the reference's own documented command asserts there."""
+    if noise_type == "white":
+        raise ValueError("noise_type white: the reference's gen_simu_certain_room.py has this default, but its NoiseSignal accepts no 'white' "
+                         "(utils_noise.py:45) and asserts; say diffuse_white (the default here) or spatial_white")
+    if noise_type not in NOISE_TYPES:
+        raise ValueError("noise_type %s: diffuse_white and spatial_white only (noise from recordings is not built)" % noise_type)
+    return noise_type
+
+
+def restate_sig(plan, tail_noise=None, rir=None, rir_dp=None, pcm=True, fs=FS, c=343.0, ism_db=12, noise_type="diffuse_white"):
     """One item of the generator in f64 from the existing restatements: the RIR and the direct path of plan['cfg'] (restate_cfg; or the
-    given ``rir`` / ``rir_dp`` (nch, L)), the diffuse field of the plan's white noise, the mix at gain 0.9, and with pcm=True the PCM
-    rule -> (Ns, nch) int16 (float64 with pcm=False).  The authority for the GPU tests."""
+    given ``rir`` / ``rir_dp`` (nch, L)), the diffuse field of the plan's white noise (noise_type="spatial_white": the white noise as
+    drawn, utils_noise.py:65-66), the mix at gain 0.9, and with pcm=True the PCM rule -> (Ns, nch) int16 (float64 with pcm=False).  The
+    authority for the GPU tests."""
     from . import rirsynth
     cfg = plan["cfg"]
     if rir is None:
         rir = restate_cfg(cfg, tail_noise, fs, c, ism_db)
     if rir_dp is None:
         rir_dp = restate_cfg(cfg, None, fs, c, ism_db, dp=True)
-    noise = rirsynth.restate_diffuse(plan["white"], rirsynth.mixing_table(cfg["mic_pos"], fs, c))
+    if check_noise_type(noise_type) == "spatial_white":
+        noise = np.asarray(plan["white"], np.float64)
+    else:
+        noise = rirsynth.restate_diffuse(plan["white"], rirsynth.mixing_table(cfg["mic_pos"], fs, c))
     mic = rirsynth.restate_mix(plan["src"], rir, rir_dp=rir_dp, noise=noise, snr_db=plan["snr"], gain=PCM_GAIN)
     return pcm16(mic) if pcm else mic
 
@@ -601,12 +637,14 @@ def read_back_accepted(batch, acc, lab):
     return batch.rir[acc].cpu().numpy(), batch.dp[acc].cpu().numpy()
 
 
-def _generate(who, out_dir, stage, cfgs, seed, args, device, noise, batch, where, sink, log=None, prepare=None, lmax=None, **recorded):
+def _generate(who, out_dir, stage, cfgs, seed, args, device, noise, batch, where, sink, log=None, prepare=None, lmax=None, saved_cfgs=None,
+              **recorded):
     """The loop of both generators: the pending items are rendered in batches (``render_items``), judged (where="host": ``judge_on_host``,
     "device": ``judge_on_device``) and, where accepted (flags == 3), handed to ``sink(batch, accepted positions, labels) -> ids written``;
     the others are rendered again with the next attempt's noise and skipped with a logged line after MAX_ATTEMPTS.  ``prepare(ids)`` runs
     between the enqueue of a batch's renders and the wait for its labels: host work there overlaps the render.  all_info.npz (``args``,
-    the stage's and ``recorded``; every configuration; the skipped ids) is written unless out_dir is None.  -> dict(written, skipped, attempts)."""
+    the stage's and ``recorded``; every configuration - ``saved_cfgs`` where the caller stores them in another shape -; the skipped ids) is
+    written unless out_dir is None.  -> dict(written, skipped, attempts)."""
     fs, c = args["fs"], args["c"]
     log = log or (lambda s: print(s, file=sys.stderr, flush=True))
     pending, written, attempts = list(range(len(cfgs))), [], {}
@@ -633,8 +671,23 @@ def _generate(who, out_dir, stage, cfgs, seed, args, device, noise, batch, where
         log("%s: item %d of stage %s failed the accept test %d times and is skipped" % (who, idx, stage, MAX_ATTEMPTS))
     if out_dir is not None:
         info = dict(args, stage=stage, data_num=len(cfgs), seed=seed, noise=noise, **recorded)
-        np.savez_compressed(os.path.join(out_dir, "all_info.npz"), args=info, cfgs=cfgs, skipped=np.array(pending, np.int64))
+        np.savez_compressed(os.path.join(out_dir, "all_info.npz"), args=info, cfgs=cfgs if saved_cfgs is None else saved_cfgs,
+                            skipped=np.array(pending, np.int64))
     return dict(written=sorted(written), skipped=pending, attempts=attempts)
+
+
+def _bank_sink(cfgs, stem, fs, c):
+    """The sink of the RIR banks: item idx goes to ``stem(idx)`` + .npy (1, nch, L, 1) float32, _dp.npy and _info.npz."""
+    def sink(batch, acc, lab):
+        rir, dp = read_back_accepted(batch, acc, lab)
+        for j, b in enumerate(acc):
+            idx = batch.ids[b]
+            np.save(stem(idx) + ".npy", rir[j, :, :batch.plans[b]["n_len"]][None, :, :, None].astype(np.float32))
+            np.save(stem(idx) + "_dp.npy", dp[j, :, :batch.plans_dp[b]["n_len"]][None, :, :, None].astype(np.float32))
+            np.savez(stem(idx) + "_info.npz", **dict(cfgs[idx], T60_edc=np.float64(lab["t60_edc"][b])), TDOA=tdoa(cfgs[idx], c),
+                     DRR=lab["drr"][b].astype(np.float16), C50=lab["c50"][b].astype(np.float16), fs=fs)
+        return [batch.ids[b] for b in acc]
+    return sink
 
 
 def simulate_bank(save_to, stage="train", data_num=1024, mic_array_cfg=None, device="cuda", noise="device", batch=16, log=None,
@@ -658,17 +711,8 @@ def simulate_bank(save_to, stage="train", data_num=1024, mic_array_cfg=None, dev
     seed = STAGE_SEEDS[stage]
     out_dir, cfgs = _rooms(save_to, stage, seed, data_num, mic_array_cfg, args)
 
-    def sink(batch, acc, lab):
-        rir, dp = read_back_accepted(batch, acc, lab)
-        for j, b in enumerate(acc):
-            idx = batch.ids[b]
-            np.save(os.path.join(out_dir, "%d.npy" % idx), rir[j, :, :batch.plans[b]["n_len"]][None, :, :, None].astype(np.float32))
-            np.save(os.path.join(out_dir, "%d_dp.npy" % idx), dp[j, :, :batch.plans_dp[b]["n_len"]][None, :, :, None].astype(np.float32))
-            np.savez(os.path.join(out_dir, "%d_info.npz" % idx), **dict(cfgs[idx], T60_edc=np.float64(lab["t60_edc"][b])), TDOA=tdoa(cfgs[idx], c),
-                     DRR=lab["drr"][b].astype(np.float16), C50=lab["c50"][b].astype(np.float16), fs=fs)
-        return [batch.ids[b] for b in acc]
-
-    return _generate("simulate_bank", out_dir, stage, cfgs, seed, args, device, noise, batch, labels, sink, log)
+    return _generate("simulate_bank", out_dir, stage, cfgs, seed, args, device, noise, batch, labels,
+                     _bank_sink(cfgs, lambda idx: os.path.join(out_dir, "%d" % idx), fs, c), log)
 
 
 WHITE_STREAM = 1 << 63           # seed bit of the white noise of --mode sig: apart from the RIR tails' (seed | attempt << 32, idx) keys
@@ -698,19 +742,34 @@ def simulate_signals(save_to, stage="pretrain", data_num=1, src_dir="", mic_arra
     partitions its RIRs by the row length it is given, so every batch is rendered at the one row length ``sig_lmax(T60_range)``.
     The host plans an item once (plan_sig: it reads the utterances) while the GPU renders, and keeps the plan across attempts.
     -> dict(written=[idx], skipped=[idx], attempts={idx: n})."""
+    from . import rirsynth
+    args = _generator_args(ranges, noise)
+    base = sig_stage(stage)
+    seed = SIG_STAGE_SEEDS[base]
+    sig_samples(T, args["fs"])
+    mic_array_cfg = MIC_ARRAY_CFG_2CH if mic_array_cfg is None else mic_array_cfg
+    sources = rirsynth.SourceBank(src_dir + "/" + SIG_SRC_SUBDIR[base], args["fs"], sort=sort_sources)
+    out_dir, cfgs = _rooms(save_to, stage, seed, data_num, mic_array_cfg, args)
+    return _signals("simulate_signals", out_dir, stage, cfgs, seed, args, sources, lambda idx: os.path.join(out_dir, "%d" % idx), device, noise,
+                    batch, T, snr_range, mic_array_cfg["mic_pos_relative"].shape[0], nthreads, log, recorded=dict(src_dir=src_dir))
+
+
+def _signals(who, out_dir, stage, cfgs, seed, args, sources, stem, device, noise, batch, T, snr_range, nmic, nthreads, log, table="host",
+             noise_type="diffuse_white", saved_cfgs=None, recorded=None):
+    """The signal generators' run of ``_generate`` (see ``simulate_signals``): item idx of ``cfgs``, planned by plan_sig after seed + idx,
+    goes to ``stem(idx)`` + .wav and _info.npz.  table: where the diffuse field's mixing table is formed - "host": rirsynth.mixing_table
+    while the GPU renders, uploaded with the source; "device": hip.mixing_table of the batch's uploaded microphone positions.
+    noise_type="spatial_white": the white noise goes into hip.rir_mix as it is (no field, no division by its maximum).
+    recorded: what all_info.npz's args hold beside the ranges, T and snr_range."""
     import torch
     from concurrent.futures import ThreadPoolExecutor
     from . import hip, rirsynth
     from .dataset import write_wav_batch
-    args = _generator_args(ranges, noise)
+    assert table in ("host", "device") and noise_type in NOISE_TYPES
     fs, c = args["fs"], args["c"]
-    base = sig_stage(stage)
-    seed = SIG_STAGE_SEEDS[base]
     ns = sig_samples(T, fs)
-    mic_array_cfg = MIC_ARRAY_CFG_2CH if mic_array_cfg is None else mic_array_cfg
-    nmic = mic_array_cfg["mic_pos_relative"].shape[0]
-    sources = rirsynth.SourceBank(src_dir + "/" + SIG_SRC_SUBDIR[base], fs, sort=sort_sources)
-    out_dir, cfgs = _rooms(save_to, stage, seed, data_num, mic_array_cfg, args)
+    diffuse = noise_type == "diffuse_white"
+    ntab = 129 * nmic * nmic if diffuse and table == "host" else 0
     rs = np.random.RandomState()
     dev = torch.device(device)
     side = torch.cuda.Stream(dev)
@@ -722,14 +781,15 @@ def simulate_signals(save_to, stage="pretrain", data_num=1, src_dir="", mic_arra
         for idx in ids:
             if idx not in sig_plans:
                 p = plan_sig(rs, idx, seed, cfgs[idx], sources, T, snr_range, nmic, draw_white=noise == "numpy", fs=fs)
-                p["C"] = rirsynth.mixing_table(cfgs[idx]["mic_pos"], fs, c).astype(np.float32)
+                if ntab:
+                    p["C"] = rirsynth.mixing_table(cfgs[idx]["mic_pos"], fs, c).astype(np.float32)
                 sig_plans[idx] = p
 
     def write(ev, buf, ids, infos):
         ev.synchronize()
-        write_wav_batch([os.path.join(out_dir, "%d.wav" % i) for i in ids], buf[:len(ids)], fs, nthreads)
+        write_wav_batch([stem(i) + ".wav" for i in ids], buf[:len(ids)], fs, nthreads)
         for i, info in zip(ids, infos):
-            np.savez(os.path.join(out_dir, "%d_info.npz" % i), **info)
+            np.savez(stem(i) + "_info.npz", **info)
 
     def sink(b, acc, lab):
         nonlocal nbatch
@@ -738,10 +798,12 @@ def simulate_signals(save_to, stage="pretrain", data_num=1, src_dir="", mic_arra
         if A < len(b.ids):
             sel = torch.tensor(acc, device=dev)
             rir_dev, dp_dev = rir_dev.index_select(0, sel), dp_dev.index_select(0, sel)
-        host = torch.empty((A, ns + 129 * nmic * nmic + 1), dtype=torch.float32, pin_memory=True)      # src | C | snr of each item
+        host = torch.empty((A, ns + 1 + ntab), dtype=torch.float32, pin_memory=True)                   # src | snr | C of each item
         hn = host.numpy()
         for j, i in enumerate(aids):
-            hn[j, :ns], hn[j, ns:-1], hn[j, -1] = sig_plans[i]["src"], sig_plans[i]["C"].reshape(-1), sig_plans[i]["snr"]
+            hn[j, :ns], hn[j, ns] = sig_plans[i]["src"], sig_plans[i]["snr"]
+            if ntab:
+                hn[j, ns + 1:] = sig_plans[i]["C"].reshape(-1)
         up = host.to(dev, non_blocking=True)
         if noise == "numpy":
             white = torch.from_numpy(np.stack([sig_plans[i]["white"] for i in aids]).astype(np.float32)).to(dev)
@@ -749,10 +811,19 @@ def simulate_signals(save_to, stage="pretrain", data_num=1, src_dir="", mic_arra
             white = torch.empty((A, ns, nmic), dtype=torch.float32, device=dev)
             for j, i in enumerate(aids):
                 hip.gauss_fill(white[j:j + 1], (int(seed) & 0xffffffff) | WHITE_STREAM, int(i))
-        mic = rirsynth.mix_simulated(up[:, :ns].contiguous(), rir_dev, torch.tensor([b.plans[j]["n_len"] for j in acc], dtype=torch.int32, device=dev),
-                                     dp_dev, torch.tensor([b.plans_dp[j]["n_len"] for j in acc], dtype=torch.int32, device=dev), white,
-                                     up[:, ns:-1].reshape(A, 129, nmic, nmic).contiguous(), up[:, -1].contiguous(),
-                                     torch.full((A,), PCM_GAIN, dtype=torch.float32, device=dev))
+        src, snr = up[:, :ns].contiguous(), up[:, ns].contiguous()
+        rir_len = torch.tensor([b.plans[j]["n_len"] for j in acc], dtype=torch.int32, device=dev)
+        dp_len = torch.tensor([b.plans_dp[j]["n_len"] for j in acc], dtype=torch.int32, device=dev)
+        gain = torch.full((A,), PCM_GAIN, dtype=torch.float32, device=dev)
+        if not diffuse:
+            mic = hip.rir_mix(src, rir_dev, rir_len, snr, gain, rir_dp=dp_dev, dp_len=dp_len, noise=white)
+        else:
+            if ntab:
+                C = up[:, ns + 1:].reshape(A, 129, nmic, nmic).contiguous()
+            else:
+                mic_pos = np.ascontiguousarray(np.stack([cfgs[i]["mic_pos"] for i in aids]), np.float64)    # (the draws leave them column-major)
+                C = hip.mixing_table(torch.from_numpy(mic_pos).to(dev), float(fs), float(c))
+            mic = rirsynth.mix_simulated(src, rir_dev, rir_len, dp_dev, dp_len, white, C, snr, gain)
         pcm = hip.pcm16_pack(mic)
         k = nbatch % 2
         nbatch += 1
@@ -766,12 +837,113 @@ def simulate_signals(save_to, stage="pretrain", data_num=1, src_dir="", mic_arra
         return aids
 
     with ThreadPoolExecutor(max_workers=1) as writer, torch.cuda.stream(side):
-        res = _generate("simulate_signals", out_dir, stage, cfgs, seed, args, dev, noise, batch, "device", sink, log, prepare,
-                        sig_lmax(args["T60_range"], fs), T=T, snr_range=tuple(snr_range), src_dir=src_dir)
+        res = _generate(who, out_dir, stage, cfgs, seed, args, dev, noise, batch, "device", sink, log, prepare,
+                        sig_lmax(args["T60_range"], fs), saved_cfgs, T=T, snr_range=tuple(snr_range), **(recorded or {}))
         for f in busy:
             if f is not None:
                 f.result()
     return res
+
+
+# ---------------------------------------------------------------------------------------------------------------- fixed rooms
+ROOM_SRC_SUBDIR = {"train": "tr", "val": "dt", "test": "et"}                   # gen_simu_certain_room.py:311-316; seeds: STAGE_SEEDS
+
+
+def room_stage(stage):
+    """train | val | test, else ValueError with the reference's assertion (gen_simu_certain_room.py:239)."""
+    if stage not in ROOM_SRC_SUBDIR:
+        raise ValueError("--stage %s: gen_simu_certain_room.py generates train | val | test only, as the reference asserts "
+                         "(gen_simu.py --mode sig writes pretrain | preval | pretest)" % stage)
+    return stage
+
+
+def room_item(g, per_room):
+    """Flattened item id -> (room r, index inside the room): g = r per_room + index."""
+    return divmod(int(g), int(per_room))
+
+
+def room_stem(out_dir, g, per_room):
+    """The path of item ``g`` without its extension: ``out_dir/R{r + 1}/{index}`` - the directories count from one
+    (gen_simu_certain_room.py:190, 389)."""
+    r, i = room_item(g, per_room)
+    return os.path.join(out_dir, "R%d" % (r + 1), "%d" % i)
+
+
+def room_placements(seed, room_num, rir_num_each_room, mic_array_cfg, args):
+    """The reference's draws of gen_simu_certain_room.py:270-299, seed collisions between rooms and placements included: room r after
+    seed + r (``random_room``), its placement j after seed + r rir_num_each_room + j -> [room][placement] configurations."""
+    rs = np.random.RandomState()
+    draw = {k: args[k] for k in DEFAULTS if k != "fs"}
+    rooms = []
+    for r in range(room_num):
+        rs.seed(seed + r)
+        room_cfg = random_room(rs, args["room_sz_range"], args["T60_range"], args["abs_weights_range"], args["c"], args["ism_db"])
+        rooms.append([random_spatial_acoustics(rs, seed, r * rir_num_each_room + j, mic_array_cfg=mic_array_cfg, room_cfg=room_cfg, **draw)
+                      for j in range(rir_num_each_room)])
+    return rooms
+
+
+def rooms_by_key(rooms):
+    """all_info.npz's ``cfgs`` of the per-room generators: {'R{r}': room r's list} with ZERO-based keys, as the reference stores them
+    (gen_simu_certain_room.py:132, 302) - the directories count from one."""
+    return {"R%d" % r: room for r, room in enumerate(rooms)}
+
+
+def _room_dirs(save_to, stage, room_num):
+    out_dir = os.path.join(save_to, stage)
+    for r in range(room_num):
+        os.makedirs(os.path.join(out_dir, "R%d" % (r + 1)), exist_ok=True)
+    return out_dir
+
+
+def simulate_room_bank(save_to, stage="train", room_num=1000, rir_num_each_room=50, mic_array_cfg=None, device="cuda", noise="device",
+                       batch=16, log=None, labels="host", **ranges):
+    """GenerateRandomRIROfCertainRoom (gen_simu_certain_room.py:32-191): ``room_num`` rooms drawn once each (``room_placements``),
+    ``rir_num_each_room`` array and source placements in each, written as ``save_to/stage/R{r + 1}/{j}.npy``, ``{j}_dp.npy`` and
+    ``{j}_info.npz`` in ``simulate_bank``'s format, which rirsynth.SimulatedBank([save_to/stage]) loads.  All rooms' placements are one
+    id space g = r rir_num_each_room + j and one ``_generate`` run, so a batch may hold several rooms; the tail's noise is keyed by
+    (seed, g, attempt).  all_info.npz: args, cfgs = {'R{r}': [configurations]} with ZERO-based keys as the reference stores them, skipped
+    (flattened ids).  -> dict(written=[g], skipped=[g], attempts={g: n})."""
+    assert labels in ("host", "device")
+    args = _generator_args(ranges, noise)
+    seed = STAGE_SEEDS[room_stage(stage)]
+    mic_array_cfg = MIC_ARRAY_CFG_2CH if mic_array_cfg is None else mic_array_cfg
+    rooms = room_placements(seed, room_num, rir_num_each_room, mic_array_cfg, args)
+    out_dir = _room_dirs(save_to, stage, room_num)
+    cfgs = [cfg for room in rooms for cfg in room]
+    return _generate("simulate_room_bank", out_dir, stage, cfgs, seed, args, device, noise, batch, labels,
+                     _bank_sink(cfgs, lambda g: room_stem(out_dir, g, rir_num_each_room), args["fs"], args["c"]), log,
+                     saved_cfgs=rooms_by_key(rooms), room_num=room_num, rir_num_each_room=rir_num_each_room)
+
+
+def simulate_room_signals(save_to, stage="train", room_num=256, rir_num_each_room=50, sig_num_each_rir=2, src_dir="",
+                          noise_type="diffuse_white", mic_array_cfg=None, device="cuda", noise="device", batch=16, T=4.112,
+                          snr_range=(15, 30), sort_sources=False, nthreads=0, log=None, **ranges):
+    """GenerateRandomMicSigOfCertainRoom (gen_simu_certain_room.py:194-393), the corpus of the downstream sweep: ``room_num`` rooms
+    drawn once each, ``rir_num_each_room`` placements per room (``room_placements``), ``sig_num_each_rir`` signals per placement.  Item
+    i = j sig_num_each_rir + s of room r goes to ``save_to/stage/R{r + 1}/{i}.wav`` and ``{i}_info.npz``; its signal draws (plan_sig)
+    follow seed + r rir_num_each_room sig_num_each_rir + i, i.e. seed + g with g the item's id in the ONE id space all rooms share.  The
+    run is ``simulate_signals``' (``_signals``): a batch may hold items of several rooms, every item renders its own RIR (own tail noise,
+    accept test and T60_edc, as in the reference), the tail-noise and white-noise keys take g, and the diffuse field's mixing table is
+    formed on the device (hip.mixing_table) from the batch's microphone positions.
+    noise_type: diffuse_white (default) | spatial_white; the reference's default 'white' is refused (``check_noise_type``).
+    all_info.npz as in ``simulate_room_bank``, every placement ``sig_num_each_rir`` times.  -> dict(written=[g], skipped=[g], attempts)."""
+    from . import rirsynth
+    args = _generator_args(ranges, noise)
+    check_noise_type(noise_type)
+    seed = STAGE_SEEDS[room_stage(stage)]
+    sig_samples(T, args["fs"])
+    mic_array_cfg = MIC_ARRAY_CFG_2CH if mic_array_cfg is None else mic_array_cfg
+    sources = rirsynth.SourceBank(src_dir + "/" + ROOM_SRC_SUBDIR[stage], args["fs"], sort=sort_sources)
+    rooms = [[cfg for cfg in room for _ in range(sig_num_each_rir)]
+             for room in room_placements(seed, room_num, rir_num_each_room, mic_array_cfg, args)]
+    out_dir = _room_dirs(save_to, stage, room_num)
+    per_room = rir_num_each_room * sig_num_each_rir
+    return _signals("simulate_room_signals", out_dir, stage, [cfg for room in rooms for cfg in room], seed, args, sources,
+                    lambda g: room_stem(out_dir, g, per_room), device, noise, batch, T, snr_range, mic_array_cfg["mic_pos_relative"].shape[0],
+                    nthreads, log, table="device", noise_type=noise_type, saved_cfgs=rooms_by_key(rooms),
+                    recorded=dict(src_dir=src_dir, room_num=room_num, rir_num_each_room=rir_num_each_room,
+                                  sig_num_each_rir=sig_num_each_rir, noise_type=noise_type))
 
 
 # ---------------------------------------------------------------------------------------------------------------- command line
@@ -788,13 +960,11 @@ def _flag(text):
     raise ValueError(text)
 
 
-def main(argv=None):
-    """``gen_simu.py --mode rir | sig`` with the reference's flag names (argparse; lists are written as Python literals, e.g. --gpus [0])."""
-    import argparse
-    ap = argparse.ArgumentParser(description="Generate simulated RIRs or microphone signals (image-source model on the GPU)")
+def _shared_arguments(ap):
+    """The flags gen_simu.py and gen_simu_certain_room.py share: the reference's names, and this project's --mic_array, --noise, --batch,
+    --labels."""
     ap.add_argument("--mode", type=str, default="rir")
     ap.add_argument("--stage", type=str, default="train")
-    ap.add_argument("--data_num", type=int, default=1024)
     ap.add_argument("--save_to", type=str, default="")
     ap.add_argument("--gpus", type=_literal, default=[0])
     ap.add_argument("--room_sz_range", type=_literal, default=DEFAULTS["room_sz_range"])
@@ -818,28 +988,22 @@ def main(argv=None):
     ap.add_argument("--snr_range", type=_literal, default=(15, 30))
     ap.add_argument("--noise_type", type=str, default="diffuse_white")
     ap.add_argument("--T", type=float, default=4.112)
-    ap.add_argument("--save_dp", type=_flag, default=False)
     ap.add_argument("--gpu_conv", type=_flag, default=False)
-    a = ap.parse_args(argv)
-    if a.mode not in ("rir", "sig"):
-        ap.error("--mode %s: only --mode rir and --mode sig are built" % a.mode)
-    if a.mode == "sig":
-        try:
-            sig_stage(a.stage)
-        except ValueError as e:
-            ap.error(str(e))
-        if a.save_dp:
-            ap.error("--save_dp True: the direct-path signal is not written (the mix kernel never stores it)")
-        if a.noise_type != "diffuse_white":
-            ap.error("--noise_type %s: diffuse_white only" % a.noise_type)
-        if a.gpu_conv:
-            ap.error("--gpu_conv True: the trajectory convolution of moving sources is not built; static sources are convolved on the GPU anyway")
-        try:
-            sig_samples(a.T, a.fs, "--T")
-        except ValueError as e:
-            ap.error(str(e))
-        if not a.src_dir:
-            ap.error("--src_dir is required with --mode sig")
+
+
+def _shared_sig_refusals(ap, a):
+    if a.gpu_conv:
+        ap.error("--gpu_conv True: the trajectory convolution of moving sources is not built; static sources are convolved on the GPU anyway")
+    try:
+        sig_samples(a.T, a.fs, "--T")
+    except ValueError as e:
+        ap.error(str(e))
+    if not a.src_dir:
+        ap.error("--src_dir is required with --mode sig")
+
+
+def _shared_refusals(ap, a):
+    """What both command lines refuse, before a GPU is touched -> (device name, the ranges as keyword arguments)."""
     if "moving" in a.source_state or a.source_state != "static":
         ap.error("--source_state %s: static sources only" % a.source_state)
     if tuple(a.num_source_range) != (1, 1):
@@ -856,12 +1020,70 @@ def main(argv=None):
     ranges = dict(room_sz_range=a.room_sz_range, T60_range=a.T60_range, abs_weights_range=a.abs_weights_range,
                   array_pos_ratio_range=a.array_pos_ratio_range, num_source_range=a.num_source_range, source_state=a.source_state,
                   min_src_array_dist=a.min_src_array_dist, min_src_boundary_dist=a.min_src_boundary_dist, c=a.c, ism_db=a.ism_db)
+    return "cuda:%d" % int(gpus[0]), ranges
+
+
+def main(argv=None):
+    """``gen_simu.py --mode rir | sig`` with the reference's flag names (argparse; lists are written as Python literals, e.g. --gpus [0])."""
+    import argparse
+    ap = argparse.ArgumentParser(description="Generate simulated RIRs or microphone signals (image-source model on the GPU)")
+    _shared_arguments(ap)
+    ap.add_argument("--data_num", type=int, default=1024)
+    ap.add_argument("--save_dp", type=_flag, default=False)
+    a = ap.parse_args(argv)
+    if a.mode not in ("rir", "sig"):
+        ap.error("--mode %s: only --mode rir and --mode sig are built" % a.mode)
     if a.mode == "sig":
-        res = simulate_signals(a.save_to, a.stage, a.data_num, a.src_dir, MIC_ARRAYS[a.mic_array], device="cuda:%d" % int(gpus[0]),
+        try:
+            sig_stage(a.stage)
+        except ValueError as e:
+            ap.error(str(e))
+        if a.save_dp:
+            ap.error("--save_dp True: the direct-path signal is not written (the mix kernel never stores it)")
+        if a.noise_type != "diffuse_white":
+            ap.error("--noise_type %s: diffuse_white only" % a.noise_type)
+        _shared_sig_refusals(ap, a)
+    device, ranges = _shared_refusals(ap, a)
+    if a.mode == "sig":
+        res = simulate_signals(a.save_to, a.stage, a.data_num, a.src_dir, MIC_ARRAYS[a.mic_array], device=device,
                                noise=a.noise, batch=a.batch, T=a.T, snr_range=tuple(a.snr_range), **ranges)
         print("%d microphone signals written to %s, %d skipped" % (len(res["written"]), os.path.join(a.save_to, a.stage), len(res["skipped"])))
         return 0
-    res = simulate_bank(a.save_to, a.stage, a.data_num, MIC_ARRAYS[a.mic_array], device="cuda:%d" % int(gpus[0]), noise=a.noise, batch=a.batch,
+    res = simulate_bank(a.save_to, a.stage, a.data_num, MIC_ARRAYS[a.mic_array], device=device, noise=a.noise, batch=a.batch,
                         labels=a.labels, **ranges)
     print("%d RIRs written to %s, %d skipped" % (len(res["written"]), os.path.join(a.save_to, a.stage), len(res["skipped"])))
+    return 0
+
+
+def main_certain_room(argv=None):
+    """``gen_simu_certain_room.py --mode rir | sig`` with the reference's flag names: ``simulate_room_bank`` / ``simulate_room_signals``."""
+    import argparse
+    ap = argparse.ArgumentParser(description="Generate simulated RIRs or microphone signals of a fixed number of rooms, for the downstream "
+                                             "stages train | val | test (image-source model on the GPU)")
+    _shared_arguments(ap)
+    ap.add_argument("--room_num", type=int, default=256)
+    ap.add_argument("--rir_num_each_room", type=int, default=50)
+    ap.add_argument("--sig_num_each_rir", type=int, default=2)
+    a = ap.parse_args(argv)
+    if a.mode not in ("rir", "sig"):
+        ap.error("--mode %s: only --mode rir and --mode sig are built" % a.mode)
+    try:
+        room_stage(a.stage)
+        if a.mode == "sig":
+            check_noise_type(a.noise_type)
+    except ValueError as e:
+        ap.error(str(e))
+    if a.mode == "sig":
+        _shared_sig_refusals(ap, a)
+    device, ranges = _shared_refusals(ap, a)
+    where = os.path.join(a.save_to, a.stage)
+    if a.mode == "sig":
+        res = simulate_room_signals(a.save_to, a.stage, a.room_num, a.rir_num_each_room, a.sig_num_each_rir, a.src_dir, a.noise_type,
+                                    MIC_ARRAYS[a.mic_array], device=device, noise=a.noise, batch=a.batch, T=a.T,
+                                    snr_range=tuple(a.snr_range), **ranges)
+        print("%d microphone signals of %d rooms written to %s, %d skipped" % (len(res["written"]), a.room_num, where, len(res["skipped"])))
+        return 0
+    res = simulate_room_bank(a.save_to, a.stage, a.room_num, a.rir_num_each_room, MIC_ARRAYS[a.mic_array], device=device, noise=a.noise,
+                             batch=a.batch, labels=a.labels, **ranges)
+    print("%d RIRs of %d rooms written to %s, %d skipped" % (len(res["written"]), a.room_num, where, len(res["skipped"])))
     return 0
