@@ -19,6 +19,10 @@ extern "C" {
 #endif
 
 const char* sarssl_last_error(void);
+/* 3.  Version 3 is one entry point per launch: where version 2 had a base name next to suffixed forms that added one optional argument
+ * (sarssl_adam_step[_dev][_guard[_lo]], sarssl_masked_mse_fwd[_acc | _bwd], sarssl_layernorm_bwd[_drop], sarssl_stem_c4_fwd[_stats],
+ * sarssl_stem_c4_bwd_apply[_pg], sarssl_cl_bn_bwd_apply[_pg]) the base name now has the widest signature with nullable pointers.  Those
+ * names CHANGED SIGNATURE: check the version before calling them. */
 int sarssl_abi_version(void);
 
 /* ---- contexts ("no global mutable state except an opaque sarssl_ctx* created per device").  A context owns everything a
@@ -36,22 +40,18 @@ int sarssl_ctx_set_conv_cus(sarssl_ctx* ctx, int ncus);       /* 3x3 data / weig
 /* fp16 range guard: kernels that encode externally scaled data as fp16 (sarssl_mask_inputs, sarssl_stft_frontend_pairs_masked with
  * dtype fp16: the spectrum divided by mean|X_0| + eps, code/learner.py:539-542) set a device word of the context when a value does not fit
  * (|v| > 65 504).  The next sarssl_masked_mse_* launch under the context then reports the loss as NaN and clears the word - an overflowed
- * forward does not reach the loss by itself (BatchNorm makes NaN of inf, ReLU makes 0 of NaN) - and the guarded Adam launches skip the
- * step.  sarssl_ctx_fp16_overflow reads (and optionally clears) the word from the host; synchronises `stream`. */
+ * forward does not reach the loss by itself (BatchNorm makes NaN of inf, ReLU makes 0 of NaN) - and the Adam launches behind a guard skip
+ * the step.  sarssl_ctx_fp16_overflow reads (and optionally clears) the word from the host; synchronises `stream`. */
 int sarssl_ctx_fp16_overflow(sarssl_ctx* ctx, int clear, void* stream);
 int sarssl_ctx_get_conv_cus(const sarssl_ctx* ctx);
 int sarssl_ctx_set_clock_probe(sarssl_ctx* ctx, void* buf);   /* see the measurement aid below; NULL = off */
 int sarssl_ctx_attach_step_state(sarssl_ctx* ctx, void* state);   /* device SarsslStepState* or NULL: dropout launches add its salt */
 int sarssl_ctx_zero_arena(sarssl_ctx* ctx, const void* base, long bytes);   /* accumulators inside [base, base+bytes) are already zero */
-int sarssl_device_info(int device, char* name_out, int name_len, int* cu_count, long* lds_bytes);
 
 /* ---- front-end: code/common/utils_module.py:49-72 (STFT.forward), code/learner.py:525-553 (data_preprocess),
- *      code/common/utils_module.py:128-134 (AddChToBatch 'M').  sig: (B, nsample, nch) f32|int16.
- *      U: workspace (B, nch, 257, nt, 2) f32; magsum: workspace f64[B]; out: (B*(nch-1), 2, 256, nt, 2) f32. */
-int sarssl_stft_frontend(const void* sig, int sig_dtype, int nb, long nsample, int nch, int win_len, int hop, int nfft,
-                         int nt, float eps, float* U, double* magsum, float* out, void* stream);
-/*      pair_mode 0 = AddChToBatch 'M' (as above), 1 = 'MM' (code/common/utils_module.py:136-143): all nch(nch-1)/2 pairs,
- *      out: (B*npair, 2, 256, nt, 2). */
+ *      code/common/utils_module.py:128-143 (AddChToBatch).  sig: (B, nsample, nch) f32|int16.
+ *      U: workspace (B, nch, 257, nt, 2) f32; magsum: workspace f64[B]; out: (B*npair, 2, 256, nt, 2) f32.
+ *      pair_mode 0 = AddChToBatch 'M': microphone 0 with every other one, npair = nch - 1; 1 = 'MM': all npair = nch(nch-1)/2 pairs. */
 int sarssl_stft_frontend_pairs(const void* sig, int sig_dtype, int nb, long nsample, int nch, int win_len, int hop, int nfft,
                                int nt, float eps, int pair_mode, float* U, double* magsum, float* out, void* stream);
 /* the same followed by sarssl_mask_inputs(mode 0) in ONE pass over the spectrum (code/learner.py:533-551 + code/model.py:541, :563):
@@ -229,11 +229,7 @@ int sarssl_stem_c4_fwd_pair(const void* y3, const float* W4, const float* scale,
                             void* y4_lo, double* stats8, int dtype, void* stream);
 int sarssl_cl_affine_act_pair(const void* x_hi, const void* x_lo, long n, int C, const float* scale, const float* shift, int act, void* z_hi,
                               void* z_lo, void* stream);
-/*      the guarded Adam launches with a third shadow: pl16 = fp16(p - fp16(p)), the weights' lo halves, rewritten in the same pass */
-int sarssl_adam_step_guard_lo(float* p, const float* g, float* m, float* v, void* p16, void* ph16, void* pl16, long n, float gscale, float lr,
-                              float beta1, float beta2, float eps, int step, const float* guard, int* nskipped, void* stream);
-int sarssl_adam_step_dev_guard_lo(float* p, float* g, float* m, float* v, void* p16, void* ph16, void* pl16, long n, float gscale, void* state,
-                                  float eps, int zero_grad, const float* guard, void* stream);
+/*      the weights' lo halves pl16 = fp16(p - fp16(p)) are rewritten by the Adam launches (sarssl_adam_step / _dev) in the same pass */
 /*      src (f32 | fp16 | bf16; n % 4 == 0) -> hi = fp16(src) (may be NULL), lo = fp16(src - hi): the weights' lo shadow, stem outputs. */
 int sarssl_split_pair(const void* src, int src_dtype, long n, void* hi, void* lo, void* stream);
 
@@ -269,7 +265,7 @@ int sarssl_ffn_pack(const void* const* src, void* const* dst, const int* N, cons
 /*      LayerNorm in the same launch (feed_forward.py:48 and its backward; arithmetic of sarssl_layernorm_fwd / _bwd):
  *      forward,  x_ln != NULL: ln = LayerNorm(x_ln; gamma, beta, eps) is formed in the launch's prologue (bit-identical to
  *                sarssl_layernorm_fwd), written to ln_out [M][d] with ln_mean / ln_rstd [M]; the `ln` argument is ignored.
- *      backward, x_ln != NULL (the module's saved input, dtype of preact): the epilogue runs sarssl_layernorm_bwd(_drop) on the second
+ *      backward, x_ln != NULL (the module's saved input, dtype of preact): the epilogue runs sarssl_layernorm_bwd on the second
  *                product - `dln` receives dx = LayerNorm'(dh W1) + resid, dx2 (optional, [M][d]) = dx * dropmask(p2, s2) * gscale2,
  *                ln_partial [M / 64][2][d] the per-tile dgamma | dbeta sums (fold: sarssl_ln_param_reduce_multi, nparts = M / 64). */
 int sarssl_ffn2_fwd(const void* ln, long ldln, const void* w1p, const void* w2p, const float* b1, const float* b2, void* preact,
@@ -280,22 +276,6 @@ int sarssl_ffn2_bwd(const void* dz2, long lddz, const void* w2tp, const void* w1
                     long M, int d, float p1, unsigned long long s1, const void* x_ln, long ldx, const float* ln_gamma,
                     const float* ln_mean, const float* ln_rstd, const void* resid, long ldr, void* dx2, float p2, unsigned long long s2,
                     float gscale2, float* ln_partial, int dtype, void* stream);
-
-/* ---- row-tile-resident Linear layers of the d = 256 Conformer blocks (round 5, csrc/lin256.hip): nn.Linear / Conv1d(k = 1) forward and
- *      data gradient (code/common/conformer/attention.py:82-85, :113 q/k/v and output projections; convolution.py:138, :143 pointwise
- *      convolutions) as ONE launch per layer with the 64 x K input tile resident in LDS and the weights read from fragment-order packs
- *      (sarssl_ffn_pack) - optionally together with the LayerNorm in front of the layer (attention.py:146, convolution.py:137; forward:
- *      prologue, bit-identical to sarssl_layernorm_fwd; backward: sarssl_layernorm_bwd(_drop) in the epilogue).  Replaces sarssl_gemm (+ the
- *      LayerNorm launches) for these shapes: M % 64 == 0, N and K multiples of 256, K <= 768, K == 256 or N == 256.
- *      fwd: y = resid + out_scale * drop(p, seed)(a W^T + bias), wp = pack(W [N x K]); dtype SARSSL_F16 | SARSSL_BF16.
- *      bwd: dx = dy Wt^T, wtp = pack(W^T [N x K]) with N = the layer's input width; dtype SARSSL_BF16 | SARSSL_MIX16 (fp16 x_ln). */
-int sarssl_lin256_supported(long M, int N, int K);
-int sarssl_lin256_fwd(const void* a, long lda, const void* wp, const float* bias, void* y, long ldy, const void* resid, long ldr, long M,
-                      int N, int K, float p, unsigned long long seed, float out_scale, const void* x_ln, long ldx, const float* ln_gamma,
-                      const float* ln_beta, float ln_eps, void* ln_out, float* ln_mean, float* ln_rstd, int dtype, void* stream);
-int sarssl_lin256_bwd(const void* dy, long lddy, const void* wtp, void* dx, long lddx, long M, int N, int K, const void* x_ln, long ldx,
-                      const float* ln_gamma, const float* ln_mean, const float* ln_rstd, const void* resid, long ldr, void* dx2, float p2,
-                      unsigned long long s2, float gscale2, float* ln_partial, int dtype, void* stream);
 
 /* ---- OCP fp8 (e4m3fn) GEMM path (BASELINE.json config 5; no reference counterpart - the reference is fp32 / fp16-AMP,
  *      code/learner.py:46-50): per-tensor scales chosen on the device, block-scaled MFMA with unit block scales, same fused epilogue as
@@ -439,11 +419,9 @@ int sarssl_conv3x3_dgrad_c1red(const void* dy, const void* w, const void* a0, co
                                int nb, int F, int T, double* red, int a0_dtype, void* stream);
 int sarssl_stem_c1_bwd_finalize_mom(const double* red, const double* mom14, const float* W1, long npix, const float* aff, int use_stats,
                                     float* dW1, float* dgamma, float* dbeta, void* stream);
+/* stats8 (may be NULL): the BatchNorm sums of the stored output, f64[8] = [sum (4) | sum of squares (4)], zeroed by the call */
 int sarssl_stem_c4_fwd(const void* y3, const float* W4, const float* scale, const float* shift, int nb, int F, int Tn, void* y4,
-                       int dtype, void* stream);
-/* sarssl_stem_c4_fwd that also returns the BatchNorm sums of its stored output: stats8 f64[8] = [sum (4) | sum of squares (4)] */
-int sarssl_stem_c4_fwd_stats(const void* y3, const float* W4, const float* scale, const float* shift, int nb, int F, int Tn, void* y4,
-                             double* stats8, int dtype, void* stream);
+                       double* stats8, int dtype, void* stream);
 int sarssl_stem_c4_bwd(const void* y3, const void* dy4, const float* W4, const float* scale, const float* shift,
                        const float* mean, const float* rstd, int nb, int F, int Tn, void* g3, double* red, int dtype,
                        void* stream);
@@ -451,14 +429,11 @@ int sarssl_stem_c4_bwd(const void* y3, const void* dy4, const float* W4, const f
  *      BatchNorm(3)-input gradient dy3 directly (the 64->4 contraction is recomputed); use_stats = 0: eval-mode BatchNorm. */
 int sarssl_stem_c4_bwd_sums(const void* y3, const void* dy4, const float* W4, const float* scale, const float* shift,
                             const float* mean, const float* rstd, int nb, int F, int Tn, double* red, int dtype, void* stream);
+/*      gW4 / dgamma / dbeta (all three or all NULL): workgroup 0 also adds the parameter gradients from the finished sums - gW4 (4,64) +=
+ *      red[0:256], dbeta += red[256:320], dgamma += red[320:384] */
 int sarssl_stem_c4_bwd_apply(const void* y3, const void* dy4, const float* W4, const float* scale, const float* shift,
-                             const float* mean, const float* rstd, int nb, int F, int Tn, const double* red, int use_stats,
-                             void* dy3, int dtype, void* stream);
-/* the same pass; workgroup 0 also adds the parameter gradients from the finished sums: gW4 (4,64) += red[0:256], dbeta += red[256:320],
- * dgamma += red[320:384] */
-int sarssl_stem_c4_bwd_apply_pg(const void* y3, const void* dy4, const float* W4, const float* scale, const float* shift,
-                                const float* mean, const float* rstd, int nb, int F, int Tn, const double* red, int use_stats, void* dy3,
-                                float* gW4, float* dgamma, float* dbeta, int dtype, void* stream);
+                             const float* mean, const float* rstd, int nb, int F, int Tn, const double* red, int use_stats, void* dy3,
+                             float* gW4, float* dgamma, float* dbeta, int dtype, void* stream);
 
 /* ---- BatchNorm{1,2}d on channels-last [N][C] tensors (training statistics, running-stat update, backward):
  *      nn.BatchNorm2d in code/model.py:52-61, nn.BatchNorm1d in code/common/conformer/convolution.py:142 */
@@ -478,13 +453,10 @@ int sarssl_cl_bn_train_act(const void* x, long N, int C, const double* sums, con
                            float* rstd, int act, void* z, int dtype, void* stream);
 int sarssl_cl_bn_bwd_reduce(const void* dz, const void* y, long N, int C, const float* scale, const float* shift,
                             const float* mean, const float* rstd, int act, double* red, int dtype, void* stream);
-int sarssl_cl_bn_bwd_apply(const void* dz, const void* y, long N, int C, const float* scale, const float* shift,
-                           const float* mean, const float* rstd, int act, int g_is_masked, int use_stats, const double* red,
-                           void* dy, int dtype, void* stream);
-/* the same pass; workgroup 0 also adds the BatchNorm parameter gradients dbeta += red[0:C], dgamma += red[C:2C] */
-int sarssl_cl_bn_bwd_apply_pg(const void* dz, const void* y, long N, int C, const float* scale, const float* shift, const float* mean,
-                              const float* rstd, int act, int g_is_masked, int use_stats, const double* red, void* dy, float* dgamma,
-                              float* dbeta, int dtype, void* stream);
+/* dgamma / dbeta (both or both NULL): workgroup 0 also adds the BatchNorm parameter gradients dbeta += red[0:C], dgamma += red[C:2C] */
+int sarssl_cl_bn_bwd_apply(const void* dz, const void* y, long N, int C, const float* scale, const float* shift, const float* mean,
+                           const float* rstd, int act, int g_is_masked, int use_stats, const double* red, void* dy, float* dgamma,
+                           float* dbeta, int dtype, void* stream);
 
 /* ---- depthwise-conv part of the Conformer convolution module as LDS tiles (convolution.py:139-143 and its backward): GLU fused
  *      into the tile load, BatchNorm1d batch sums in the epilogue; the data gradient fused with the GLU backward; the weight gradient
@@ -500,7 +472,7 @@ int sarssl_dwglu_wgrad(const void* dc, const void* h, int nb, int Tn, int d, int
  *      (attention.py:87-113), u/v bias add (attention.py:87-88) */
 /*      sarssl_layernorm_fwd / _bwd: any d % 4 == 0.  d <= 1024: a wave per row, the row in registers (the encoder's 256 / 512);
  *      d > 1024: a 256-thread workgroup per row, re-read per pass (the multi-pair head); same f32 statistics, same partials layout and
- *      workspace.  Every other LayerNorm entry point (_fwd2, _fwd_pair, _fwd2_pair, _bwd_drop, _bwd_stream) takes d <= 1024. */
+ *      workspace.  Every other LayerNorm entry point (_fwd2, _fwd_pair, _fwd2_pair, _bwd_stream), and _bwd with dx2, takes d <= 1024. */
 int sarssl_layernorm_fwd(const void* x, long ldx, long M, int d, const float* gamma, const float* beta, float eps, void* y,
                          long ldy, float* mean, float* rstd, int dtype, void* stream);
 /* a Conformer block's closing LayerNorm followed by the first LayerNorm of the next block's feed-forward module (Conformer.py:88-90,
@@ -509,15 +481,13 @@ int sarssl_layernorm_fwd2(const void* x, long ldx, long M, int d, const float* g
                           float* mean_a, float* rstd_a, const float* gamma_b, const float* beta_b, float eps_b, void* z, long ldz,
                           float* mean_b, float* rstd_b, int dtype, void* stream);
 long sarssl_layernorm_bwd_workspace_bytes(long M, int d);
+/*      dx2 (may be NULL; d <= 1024) [M][d] = dx * dropout_mask(seed, m*d + c) * gscale, i.e. the sarssl_act_bwd(act = 0) pass the next
+ *      module of the backward chain (Dropout backward of feed_forward.py:53 / attention.py:151 / convolution.py:145 + the half-step
+ *      factor) starts with; p_drop / seed / gscale are read only with dx2 */
 int sarssl_layernorm_bwd(const void* dy, long lddy, const void* x, long ldx, long M, int d, const float* gamma,
                          const float* mean, const float* rstd, const void* resid, long ldr, void* dx, long lddx,
-                         float* dgamma, float* dbeta, float* partial, int dtype, void* stream);
-/*      + dx2 [M][d] = dx * dropout_mask(seed, m*d + c) * gscale, i.e. the sarssl_act_bwd(act = 0) pass the next module of the backward
- *      chain (Dropout backward of feed_forward.py:53 / attention.py:151 / convolution.py:145 + the half-step factor) starts with */
-int sarssl_layernorm_bwd_drop(const void* dy, long lddy, const void* x, long ldx, long M, int d, const float* gamma,
-                              const float* mean, const float* rstd, const void* resid, long ldr, void* dx, long lddx,
-                              float* dgamma, float* dbeta, float* partial, void* dx2, float p_drop, unsigned long long seed,
-                              float gscale, int dtype, void* stream);
+                         float* dgamma, float* dbeta, float* partial, void* dx2, float p_drop, unsigned long long seed,
+                         float gscale, int dtype, void* stream);
 /*      dgamma == NULL with partial != NULL: the [nparts][2 d] partial sums only (nparts = sarssl_layernorm_bwd_nparts(M)); the folds
  *      of up to 8 such launches (the LayerNorms of one Conformer block) then run as one launch: dgamma_q / dbeta_q += ... */
 int sarssl_layernorm_bwd_nparts(long M);
@@ -558,17 +528,12 @@ int sarssl_f64_accum2(const double* src, float* dst1, float* dst2, int n, void* 
  * they lie inside [base, base + bytes), an arena the caller zeroes itself once per forward / backward pass (NULL unregisters). */
 
 /* ---- loss: code/model.py:585-592 (channel select) + 721-747 (gen_loss).  fwd: sums = f64[128] scratch, out = f32[2]
- * (loss, diff); F <= 480. */
+ * (loss, diff); F <= 480.  The finalize launch also copies (loss, diff) to out_keep (f32[2]) and adds them to acc (f64[2]); either may
+ * be NULL (the captured step's running sums, learner.py:104-110).  dpred (may be NULL): in the same pass the loss's gradient w.r.t. pred
+ * for an incoming gradient of 1 (= sarssl_masked_mse_bwd with gscale 1), (nb, Tn, F*4) of the gradient dtype; dtype is then the pairing
+ * bf16 | f32 | mixed 16 (pred fp16, dpred bf16), else pred's dtype. */
 int sarssl_masked_mse_fwd(const void* pred, const float* x, const int* idx, const int* mch, int nb, int F, int Tn, int nm,
-                          double* sums, float* out, int dtype, void* stream);
-/*      the same; the finalize launch also copies (loss, diff) to out_keep (f32[2]) and adds them to acc (f64[2]); either may be null
- *      (the captured step's running sums, learner.py:104-110) */
-int sarssl_masked_mse_fwd_acc(const void* pred, const float* x, const int* idx, const int* mch, int nb, int F, int Tn, int nm,
-                              double* sums, float* out, float* out_keep, double* acc, int dtype, void* stream);
-/* loss and, in the same pass, its gradient w.r.t. pred for an incoming gradient of 1 (= sarssl_masked_mse_bwd with gscale 1):
- * dpred (nb, Tn, F*4) of the gradient dtype; dtype: bf16 | f32 | mixed 16 (pred fp16, dpred bf16) */
-int sarssl_masked_mse_fwd_bwd(const void* pred, const float* x, const int* idx, const int* mch, int nb, int F, int Tn, int nm,
-                              double* sums, float* out, float* out_keep, double* acc, void* dpred, int dtype, void* stream);
+                          double* sums, float* out, float* out_keep, double* acc, void* dpred, int dtype, void* stream);
 int sarssl_masked_mse_bwd(const void* pred, const float* x, const unsigned char* mp, const int* mch, int nb, int F, int Tn,
                           int nm, float gscale, const float* gscale_dev, void* dpred, int dtype, void* stream);
 /* ---- the decoder on the masked frames only (round 5).  gen_loss (code/model.py:721-747) reads the prediction at the masked frames of
@@ -592,14 +557,13 @@ int sarssl_masked_mse_bwd_compact(const void* pred_c, const float* x, const int*
                                   float gscale, const float* gscale_dev, void* dpred_c, int dtype, void* stream);
 
 /* ---- optimiser: torch.optim.Adam(betas=(0.9,0.999), weight_decay=0) at code/learner.py:83, over one flat buffer */
-/*      p16 / ph16 (either may be null): bf16 / fp16 shadow copies of the updated parameters, the GEMM / convolution operands */
-int sarssl_adam_step(float* p, const float* g, float* m, float* v, void* p16, void* ph16, long n, float gscale, float lr, float beta1,
-                     float beta2, float eps, int step, void* stream);
-/*      the same behind a device-side guard: `guard` -> the step's loss (f32 on the device).  Not finite -> the update is skipped as a
- *      whole (parameters, moments, shadow copies untouched; *nskipped += 1 when given): torch.cuda.amp.GradScaler.step of the reference's
- *      fp16 autocast path (code/learner.py:105-108: a step whose forward overflowed is not an optimizer step) without a host sync. */
-int sarssl_adam_step_guard(float* p, const float* g, float* m, float* v, void* p16, void* ph16, long n, float gscale, float lr, float beta1,
-                           float beta2, float eps, int step, const float* guard, int* nskipped, void* stream);
+/*      p16 / ph16 / pl16 (each may be NULL): bf16 / fp16 shadow copies of the updated parameters, the GEMM / convolution operands, and
+ *      (hybrid mode) the fp16 lo shadow pl16 = fp16(p - fp16(p)), rewritten in the same pass.
+ *      guard (may be NULL) -> the step's loss (f32 on the device).  Not finite -> the update is skipped as a whole (parameters, moments,
+ *      shadow copies untouched; *nskipped += 1 when given): torch.cuda.amp.GradScaler.step of the reference's fp16 autocast path
+ *      (code/learner.py:105-108: a step whose forward overflowed is not an optimizer step) without a host sync. */
+int sarssl_adam_step(float* p, const float* g, float* m, float* v, void* p16, void* ph16, void* pl16, long n, float gscale, float lr,
+                     float beta1, float beta2, float eps, int step, const float* guard, int* nskipped, void* stream);
 
 /* ---- device-resident step state: what varies from step to step when the whole step (code/learner.py:93-115: forward, backward,
  *      optimizer.step(), optimizer.zero_grad()) is replayed from a hipGraph with frozen launch arguments.  `state` is
@@ -611,12 +575,10 @@ long sarssl_step_state_bytes(void);
 int sarssl_step_state_init(void* state, unsigned long long salt, float lr, float beta1, float beta2, void* stream);
 int sarssl_step_state_reset(void* state, float lr, float beta1, float beta2, void* stream);
 int sarssl_step_tick(void* state, void* stream);
-int sarssl_adam_step_dev(float* p, float* g, float* m, float* v, void* p16, void* ph16, long n, float gscale, const void* state,
-                         float eps, int zero_grad, void* stream);
-/*      guarded form (see sarssl_adam_step_guard): a skipped step still clears the gradient buffer (zero_grad), takes the state's step
+/*      guard (may be NULL) as in sarssl_adam_step: a skipped step still clears the gradient buffer (zero_grad), takes the state's step
  *      count back by one and counts itself in the state (sarssl_step_state_skipped) */
-int sarssl_adam_step_dev_guard(float* p, float* g, float* m, float* v, void* p16, void* ph16, long n, float gscale, void* state, float eps,
-                               int zero_grad, const float* guard, void* stream);
+int sarssl_adam_step_dev(float* p, float* g, float* m, float* v, void* p16, void* ph16, void* pl16, long n, float gscale, void* state,
+                         float eps, int zero_grad, const float* guard, void* stream);
 int sarssl_step_state_skipped(const void* state, void* stream);      /* synchronises `stream`; -> steps skipped since init, < 0 on error */
 
 /* ---- collectives: the gradient exchange of data-parallel training (replaces torch.nn.DataParallel's per-step replicate / gather /

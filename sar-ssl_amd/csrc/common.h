@@ -45,7 +45,7 @@ struct SarsslStepState {
     float lr, beta1, beta2;
     float step_size;             // lr / (1 - beta1^step)
     float inv_bc2_sqrt;          // 1 / sqrt(1 - beta2^step)
-    int nskipped;                // optimizer steps skipped because the step's loss was not finite (sarssl_adam_step_dev_guard)
+    int nskipped;                // optimizer steps skipped because the step's loss was not finite (sarssl_adam_step_dev behind a guard)
 };
 int sarssl_mfma_prio();         // where waves raise their issue priority (s_setprio) during MFMA phases: 2 = the ping-pong convolution only
 bool sarssl_prezeroed(const void* p);               // pointer inside the host-zeroed arena (api.hip): its memset can be skipped

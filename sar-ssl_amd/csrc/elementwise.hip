@@ -220,8 +220,8 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const T* __restrict_
                                                             const float* __restrict__ mean, const float* __restrict__ rstd,
                                                             const T* __restrict__ resid, long ldr, T* __restrict__ dx, long lddx,
                                                             float* __restrict__ partial /* [gridDim.x][2][d] or null */,
-                                                            T* __restrict__ dx2 = nullptr, float p_drop = 0.f, unsigned long long seed0 = 0,
-                                                            const unsigned long long* __restrict__ salt = nullptr, float gscale = 1.f) {
+                                                            T* __restrict__ dx2 /* or null */, float p_drop, unsigned long long seed0,
+                                                            const unsigned long long* __restrict__ salt /* or null */, float gscale) {
     // dx2 (optional, contiguous [M][d]): dx * dropout_mask(seed, m*d + c) * gscale - the dropout backward the NEXT module of the
     // backward chain applies to its incoming gradient (act_bwd), produced here while dx is still in registers
     const unsigned long long seed = salted_seed(seed0, salt);
@@ -1011,7 +1011,7 @@ __global__ void masked_mse_bwd_kernel(const TA* __restrict__ pred, const float* 
 __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                             bf16* __restrict__ p16, f16* __restrict__ ph16, long n, float gscale, float beta1, float beta2, float step_size,
                             float inv_bc2_sqrt, float eps, const float* __restrict__ guard, int* __restrict__ nskipped,
-                            f16* __restrict__ pl16 = nullptr /* hybrid mode: fp16(p - fp16(p)), the lo shadow */) {
+                            f16* __restrict__ pl16 /* hybrid mode: fp16(p - fp16(p)), the lo shadow; may be null */) {
     if (guard && !isfinite(guard[0])) {
         if (nskipped && blockIdx.x == 0 && threadIdx.x == 0) nskipped[0] += 1;
         return;
@@ -1034,7 +1034,7 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
 // gradient buffer in the same pass (the reference's optimizer.zero_grad() right after optimizer.step(), code/learner.py:113-115).
 __global__ void adam_dev_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                                 bf16* __restrict__ p16, f16* __restrict__ ph16, long n, float gscale, SarsslStepState* __restrict__ st, float eps,
-                                int zero_g, const float* __restrict__ guard, f16* __restrict__ pl16 = nullptr) {
+                                int zero_g, const float* __restrict__ guard, f16* __restrict__ pl16) {
     const float beta1 = st->beta1, beta2 = st->beta2, step_size = st->step_size, inv_bc2_sqrt = st->inv_bc2_sqrt;
     if (guard && !isfinite(guard[0])) {
         // skipped step: nothing moves, the gradient buffer is still cleared (zero_grad follows the step), the Adam step count is taken
@@ -1098,18 +1098,24 @@ extern "C" long sarssl_layernorm_bwd_workspace_bytes(long M, int d) {
 }
 // dgamma/dbeta accumulate (+=) through per-workgroup partials in `partial` (sarssl_layernorm_bwd_workspace_bytes) and a second
 // reduce kernel; pass dgamma = null to skip the parameter gradients.
+// dx2 (may be null; d <= 1024): a second output [M][d] (contiguous) = dx * dropout_mask(seed, m*d + c) * gscale: the dropout backward
+// (sarssl_act_bwd, act = 0) the next module of the backward chain would run on dx as its first step.  Without dx2 the kernel reads none of
+// p_drop / seed / gscale, and no salt is handed to it.
 extern "C" int sarssl_layernorm_bwd(const void* dy, long lddy, const void* x, long ldx, long M, int d, const float* gamma,
                                     const float* mean, const float* rstd, const void* resid, long ldr, void* dx, long lddx,
-                                    float* dgamma, float* dbeta, float* partial, int dtype, void* stream) {
+                                    float* dgamma, float* dbeta, float* partial, void* dx2, float p_drop, unsigned long long seed,
+                                    float gscale, int dtype, void* stream) {
     SARSSL_REQUIRE(M > 0 && d > 0 && (d & 3) == 0 && (!dgamma || partial), "sarssl_layernorm_bwd");
+    SARSSL_REQUIRE(!dx2 || d <= 1024, "sarssl_layernorm_bwd(dx2)");
     const int nblk = ln_bwd_blocks(M);
     float* part = partial;          // dgamma == null && partial != null: partials only, folded later (sarssl_ln_param_reduce_multi)
     if (d > 1024) {                 // one workgroup per partial row (layernorm_bwd_wide_kernel), same partials layout and workspace
         DISPATCH_GA(dtype, (layernorm_bwd_wide_kernel<T, TA><<<nblk, 256, 0, ST>>>((const T*)dy, lddy, (const TA*)x, ldx, M, d, gamma, mean,
                                                                                    rstd, (const T*)resid, ldr, (T*)dx, lddx, part)));
     } else {
+        const unsigned long long* salt = dx2 ? sarssl_dropout_salt() : nullptr;
 #define LN_BWD_LAUNCH(NVv) layernorm_bwd_kernel<T, TA, NVv><<<nblk, 256, 0, ST>>>((const T*)dy, lddy, (const TA*)x, ldx, M, d, gamma, mean, rstd, \
-                                                                           (const T*)resid, ldr, (T*)dx, lddx, part)
+                                                                           (const T*)resid, ldr, (T*)dx, lddx, part, (T*)dx2, p_drop, seed, salt, gscale)
         DISPATCH_GA(dtype, (d <= 256 ? LN_BWD_LAUNCH(1) : (d <= 512 ? LN_BWD_LAUNCH(2) : LN_BWD_LAUNCH(4))));
 #undef LN_BWD_LAUNCH
     }
@@ -1117,24 +1123,6 @@ extern "C" int sarssl_layernorm_bwd(const void* dy, long lddy, const void* x, lo
         ln_param_reduce_kernel<<<(2 * d + 63) / 64, 1024, 0, ST>>>(part, nblk, d, dgamma, dbeta);
     }
     SARSSL_CHECK_LAUNCH("layernorm_bwd_kernel");
-    return 0;
-}
-// The same with a second output dx2 [M][d] (contiguous) = dx * dropout_mask(seed, m*d + c) * gscale: the dropout backward (sarssl_act_bwd,
-// act = 0) the next module of the backward chain would run on dx as its first step.
-extern "C" int sarssl_layernorm_bwd_drop(const void* dy, long lddy, const void* x, long ldx, long M, int d, const float* gamma,
-                                         const float* mean, const float* rstd, const void* resid, long ldr, void* dx, long lddx,
-                                         float* dgamma, float* dbeta, float* partial, void* dx2, float p_drop, unsigned long long seed,
-                                         float gscale, int dtype, void* stream) {
-    SARSSL_REQUIRE(M > 0 && d > 0 && (d & 3) == 0 && d <= 1024 && (!dgamma || partial) && dx2, "sarssl_layernorm_bwd_drop");
-    const int nblk = ln_bwd_blocks(M);
-    float* part = partial;
-    const unsigned long long* salt = sarssl_dropout_salt();
-#define LN_BWD_LAUNCH(NVv) layernorm_bwd_kernel<T, TA, NVv><<<nblk, 256, 0, ST>>>((const T*)dy, lddy, (const TA*)x, ldx, M, d, gamma, mean, rstd, \
-                                                                           (const T*)resid, ldr, (T*)dx, lddx, part, (T*)dx2, p_drop, seed, salt, gscale)
-    DISPATCH_GA(dtype, (d <= 256 ? LN_BWD_LAUNCH(1) : (d <= 512 ? LN_BWD_LAUNCH(2) : LN_BWD_LAUNCH(4))));
-#undef LN_BWD_LAUNCH
-    if (dgamma) ln_param_reduce_kernel<<<(2 * d + 63) / 64, 1024, 0, ST>>>(part, nblk, d, dgamma, dbeta);
-    SARSSL_CHECK_LAUNCH("layernorm_bwd_kernel(drop)");
     return 0;
 }
 extern "C" int sarssl_layernorm_bwd_nparts(long M) { return ln_bwd_blocks(M); }
@@ -1312,7 +1300,7 @@ extern "C" int sarssl_f64_accum(const double* src, float* dst, int n, float scal
 // out: f32[2] = (loss, diff).  sums: f64[128] workspace (zeroed here).
 static int masked_mse_fwd_impl(const void* pred, const float* x, const int* idx, const int* mch, int nb, int F, int Tn,
                                int nm, double* sums, float* out, float* out_keep, double* acc, int dtype, void* stream,
-                               void* dpred = nullptr, bool compact = false) {
+                               void* dpred, bool compact) {
     const size_t lds = (size_t)MSE_TT * F * 4 * sizeof(float);
     SARSSL_REQUIRE(nb > 0 && nm > 0 && lds <= 60 * 1024, "sarssl_masked_mse_fwd (F <= 480)");
     const int groups = (Tn + MSE_TT - 1) / MSE_TT;
@@ -1331,22 +1319,13 @@ static int masked_mse_fwd_impl(const void* pred, const float* x, const int* idx,
     SARSSL_CHECK_LAUNCH("masked_mse_fwd_kernel");
     return 0;
 }
-extern "C" int sarssl_masked_mse_fwd(const void* pred, const float* x, const int* idx, const int* mch, int nb, int F, int Tn,
-                                     int nm, double* sums, float* out, int dtype, void* stream) {
-    return masked_mse_fwd_impl(pred, x, idx, mch, nb, F, Tn, nm, sums, out, nullptr, nullptr, dtype, stream);
-}
-// The same; the finalize launch also copies (loss, diff) to out_keep (f32[2]) and adds them to acc (f64[2]) - either may be null.
-extern "C" int sarssl_masked_mse_fwd_acc(const void* pred, const float* x, const int* idx, const int* mch, int nb, int F, int Tn,
-                                         int nm, double* sums, float* out, float* out_keep, double* acc, int dtype, void* stream) {
-    return masked_mse_fwd_impl(pred, x, idx, mch, nb, F, Tn, nm, sums, out, out_keep, acc, dtype, stream);
-}
-// Loss forward AND its gradient w.r.t. pred for an incoming gradient of 1 in one pass over pred / x (gen_loss, code/model.py:585-592, and
-// its backward): dpred (nb, Tn, F*4) of the gradient dtype = what sarssl_masked_mse_bwd(gscale = 1) writes.  dtype: bf16 | f32 | mixed 16.
-extern "C" int sarssl_masked_mse_fwd_bwd(const void* pred, const float* x, const int* idx, const int* mch, int nb, int F, int Tn,
-                                         int nm, double* sums, float* out, float* out_keep, double* acc, void* dpred, int dtype,
-                                         void* stream) {
-    SARSSL_REQUIRE(dpred != nullptr, "sarssl_masked_mse_fwd_bwd");
-    return masked_mse_fwd_impl(pred, x, idx, mch, nb, F, Tn, nm, sums, out, out_keep, acc, dtype, stream, dpred);
+// dpred (may be null): in the same pass, the loss's gradient w.r.t. pred for an incoming gradient of 1 (gen_loss, code/model.py:585-592,
+// and its backward) - dpred (nb, Tn, F*4) of the gradient dtype = what sarssl_masked_mse_bwd(gscale = 1) writes; dtype is then the gradient /
+// saved-activation pairing (bf16 | f32 | mixed 16), a plain dtype otherwise.  The finalize launch also copies (loss, diff) to out_keep
+// (f32[2]) and adds them to acc (f64[2]) - either may be null.
+extern "C" int sarssl_masked_mse_fwd(const void* pred, const float* x, const int* idx, const int* mch, int nb, int F, int Tn, int nm,
+                                     double* sums, float* out, float* out_keep, double* acc, void* dpred, int dtype, void* stream) {
+    return masked_mse_fwd_impl(pred, x, idx, mch, nb, F, Tn, nm, sums, out, out_keep, acc, dtype, stream, dpred, false);
 }
 // ---- the decoder on the masked frames only.  gen_loss (code/model.py:721-747) reads the prediction at the masked frames of the masked
 // channel and nowhere else, and the decoder (Linear - ReLU - Linear, code/model.py:296-301) acts on every frame independently: rows of
@@ -1437,7 +1416,7 @@ extern "C" int sarssl_scatter_rows_drop16(const float* src, const int* idx, int 
     return 0;
 }
 // loss (and, dpred != null, its gradient for an incoming gradient of 1) on the compact prediction pred_c [nb][nm][F * 4]; idx must be
-// ascending per item.  dtype as sarssl_masked_mse_fwd (dpred == null) / sarssl_masked_mse_fwd_bwd (dpred != null).
+// ascending per item.  dtype as sarssl_masked_mse_fwd.
 extern "C" int sarssl_masked_mse_compact(const void* pred_c, const float* x, const int* idx, const int* mch, int nb, int F, int Tn, int nm,
                                          double* sums, float* out, float* out_keep, double* acc, void* dpred_c, int dtype, void* stream) {
     return masked_mse_fwd_impl(pred_c, x, idx, mch, nb, F, Tn, nm, sums, out, out_keep, acc, dtype, stream, dpred_c, true);
@@ -1477,19 +1456,10 @@ extern "C" int sarssl_masked_mse_bwd(const void* pred, const float* x, const uns
     SARSSL_CHECK_LAUNCH("masked_mse_bwd_kernel");
     return 0;
 }
-// p16 / ph16 (either may be null): bf16 and fp16 shadow copies of the updated parameters (the GEMM / convolution operands)
-extern "C" int sarssl_adam_step_guard(float* p, const float* g, float* m, float* v, void* p16, void* ph16, long n, float gscale, float lr,
-                                      float beta1, float beta2, float eps, int step, const float* guard, int* nskipped, void* stream) {
-    SARSSL_REQUIRE(n > 0 && step >= 1, "sarssl_adam_step");
-    const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
-    adam_kernel<<<nblocks_for(n, 256, 8192), 256, 0, ST>>>(p, g, m, v, (bf16*)p16, (f16*)ph16, n, gscale, beta1, beta2, (float)(lr / bc1),
-                                                           (float)(1.0 / sqrt(bc2)), eps, guard, nskipped);
-    SARSSL_CHECK_LAUNCH("adam_kernel");
-    return 0;
-}
-// hybrid mode: the same pass also rewrites the fp16 lo shadow pl16 = fp16(p - fp16(p)) (with ph16 the pair a forward product contracts against)
-extern "C" int sarssl_adam_step_guard_lo(float* p, const float* g, float* m, float* v, void* p16, void* ph16, void* pl16, long n, float gscale,
-                                         float lr, float beta1, float beta2, float eps, int step, const float* guard, int* nskipped, void* stream) {
+// p16 / ph16 / pl16 (each may be null): bf16 and fp16 shadow copies of the updated parameters (the GEMM / convolution operands) and, hybrid
+// mode, the fp16 lo shadow pl16 = fp16(p - fp16(p)) (with ph16 the pair a forward product contracts against); guard / nskipped may be null
+extern "C" int sarssl_adam_step(float* p, const float* g, float* m, float* v, void* p16, void* ph16, void* pl16, long n, float gscale, float lr,
+                                float beta1, float beta2, float eps, int step, const float* guard, int* nskipped, void* stream) {
     SARSSL_REQUIRE(n > 0 && step >= 1, "sarssl_adam_step");
     const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
     adam_kernel<<<nblocks_for(n, 256, 8192), 256, 0, ST>>>(p, g, m, v, (bf16*)p16, (f16*)ph16, n, gscale, beta1, beta2, (float)(lr / bc1),
@@ -1497,27 +1467,11 @@ extern "C" int sarssl_adam_step_guard_lo(float* p, const float* g, float* m, flo
     SARSSL_CHECK_LAUNCH("adam_kernel");
     return 0;
 }
-extern "C" int sarssl_adam_step_dev_guard_lo(float* p, float* g, float* m, float* v, void* p16, void* ph16, void* pl16, long n, float gscale,
-                                             void* state, float eps, int zero_grad, const float* guard, void* stream) {
+extern "C" int sarssl_adam_step_dev(float* p, float* g, float* m, float* v, void* p16, void* ph16, void* pl16, long n, float gscale, void* state,
+                                    float eps, int zero_grad, const float* guard, void* stream) {
     SARSSL_REQUIRE(n > 0 && state, "sarssl_adam_step_dev");
     adam_dev_kernel<<<nblocks_for(n, 256, 8192), 256, 0, ST>>>(p, g, m, v, (bf16*)p16, (f16*)ph16, n, gscale, (SarsslStepState*)state, eps,
                                                                zero_grad, guard, (f16*)pl16);
     SARSSL_CHECK_LAUNCH("adam_dev_kernel");
     return 0;
-}
-extern "C" int sarssl_adam_step(float* p, const float* g, float* m, float* v, void* p16, void* ph16, long n, float gscale, float lr,
-                                float beta1, float beta2, float eps, int step, void* stream) {
-    return sarssl_adam_step_guard(p, g, m, v, p16, ph16, n, gscale, lr, beta1, beta2, eps, step, nullptr, nullptr, stream);
-}
-extern "C" int sarssl_adam_step_dev_guard(float* p, float* g, float* m, float* v, void* p16, void* ph16, long n, float gscale, void* state,
-                                          float eps, int zero_grad, const float* guard, void* stream) {
-    SARSSL_REQUIRE(n > 0 && state, "sarssl_adam_step_dev");
-    adam_dev_kernel<<<nblocks_for(n, 256, 8192), 256, 0, ST>>>(p, g, m, v, (bf16*)p16, (f16*)ph16, n, gscale, (SarsslStepState*)state, eps,
-                                                               zero_grad, guard);
-    SARSSL_CHECK_LAUNCH("adam_dev_kernel");
-    return 0;
-}
-extern "C" int sarssl_adam_step_dev(float* p, float* g, float* m, float* v, void* p16, void* ph16, long n, float gscale, const void* state,
-                                    float eps, int zero_grad, void* stream) {
-    return sarssl_adam_step_dev_guard(p, g, m, v, p16, ph16, n, gscale, const_cast<void*>(state), eps, zero_grad, nullptr, stream);
 }

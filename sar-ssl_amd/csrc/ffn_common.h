@@ -1,4 +1,4 @@
-// Helpers shared by the row-tile-resident fused launches (ffn2.hip, lin256.hip).
+// Helpers shared by the row-tile-resident fused launches (ffn2.hip, ffn2h.hip).
 #pragma once
 #include <stdlib.h>
 #include "common.h"

@@ -1283,7 +1283,7 @@ extern "C" int sarssl_stem_c1_stats_affine(const void* a0, long npix, const floa
 // (8 bins x 4U frames) items, U loads in flight per thread; 2048 workgroups = one resident round at B = 64 (sweep 1024 / 2048 / 4096 /
 // 8192 with U = 8: 125 / 121 / 126 / 141 us); frame counts that are no multiple of 16 (or bin counts of 8) take the pixel-order loop
 static int stem_c4_fwd_launch(const void* y3, const float* W4, const float* scale, const float* shift, int nb, int F, int Tn, void* y4,
-                              double* stats8, int dtype, void* stream, void* y4lo = nullptr) {
+                              double* stats8, int dtype, void* stream, void* y4lo) {
     SARSSL_REQUIRE(nb > 0 && F > 0 && Tn > 0 && (long)nb * F * Tn < (1L << 31), "sarssl_stem_c4_fwd");
     static const int cap = grid_cap("SARSSL_GRID_C4F", 2048);
     const int u = (F % 8 == 0) ? (Tn % 32 == 0 ? 8 : (Tn % 16 == 0 ? 4 : 0)) : 0;
@@ -1298,17 +1298,12 @@ static int stem_c4_fwd_launch(const void* y3, const float* W4, const float* scal
     SARSSL_CHECK_LAUNCH("stem_c4_fwd_kernel");
     return 0;
 }
-extern "C" int sarssl_stem_c4_fwd(const void* y3, const float* W4, const float* scale, const float* shift, int nb, int F,
-                                  int Tn, void* y4, int dtype, void* stream) {
-    return stem_c4_fwd_launch(y3, W4, scale, shift, nb, F, Tn, y4, nullptr, dtype, stream);
-}
-// The same, also returning the BatchNorm(4) sums of the stored output: stats8 f64[8] = [sum (4) | sum of squares (4)] (zeroed here) - the
-// separate statistics pass over y4 is not needed.
-extern "C" int sarssl_stem_c4_fwd_stats(const void* y3, const float* W4, const float* scale, const float* shift, int nb, int F, int Tn,
-                                        void* y4, double* stats8, int dtype, void* stream) {
-    SARSSL_REQUIRE(stats8 != nullptr, "sarssl_stem_c4_fwd_stats");
-    if (SARSSL_ZERO(stats8, 8 * sizeof(double), ST) != hipSuccess) { sarssl_set_error("memset"); return -2; }
-    return stem_c4_fwd_launch(y3, W4, scale, shift, nb, F, Tn, y4, stats8, dtype, stream);
+// stats8 (may be null): the BatchNorm(4) sums of the stored output, f64[8] = [sum (4) | sum of squares (4)] (zeroed here) - the separate
+// statistics pass over y4 is not needed.
+extern "C" int sarssl_stem_c4_fwd(const void* y3, const float* W4, const float* scale, const float* shift, int nb, int F, int Tn,
+                                  void* y4, double* stats8, int dtype, void* stream) {
+    if (stats8 && SARSSL_ZERO(stats8, 8 * sizeof(double), ST) != hipSuccess) { sarssl_set_error("memset"); return -2; }
+    return stem_c4_fwd_launch(y3, W4, scale, shift, nb, F, Tn, y4, stats8, dtype, stream, nullptr);
 }
 
 // Hybrid mode: the f32 result as a pair of `dtype` tensors (y4_hi = T(o), y4_lo = T(o - y4_hi)); stats8 (may be null) = the sums of the
@@ -1354,19 +1349,11 @@ extern "C" int sarssl_stem_c4_bwd_sums(const void* y3, const void* dy4, const fl
     SARSSL_CHECK_LAUNCH("stem_c4_bwd_kernel<sums>");
     return 0;
 }
-extern "C" int sarssl_stem_c4_bwd_apply_pg(const void* y3, const void* dy4, const float* W4, const float* scale, const float* shift,
-                                           const float* mean, const float* rstd, int nb, int F, int Tn, const double* red,
-                                           int use_stats, void* dy3, float* gW4, float* dgamma, float* dbeta, int dtype, void* stream);
+// workgroup 0 also adds gW4 (4 x 64) += red[0:256], dbeta += red[256:320], dgamma += red[320:384] (all three or none).
 extern "C" int sarssl_stem_c4_bwd_apply(const void* y3, const void* dy4, const float* W4, const float* scale, const float* shift,
                                         const float* mean, const float* rstd, int nb, int F, int Tn, const double* red,
-                                        int use_stats, void* dy3, int dtype, void* stream) {
-    return sarssl_stem_c4_bwd_apply_pg(y3, dy4, W4, scale, shift, mean, rstd, nb, F, Tn, red, use_stats, dy3, nullptr, nullptr, nullptr, dtype, stream);
-}
-// The same pass; workgroup 0 also adds gW4 (4 x 64) += red[0:256], dbeta += red[256:320], dgamma += red[320:384] (all three or none).
-extern "C" int sarssl_stem_c4_bwd_apply_pg(const void* y3, const void* dy4, const float* W4, const float* scale, const float* shift,
-                                           const float* mean, const float* rstd, int nb, int F, int Tn, const double* red,
-                                           int use_stats, void* dy3, float* gW4, float* dgamma, float* dbeta, int dtype, void* stream) {
-    SARSSL_REQUIRE((gW4 == nullptr) == (dgamma == nullptr) && (gW4 == nullptr) == (dbeta == nullptr), "sarssl_stem_c4_bwd_apply_pg");
+                                        int use_stats, void* dy3, float* gW4, float* dgamma, float* dbeta, int dtype, void* stream) {
+    SARSSL_REQUIRE((gW4 == nullptr) == (dgamma == nullptr) && (gW4 == nullptr) == (dbeta == nullptr), "sarssl_stem_c4_bwd_apply");
     static const int cap = grid_cap("SARSSL_GRID_C4A", 4096);
     const int nblk = nblocks_for((long)nb * F * Tn * 8, 256, cap);
     DISPATCH_GA(dtype, (stem_c4_bwd_kernel<T, TA, 2><<<nblk, 256, 0, ST>>>((const TA*)y3, (const T*)dy4, W4, scale, shift, mean, rstd,
@@ -1459,19 +1446,11 @@ extern "C" int sarssl_cl_bn_bwd_reduce(const void* dz, const void* y, long N, in
     return 0;
 }
 
-extern "C" int sarssl_cl_bn_bwd_apply_pg(const void* dz, const void* y, long N, int C, const float* scale, const float* shift,
-                                         const float* mean, const float* rstd, int act, int g_is_masked, int use_stats,
-                                         const double* red, void* dy, float* dgamma, float* dbeta, int dtype, void* stream);
+// workgroup 0 also adds the BatchNorm parameter gradients dbeta += red[0:C], dgamma += red[C:2C] (f32 buffers; both or neither).
 extern "C" int sarssl_cl_bn_bwd_apply(const void* dz, const void* y, long N, int C, const float* scale, const float* shift,
                                       const float* mean, const float* rstd, int act, int g_is_masked, int use_stats,
-                                      const double* red, void* dy, int dtype, void* stream) {
-    return sarssl_cl_bn_bwd_apply_pg(dz, y, N, C, scale, shift, mean, rstd, act, g_is_masked, use_stats, red, dy, nullptr, nullptr, dtype, stream);
-}
-// The same pass; workgroup 0 also adds the BatchNorm parameter gradients dbeta += red[0:C], dgamma += red[C:2C] (f32 buffers; both or neither).
-extern "C" int sarssl_cl_bn_bwd_apply_pg(const void* dz, const void* y, long N, int C, const float* scale, const float* shift,
-                                         const float* mean, const float* rstd, int act, int g_is_masked, int use_stats,
-                                         const double* red, void* dy, float* dgamma, float* dbeta, int dtype, void* stream) {
-    SARSSL_REQUIRE((dgamma == nullptr) == (dbeta == nullptr), "sarssl_cl_bn_bwd_apply_pg");
+                                      const double* red, void* dy, float* dgamma, float* dbeta, int dtype, void* stream) {
+    SARSSL_REQUIRE((dgamma == nullptr) == (dbeta == nullptr), "sarssl_cl_bn_bwd_apply");
     long rows; int L;
     SARSSL_REQUIRE(cl_view(N, C, &rows, &L) && cl_rowthreads_ok(L), "sarssl_cl_bn_bwd_apply");
     static const int cap = grid_cap("SARSSL_GRID_BNA", 1024);       // one resident round (4 workgroups per CU): every further round repeats the per-channel prologue and adds a tail (4096: 378 us, 1024: 321 us at B = 64)

@@ -291,11 +291,6 @@ extern "C" int sarssl_stft_frontend_pairs_masked(const void* sig, int sig_dtype,
     SARSSL_CHECK_LAUNCH("frontend_pack_masked_kernel");
     return 0;
 }
-extern "C" int sarssl_stft_frontend(const void* sig, int sig_dtype, int nb, long nsample, int nch, int win_len, int hop,
-                                    int nfft, int nt, float eps, float* U, double* magsum, float* out, void* stream) {
-    return sarssl_stft_frontend_pairs(sig, sig_dtype, nb, nsample, nch, win_len, hop, nfft, nt, eps, 0, U, magsum, out, stream);
-}
-
 // out: complex64 (B, 257, nt, nch) as interleaved f32 pairs.
 extern "C" int sarssl_stft_raw(const void* sig, int sig_dtype, int nb, long nsample, int nch, int win_len, int hop,
                                int nfft, int nt, float* U, double* magsum, float* out, void* stream) {

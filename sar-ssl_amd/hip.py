@@ -481,74 +481,6 @@ def ffn2_bwd(dz2, w2tp, w1tp, preact, d, p1=0.0, s1=0, ln_bwd=None):
     return dln, dh
 
 
-# ---- row-tile-resident Linear layers of the d = 256 blocks (csrc/lin256.hip) ------------------------------------------------------------
-def lin256_supported(M, N, K, dtype):
-    return dtype in _16 and bool(_lib.lib().sarssl_lin256_supported(c_long(M), c_int(N), c_int(K)))
-
-
-def _ln_partial_register(M, d, dgamma, dbeta, device):
-    """partials [M / 64][2][d] of a fused LayerNorm backward: folded with the block's other LayerNorms inside ln_reduce_batched(), else
-    by the returned callable right behind the launch."""
-    part = torch.empty(((M // 64) * 2 * d,), dtype=torch.float32, device=device)
-    item = (part, M // 64, d, dgamma, dbeta)
-    if _ln_batch is not None:
-        _ln_batch.append(item)
-        return part, None
-
-    def flush():
-        import ctypes
-        _lib.call("sarssl_ln_param_reduce_multi", (ctypes.c_void_p * 1)(item[0].data_ptr()), (ctypes.c_int * 1)(item[1]), (ctypes.c_int * 1)(item[2]),
-                  (ctypes.c_void_p * 1)(item[3].data_ptr()), (ctypes.c_void_p * 1)(item[4].data_ptr()), c_int(1), _stream())
-    return part, flush
-
-
-def lin256_fwd(a, wp, bias, N, K, resid=None, p_drop=0.0, seed=0, out_scale=1.0, out=None, ln_in=None):
-    """y [M, N] = resid + out_scale * drop(a W^T + bias), wp = pack(W [N, K]).  ln_in = (x, gamma, beta, eps): a = LayerNorm(x) formed in the
-    launch -> (y, ln, stats)."""
-    src = a if ln_in is None else ln_in[0]
-    _need_cuda(src, wp, bias, resid, out)
-    M = src.shape[0]
-    if out is None:
-        out = torch.empty((M, N), dtype=src.dtype, device=src.device)
-    lno = stats = None
-    if ln_in is not None:
-        lno = torch.empty((M, K), dtype=src.dtype, device=src.device)
-        stats = torch.empty((2, M), dtype=torch.float32, device=src.device)
-    with _Timed("lin256_fwd[%d,%d%s]" % (N, K, " +ln" if ln_in is not None else "") if _prof_shapes and _prof is not None else None):
-        _lib.call("sarssl_lin256_fwd", _p(a), c_long(a.stride(0) if a is not None else 0), _p(wp), _p(bias), _p(out), c_long(out.stride(0)), _p(resid),
-                  c_long(resid.stride(0) if resid is not None else 0), c_long(M), c_int(N), c_int(K), c_float(p_drop), c_ulonglong(seed),
-                  c_float(out_scale), _p(ln_in[0]) if ln_in is not None else c_void_p(0), c_long(ln_in[0].stride(0) if ln_in is not None else 0),
-                  _p(ln_in[1]) if ln_in is not None else c_void_p(0), _p(ln_in[2]) if ln_in is not None else c_void_p(0),
-                  c_float(ln_in[3] if ln_in is not None else 0.0), _p(lno), _p(stats[0]) if stats is not None else c_void_p(0),
-                  _p(stats[1]) if stats is not None else c_void_p(0), c_int(dt(src)), _stream())
-    return (out, lno, stats) if ln_in is not None else out
-
-
-def lin256_bwd(dy, wtp, N, K, ln_bwd=None):
-    """dx [M, N] = dy [M, K] W (wtp = pack(W^T [N, K])).  ln_bwd = (x, gamma, stats, resid, dgamma, dbeta, drop): the LayerNorm backward of
-    the layer's input runs in the epilogue -> dx or (dx, dx2)."""
-    _need_cuda(dy, wtp)
-    M = dy.shape[0]
-    dx = torch.empty((M, N), dtype=dy.dtype, device=dy.device)
-    x = gamma = stats = resid = dx2 = part = flush = None
-    drop = None
-    if ln_bwd is not None:
-        x, gamma, stats, resid, dgamma, dbeta, drop = ln_bwd
-        if dgamma is not None:
-            part, flush = _ln_partial_register(M, N, dgamma, dbeta, dy.device)
-        if drop is not None:
-            dx2 = torch.empty((M, N), dtype=dy.dtype, device=dy.device)
-    p2, s2, g2 = drop if drop is not None else (0.0, 0, 1.0)
-    with _Timed("lin256_bwd[%d,%d%s]" % (N, K, " +ln" if ln_bwd is not None else "") if _prof_shapes and _prof is not None else None):
-        _lib.call("sarssl_lin256_bwd", _p(dy), c_long(dy.stride(0)), _p(wtp), _p(dx), c_long(dx.stride(0)), c_long(M), c_int(N), c_int(K), _p(x),
-                  c_long(x.stride(0) if x is not None else 0), _p(gamma), _p(stats[0]) if stats is not None else c_void_p(0),
-                  _p(stats[1]) if stats is not None else c_void_p(0), _p(resid), c_long(resid.stride(0) if resid is not None else 0), _p(dx2),
-                  c_float(p2), c_ulonglong(s2), c_float(g2), _p(part), c_int(dt_ga(dy, x) if x is not None else dt(dy)), _stream())
-    if flush is not None:
-        flush()
-    return (dx, dx2) if dx2 is not None else dx
-
-
 _splitk_batch = None
 
 
@@ -744,7 +676,9 @@ def istft(spec, center=False, win_len=512, hop=256, nfft=512):
     nb, nf, nt, nch, _ = sp.shape
     assert nf == nfft // 2 + 1
     nsample = (nt - 1) * hop if center else (nt + 1) * hop
-    ws = _f32ws(nb * nch * nt * nfft, spec.device, "istft")
+    fn = _lib.lib().sarssl_istft_workspace_bytes
+    fn.restype = c_long
+    ws = _f32ws(fn(c_int(nb), c_int(nch), c_int(nt)) // 4, spec.device, "istft")
     sig = torch.empty((nb, nsample, nch), dtype=torch.float32, device=spec.device)
     _lib.call("sarssl_istft", _p(sp), c_int(nb), c_int(nch), c_int(nt), c_int(win_len), c_int(hop), c_int(nfft),
               c_int(1 if center else 0), _p(ws), _p(sig), _stream())
@@ -1027,13 +961,10 @@ def stem_c4_fwd(y3, W4, scale, shift, want_stats=False):
     """-> y4 (B,T,F,4), or (y4, sums f64[8]) with the BatchNorm sums of the stored y4 accumulated in the same pass."""
     B, F, T, _ = y3.shape
     y4 = torch.empty((B, T, F, 4), dtype=y3.dtype, device=y3.device)
-    if want_stats:
-        sums = _sums(8, y3.device)
-        _lib.call("sarssl_stem_c4_fwd_stats", _p(y3), _p(W4), _p(scale), _p(shift), c_int(B), c_int(F), c_int(T), _p(y4), _p(sums),
-                  c_int(dt(y3)), _stream())
-        return y4, sums
-    _lib.call("sarssl_stem_c4_fwd", _p(y3), _p(W4), _p(scale), _p(shift), c_int(B), c_int(F), c_int(T), _p(y4), c_int(dt(y3)), _stream())
-    return y4
+    sums = _sums(8, y3.device) if want_stats else None
+    _lib.call("sarssl_stem_c4_fwd", _p(y3), _p(W4), _p(scale), _p(shift), c_int(B), c_int(F), c_int(T), _p(y4), _p(sums), c_int(dt(y3)),
+              _stream())
+    return (y4, sums) if want_stats else y4
 
 
 def stem_c4_fwd_pair(y3, W4, scale, shift, want_stats=False):
@@ -1082,7 +1013,7 @@ def stem_c4_bwd_two_phase(y3, dy4, W4, aff, train, pgrads=None):
     red = stem_c4_bwd_sums(y3, dy4, W4, aff)
     dy3 = torch.empty(y3.shape, dtype=dy4.dtype, device=y3.device)
     gw, dg, db = pgrads if pgrads is not None else (None, None, None)
-    _lib.call("sarssl_stem_c4_bwd_apply_pg", _p(y3), _p(dy4), _p(W4), _p(aff[0]), _p(aff[1]), _p(aff[2]), _p(aff[3]), c_int(B), c_int(F),
+    _lib.call("sarssl_stem_c4_bwd_apply", _p(y3), _p(dy4), _p(W4), _p(aff[0]), _p(aff[1]), _p(aff[2]), _p(aff[3]), c_int(B), c_int(F),
               c_int(T), _p(red), c_int(1 if train else 0), _p(dy3), _p(gw), _p(dg), _p(db), c_int(dt_ga(dy4, y3)), _stream())
     return dy3, red
 
@@ -1202,25 +1133,23 @@ def conv_cus_override(ncus):
     _lib.call("sarssl_ctx_set_conv_cus", c_void_p(_lib._make_current()), c_int(int(ncus)))
 
 
+def _wgrad_part(B, F, T, device):
+    nbytes = _lib.lib().sarssl_conv3x3_wgrad_workspace_bytes
+    nbytes.restype = c_long
+    return workspace(nbytes(c_int(B), c_int(F), c_int(T)), device, "wgrad_part")
+
+
 def conv3x3_wgrad_c1(dy, a0, W1, scale, shift, acc_into):
     """Weight gradient of that convolution, added into the (64,64,3,3) f32 parameter-gradient buffer; the input operand is formed from a0
     while staging."""
     _need_cuda(dy, a0, W1)
     B, F, T, _ = a0.shape
     assert a0.dtype in _16 and dy.dtype == torch.bfloat16 and acc_into.shape == (64, 64, 3, 3) and acc_into.is_contiguous()
-    nbytes = _lib.lib().sarssl_conv3x3_wgrad_workspace_bytes
-    nbytes.restype = c_long
-    part = workspace(nbytes(c_int(B), c_int(F), c_int(T)), a0.device, "wgrad_part")
+    part = _wgrad_part(B, F, T, a0.device)
     with _Timed("conv3x3_wgrad_kernel"):
         _lib.call("sarssl_conv3x3_wgrad_c1_acc", _p(dy), _p(a0), _p(W1), c_int(B), c_int(F), c_int(T), _p(scale), _p(shift), _p(acc_into),
                   _p(part), c_int(dt(a0)), _stream())
     return True
-
-
-def _wgrad_part(B, F, T, device):
-    nbytes = _lib.lib().sarssl_conv3x3_wgrad_workspace_bytes
-    nbytes.restype = c_long
-    return workspace(nbytes(c_int(B), c_int(F), c_int(T)), device, "wgrad_part")
 
 
 def conv3x3_wgrad_c4(y3, dy4, W4, aff3, train, red, y2, scale, shift, acc_into, out=None, pgrads=None):
@@ -1283,9 +1212,7 @@ def conv3x3_wgrad(dy, zin, scale=None, shift=None, precise=False, acc_into=None)
     weight gradient is added straight into it (nn.Conv2d layout) and None is returned."""
     _need_cuda(dy, zin)
     B, F, T, C = zin.shape
-    nbytes = _lib.lib().sarssl_conv3x3_wgrad_workspace_bytes
-    nbytes.restype = c_long
-    part = workspace(nbytes(c_int(B), c_int(F), c_int(T)), zin.device, "wgrad_part")
+    part = _wgrad_part(B, F, T, zin.device)
     if acc_into is not None and zin.dtype in _16:
         assert acc_into.shape == (64, 64, 3, 3) and acc_into.dtype == torch.float32 and acc_into.is_contiguous() and dy.dtype == torch.bfloat16
         with _Timed("conv3x3_wgrad_kernel"):
@@ -1356,7 +1283,7 @@ def cl_bn_bwd_apply(dz, y, C, aff, act, g_is_masked, use_stats, red, out=None, p
     if out is None:
         out = torch.empty(y.shape, dtype=dz.dtype, device=y.device)
     dg, db = pgrads if pgrads is not None else (None, None)
-    _lib.call("sarssl_cl_bn_bwd_apply_pg", _p(dz), _p(y), c_long(y.numel() // C), c_int(C), _p(aff[0]), _p(aff[1]), _p(aff[2]),
+    _lib.call("sarssl_cl_bn_bwd_apply", _p(dz), _p(y), c_long(y.numel() // C), c_int(C), _p(aff[0]), _p(aff[1]), _p(aff[2]),
               _p(aff[3]), c_int(act), c_int(1 if g_is_masked else 0), c_int(1 if use_stats else 0), _p(red), _p(out), _p(dg), _p(db),
               c_int(dt_ga(dz, y)), _stream())
     return out
@@ -1443,18 +1370,13 @@ def layernorm_bwd(dy2d, x2d, gamma, stats, resid=None, dgamma=None, dbeta=None, 
             dgamma = dbeta = None
         else:
             part = workspace(fn(c_long(M), c_int(d)), x2d.device, "ln_part")
-    if drop is not None:
-        p, seed, gscale = drop
-        out2 = torch.empty((M, d), dtype=dy2d.dtype, device=x2d.device)
-        _lib.call("sarssl_layernorm_bwd_drop", _p(dy2d), c_long(dy2d.stride(0)), _p(x2d), c_long(x2d.stride(0)), c_long(M), c_int(d),
-                  _p(gamma), _p(stats[0]), _p(stats[1]), _p(resid), c_long(resid.stride(0) if resid is not None else 0), _p(out),
-                  c_long(out.stride(0)), _p(dgamma), _p(dbeta), _p(part), _p(out2), c_float(p), c_ulonglong(seed), c_float(gscale),
-                  c_int(dt_ga(dy2d, x2d)), _stream())
-        return out, out2
+    p, seed, gscale = drop if drop is not None else (0.0, 0, 1.0)
+    out2 = torch.empty((M, d), dtype=dy2d.dtype, device=x2d.device) if drop is not None else None
     _lib.call("sarssl_layernorm_bwd", _p(dy2d), c_long(dy2d.stride(0)), _p(x2d), c_long(x2d.stride(0)), c_long(M), c_int(d),
               _p(gamma), _p(stats[0]), _p(stats[1]), _p(resid), c_long(resid.stride(0) if resid is not None else 0), _p(out),
-              c_long(out.stride(0)), _p(dgamma), _p(dbeta), _p(part), c_int(dt_ga(dy2d, x2d)), _stream())
-    return out
+              c_long(out.stride(0)), _p(dgamma), _p(dbeta), _p(part), _p(out2), c_float(p), c_ulonglong(seed), c_float(gscale),
+              c_int(dt_ga(dy2d, x2d)), _stream())
+    return (out, out2) if drop is not None else out
 
 
 def glu_fwd(h):
@@ -1808,21 +1730,12 @@ def masked_mse_fwd(pred, x, idx_i32, mch_i32, sink=None, with_grad=False):
     nm = idx_i32.shape[1]
     sums = _sums(128, x.device)
     out = torch.empty((2,), dtype=torch.float32, device=x.device)
-    if with_grad:
-        dpred = torch.empty(pred.shape, dtype=gdtype_of(pred.dtype), device=pred.device)
-        keep, acc = sink if sink is not None else (None, None)
-        _lib.call("sarssl_masked_mse_fwd_bwd", _p(pred), _p(x), _p(idx_i32), _p(mch_i32), c_int(B), c_int(F), c_int(T), c_int(nm),
-                  _p(sums), _p(out), _p(keep), _p(acc), _p(dpred), c_int(dt_ga(dpred, pred)), _stream())
-        return out, dpred
-    if sink is not None:
-        keep, acc = sink
-        assert keep.dtype == torch.float32 and acc.dtype == torch.float64 and keep.numel() == 2 and acc.numel() == 2
-        _lib.call("sarssl_masked_mse_fwd_acc", _p(pred), _p(x), _p(idx_i32), _p(mch_i32), c_int(B), c_int(F), c_int(T), c_int(nm),
-                  _p(sums), _p(out), _p(keep), _p(acc), c_int(dt(pred)), _stream())
-        return out
-    _lib.call("sarssl_masked_mse_fwd", _p(pred), _p(x), _p(idx_i32), _p(mch_i32), c_int(B), c_int(F), c_int(T), c_int(nm), _p(sums),
-              _p(out), c_int(dt(pred)), _stream())
-    return out
+    keep, acc = sink if sink is not None else (None, None)
+    assert (keep is None or (keep.dtype == torch.float32 and keep.numel() == 2)) and (acc is None or (acc.dtype == torch.float64 and acc.numel() == 2))
+    dpred = torch.empty(pred.shape, dtype=gdtype_of(pred.dtype), device=pred.device) if with_grad else None
+    _lib.call("sarssl_masked_mse_fwd", _p(pred), _p(x), _p(idx_i32), _p(mch_i32), c_int(B), c_int(F), c_int(T), c_int(nm), _p(sums), _p(out),
+              _p(keep), _p(acc), _p(dpred), c_int(dt_ga(dpred, pred) if with_grad else dt(pred)), _stream())
+    return (out, dpred) if with_grad else out
 
 
 def regress_loss(pred, target, sink=None, with_grad=False, skip_nonfinite=True):
@@ -1905,16 +1818,12 @@ def masked_mse_bwd(pred, x, mp_u8, mch_i32, nm, gscale=1.0, gscale_dev=None):
 
 
 def adam_step(p, g, m, v, p16, lr, step, gscale=1.0, betas=(0.9, 0.999), eps=1e-8, ph16=None, guard=None, nskipped=None, pl16=None):
-    """p16 / ph16: bf16 / fp16 shadow copies of the parameters rewritten by the same pass (either may be None).  guard: f32 device
+    """p16 / ph16 / pl16: bf16 / fp16 / fp16-lo shadow copies of the parameters rewritten by the same pass (each may be None).  guard: f32 device
     tensor holding the step's loss - not finite -> the update is skipped on the device (nskipped: int32 device counter, += 1)."""
     assert (p16 is None or p16.dtype == torch.bfloat16) and (ph16 is None or ph16.dtype == torch.float16)
     assert guard is None or (guard.dtype == torch.float32 and guard.is_cuda)
-    if pl16 is not None:              # hybrid mode: the lo shadow (fp16(p - fp16(p))) in the same pass
-        assert pl16.dtype == torch.float16
-        _lib.call("sarssl_adam_step_guard_lo", _p(p), _p(g), _p(m), _p(v), _p(p16), _p(ph16), _p(pl16), c_long(p.numel()), c_float(gscale), c_float(lr),
-                  c_float(betas[0]), c_float(betas[1]), c_float(eps), c_int(step), _p(guard), _p(nskipped), _stream())
-        return
-    _lib.call("sarssl_adam_step_guard", _p(p), _p(g), _p(m), _p(v), _p(p16), _p(ph16), c_long(p.numel()), c_float(gscale), c_float(lr),
+    assert pl16 is None or pl16.dtype == torch.float16      # hybrid mode: the lo shadow (fp16(p - fp16(p))) in the same pass
+    _lib.call("sarssl_adam_step", _p(p), _p(g), _p(m), _p(v), _p(p16), _p(ph16), _p(pl16), c_long(p.numel()), c_float(gscale), c_float(lr),
               c_float(betas[0]), c_float(betas[1]), c_float(eps), c_int(step), _p(guard), _p(nskipped), _stream())
 
 
@@ -1991,13 +1900,9 @@ def step_tick(st):
 def adam_step_dev(p, g, m, v, p16, st, gscale=1.0, eps=1e-8, zero_grad=False, ph16=None, guard=None, pl16=None):
     assert (p16 is None or p16.dtype == torch.bfloat16) and (ph16 is None or ph16.dtype == torch.float16)
     assert guard is None or (guard.dtype == torch.float32 and guard.is_cuda)
-    if pl16 is not None:
-        assert pl16.dtype == torch.float16
-        _lib.call("sarssl_adam_step_dev_guard_lo", _p(p), _p(g), _p(m), _p(v), _p(p16), _p(ph16), _p(pl16), c_long(p.numel()), c_float(gscale), _p(st),
-                  c_float(eps), c_int(1 if zero_grad else 0), _p(guard), _stream())
-        return
-    _lib.call("sarssl_adam_step_dev_guard", _p(p), _p(g), _p(m), _p(v), _p(p16), _p(ph16), c_long(p.numel()), c_float(gscale), _p(st), c_float(eps),
-              c_int(1 if zero_grad else 0), _p(guard), _stream())
+    assert pl16 is None or pl16.dtype == torch.float16
+    _lib.call("sarssl_adam_step_dev", _p(p), _p(g), _p(m), _p(v), _p(p16), _p(ph16), _p(pl16), c_long(p.numel()), c_float(gscale), _p(st),
+              c_float(eps), c_int(1 if zero_grad else 0), _p(guard), _stream())
 
 
 def fp16_overflow(clear=True, device=None):

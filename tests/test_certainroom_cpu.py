@@ -241,7 +241,7 @@ def test_the_library_exports_the_mixing_table_and_the_header_binds_it():
     from sar_ssl_amd import _lib, hip
     if not os.path.exists(_lib.LIB_PATH):
         g.build()
-    assert hasattr(_lib.lib(), "sarssl_mixing_table") and _lib.lib().sarssl_abi_version() == 2
+    assert hasattr(_lib.lib(), "sarssl_mixing_table") and _lib.lib().sarssl_abi_version() == 3
     hdr = open(os.path.join(ROOT, "include", "sarssl_hip.h")).read()
     m = re.search(r"\bint\s+sarssl_mixing_table\s*\(([^()]*)\)\s*;", hdr)
     assert m is not None

@@ -141,3 +141,30 @@ def test_adam_entry_points_vs_f64_torch_adam(entry, n):
     if with_lo and n >= 255:                         # the lo shadows do reach fp16's subnormal range (and were not flushed)
         lo = pl16.float().abs()
         assert bool(((lo > 0) & (lo < 2.0 ** -14)).any())
+
+
+@pytest.mark.parametrize("with_lo", [False, True])
+def test_adam_step_dev_without_a_guard_is_the_step_behind_a_finite_guard(with_lo):
+    """sarssl_adam_step_dev with guard = NULL (a caller that never skips) against the same launch behind a finite guard, which the test
+    above pins: parameters, moments, shadows and the cleared gradient bit for bit; n = 1000 leaves a partial workgroup."""
+    from sar_ssl_amd import hip
+    dev = torch.device("cuda:0")
+    n = 1000
+    gen = torch.Generator().manual_seed(77)
+    p0 = torch.randn(n, generator=gen)
+    g0 = torch.randn(n, generator=gen) * 1e-2
+    results = []
+    for guard in (torch.ones(1, device=dev), None):
+        p, g = p0.to(dev), g0.to(dev)
+        m, v = torch.full((n,), 1e-3, device=dev), torch.full((n,), 1e-6, device=dev)
+        p16 = torch.zeros(n, dtype=torch.bfloat16, device=dev)
+        ph16 = torch.zeros(n, dtype=torch.float16, device=dev)
+        pl16 = torch.zeros(n, dtype=torch.float16, device=dev) if with_lo else None
+        st = hip.step_state_new(dev, 0x1234, LR0, BETAS)
+        hip.step_tick(st)
+        hip.adam_step_dev(p, g, m, v, p16, st, gscale=GSCALE, eps=EPS, zero_grad=True, ph16=ph16, guard=guard, pl16=pl16)
+        torch.cuda.synchronize()
+        assert hip.step_state_skipped(st) == 0 and bool((g == 0).all()) and not torch.equal(p.cpu(), p0)
+        _shadows_ok(p, p16, ph16, pl16)
+        results.append((p, m, v, p16, ph16) + ((pl16,) if with_lo else ()))
+    assert all(torch.equal(a, b) for a, b in zip(*results))

@@ -140,7 +140,7 @@ def test_layernorm_bwd_beyond_the_workgroup_cap():
 @pytest.mark.parametrize("M,d", [(7, 32), (70, 768)])
 @pytest.mark.parametrize("pair", PAIRS[2:], ids=_ids)
 def test_layernorm_bwd_drop_in_the_mixed_pairings(pair, M, d):
-    """sarssl_layernorm_bwd_drop in MIX16 and MIXF32: the first output is the plain call's bit for bit, the second has the keep mask of
+    """sarssl_layernorm_bwd with dx2 in MIX16 and MIXF32: the first output is the plain call's bit for bit, the second has the keep mask of
     act_bwd(first, None, 0, p, seed, gscale) and its values within one bf16 rounding (rounded once from the f32 gradient, not twice)."""
     hip, dev = _hip(), _dev()
     name, gt, at = pair
@@ -159,6 +159,25 @@ def test_layernorm_bwd_drop_in_the_mixed_pairings(pair, M, d):
         assert 0.2 < float((out2 == 0).float().mean()) < 0.3
     # one bf16 rounding: a unit in the last place is at most 2^-7 of the value
     assert bool(((out2.double() - want.double()).abs() <= 2.0 ** -7 * want.double().abs()).all())
+
+
+def test_layernorm_bwd_with_dropout_output_is_refused_past_1024_columns():
+    """d > 1024 runs the one-workgroup-per-row kernel, which has no second output: hip.layernorm_bwd(..., drop=...) is refused on the host
+    (nothing is launched, dx stays as it was), the plain call at the same shape goes through."""
+    from sar_ssl_amd._lib import SarsslHipError
+    hip, dev = _hip(), _dev()
+    M, d = 4, 1536
+    g = _gen(9)
+    x, dy = torch.randn((M, d), generator=g).to(dev), torch.randn((M, d), generator=g).to(dev)
+    gamma, beta = (torch.rand(d, generator=g) + 0.5).to(dev), torch.zeros(d, device=dev)
+    _, stats = hip.layernorm_fwd(x, gamma, beta, 1e-5)
+    out = torch.full((M, d), 7.0, device=dev)
+    with pytest.raises(SarsslHipError, match="d <= 1024"):
+        hip.layernorm_bwd(dy, x, gamma, stats, out=out, drop=(0.25, 3, 1.0))
+    torch.cuda.synchronize()
+    assert bool((out == 7.0).all())
+    hip.layernorm_bwd(dy, x, gamma, stats, out=out)
+    assert bool(torch.isfinite(out).all()) and not bool((out == 7.0).any())
 
 
 # ================================================================================================ b. convolution-module row kernels

@@ -24,11 +24,29 @@ def test_cabi_library_exports_every_declared_symbol():
     assert len(names) >= 35
     for n in names:
         assert hasattr(lib, n), "missing export: " + n
-    assert lib.sarssl_abi_version() == 2
+    assert lib.sarssl_abi_version() == 3
     # collectives: RCCL is resolved with dlopen at first use - the answer needs no GPU, and the library loaded without librccl linked in
     assert lib.sarssl_comm_available() in (0, 1)
     if lib.sarssl_comm_available():
         assert lib.sarssl_comm_rccl_version() > 20000
+
+
+def test_cabi_library_exports_nothing_but_the_declared_symbols():
+    """The other direction of the test above: every dynamic symbol of the library that starts with sarssl_ is declared in the header (the
+    three stamp buffers of a probe build excepted), so a retired entry point cannot stay behind as an export."""
+    import shutil
+    import subprocess
+    from sar_ssl_amd import _lib
+    if not os.path.exists(_lib.LIB_PATH):
+        pytest.skip("libsarssl_hip.so is not built")
+    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
+    nm = shutil.which("nm") or shutil.which("llvm-nm") or shutil.which("llvm-nm", path=os.path.join(rocm, "llvm", "bin"))
+    assert nm is not None, "neither nm nor ROCm's llvm-nm found"
+    out = subprocess.run([nm, "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    exported = {ln.split()[-1] for ln in out.splitlines() if ln.split() and ln.split()[-1].startswith("sarssl_")}
+    declared = set(_header_prototypes())
+    probe = {"sarssl_conv_stamp_buffer", "sarssl_gemm_stamp_buffer", "sarssl_ffn_stamp_buffer"}
+    assert len(declared) >= 148 and exported - probe == declared, (sorted(exported - probe - declared), sorted(declared - exported))
 
 
 _C_SCALARS = ("int", "long", "float", "double", "unsigned long long", "unsigned int")
@@ -173,17 +191,24 @@ def _check_abi_file(path, source, protos, probe, at_load=()):
     return sum(1 for s in sites if s[0] in seen), nkinds, seen
 
 
+def _check_every_entry_point_is_called(protos, called):
+    """Every entry point the header declares has a call site: an export nobody calls is a signature nothing checks and a body nothing
+    runs (forwarding shims of older names piled up that way)."""
+    idle = sorted(set(protos) - set(called))
+    assert not idle, "declared in include/sarssl_hip.h without a call site: " + ", ".join(idle)
+
+
 def test_cabi_call_sites_agree_with_the_header():
     """The call sites wrap every argument by hand (c_int / c_long / c_float / c_ulonglong / pointers) and ctypes checks none of it: a
     c_int where the header says long, a dropped or swapped argument, a byte count read without ``restype = c_long`` would show on the GPU
     only.  This walks both ways into the library - `call("sarssl_...", ...)` with a literal name, and the attribute-style calls on the
     CDLL (`lib().sarssl_x(...)`, also through a local `fn = lib().sarssl_x`) - in the package, the tools and the drivers, and compares
     argument count, wrapper kinds and the assigned return types with the header's prototypes (probe-build symbols, which the header does
-    not declare, take one pointer)."""
+    not declare, take one pointer).  The other way round, every declared entry point has a call site in those files or in the tests."""
     import glob
     protos = _header_prototypes()
     hdr = open(os.path.join(ROOT, "include", "sarssl_hip.h")).read()
-    assert sorted(protos) == sorted(set(re.findall(r"\b(sarssl_[a-z0-9_]+)\s*\(", hdr))) and len(protos) >= 150
+    assert sorted(protos) == sorted(set(re.findall(r"\b(sarssl_[a-z0-9_]+)\s*\(", hdr))) and len(protos) >= 148
     assert {"sarssl_istft_workspace_bytes", "sarssl_wall_clock_khz", "sarssl_conv3x3_wgrad_workspace_bytes", "sarssl_dwglu_wgrad_workspace_bytes",
             "sarssl_layernorm_bwd_workspace_bytes", "sarssl_dwconv_wgrad_workspace_bytes",
             "sarssl_step_state_bytes"} <= {n for n, (r, _) in protos.items() if r == "long"}
@@ -201,13 +226,20 @@ def test_cabi_call_sites_agree_with_the_header():
         n, k, names = _check_abi_file(rel, open(path).read(), protos, probe, at_load)
         per_file[rel] = n
         nsites, nkinds, seen = nsites + n, nkinds + k, seen | names
-    # the scan really finds the sites: 129 literal call(...) sites and 37 attribute-style ones today, 1528 wrapped arguments
-    assert nsites >= 160 and len(seen) >= 125 and nkinds >= 1450, (nsites, len(seen), nkinds)
+    # the scan really finds the sites: 148 prototypes; 129 literal call(...) sites and 39 attribute-style ones today, 149 names called
+    # (146 entry points and the three probe-build symbols), 1505 wrapped arguments
+    assert nsites >= 162 and len(seen) >= 133 and nkinds >= 1427, (nsites, len(seen), nkinds)
     hip = os.path.join("sar-ssl_amd", "hip.py")
     direct = [s for s in _abi_sites(open(os.path.join(ROOT, hip)).read())[0] if s[4]]
     assert len(direct) >= 25 and {"sarssl_gemm_group_tn", "sarssl_layernorm_bwd_workspace_bytes", "sarssl_conv3x3_wgrad_workspace_bytes",
                                   "sarssl_colsum_slices", "sarssl_comm_create", "sarssl_step_state_skipped"} <= {s[0] for s in direct}
     assert per_file[os.path.join("sar-ssl_amd", "_lib.py")] >= 5 and per_file["__graft_entry__.py"] >= 1 and per_file["bench.py"] >= 1
+    # the other direction: the tests count as callers (they read sarssl_ctx_device / sarssl_ctx_get_conv_cus), their arguments are not checked
+    in_tests = set()
+    for path in glob.glob(os.path.join(ROOT, "tests", "**", "*.py"), recursive=True):
+        in_tests |= {s[0] for s in _abi_sites(open(path).read(), path)[0]}
+    assert {"sarssl_ctx_device", "sarssl_ctx_get_conv_cus"} <= in_tests - seen
+    _check_every_entry_point_is_called(protos, seen | in_tests)
 
 
 def test_cabi_call_site_scan_catches_what_it_is_for(tmp_path):
@@ -239,6 +271,12 @@ def test_cabi_call_site_scan_catches_what_it_is_for(tmp_path):
     with pytest.raises(AssertionError, match="returns long"):
         _check_abi_file("bad.py", ok.replace("    fn.restype = c_long\n", "") + "def g():\n    _lib.lib().sarssl_layernorm_bwd_workspace_bytes.restype = c_long\n",
                         protos, {})
+    # a declared entry point nobody calls
+    two = _header_prototypes("int sarssl_glu_fwd(const void* h, long M, int d, void* g, int dtype, void* stream);\nint sarssl_idle(int a);\n")
+    called = _check_abi_file("ok.py", ok, protos, {})[2]
+    _check_every_entry_point_is_called({"sarssl_glu_fwd": two["sarssl_glu_fwd"]}, called)
+    with pytest.raises(AssertionError, match="without a call site: sarssl_idle\\n"):
+        _check_every_entry_point_is_called(two, called)
     # the header reader names what it cannot read
     for text, what in (("int sarssl_x(int a, size_t n);", "unknown type `size_t n`"), ("void sarssl_x(int a);", "unknown type `void`"),
                        ("int sarssl_x(int (*cb)(int));", "unreadable declaration")):
