@@ -69,9 +69,10 @@ def test_gemm_layouts(a_kc, b_kc, mode, M, N, K):
 @pytest.mark.parametrize("a_kc,b_kc", LAYOUTS)
 @pytest.mark.parametrize("M,N,K,nbatch", [(4096, 1024, 256, 1), (512, 256, 768, 128), (520, 264, 776, 60)])
 def test_gemm_large_tiles_all_epilogues(a_kc, b_kc, M, N, K, nbatch):
-    """Grids large enough for the 256 x 128-tile instantiations (plain and ragged-edge): batched product with bias, Swish,
-    pre-activation side output, dropout, output scale and residual, in bf16 against an f64 reference of the same bf16 operands;
-    and the split-K accumulate path with f32 output."""
+    """Large grids with every epilogue term at once: batched product with bias, Swish, pre-activation side output, dropout, output scale
+    and residual, in bf16 against an f64 reference of the same bf16 operands; and the split-K accumulate path with f32 output.  Which
+    tile height the dispatcher picks for these shapes is not asserted here (an earlier version of this text named the 256 x 128 tile,
+    which needs a longer K than any of them has); tests/test_gpu_gemm.py holds the shapes aimed at each tile height."""
     from sar_ssl_amd import hip
     dev = _dev()
     A = _mk((nbatch, M, K) if a_kc else (nbatch, K, M), torch.bfloat16, dev, 11)
