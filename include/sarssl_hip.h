@@ -44,6 +44,7 @@ int sarssl_ctx_set_conv_cus(sarssl_ctx* ctx, int ncus);       /* 3x3 data / weig
  * the step.  sarssl_ctx_fp16_overflow reads (and optionally clears) the word from the host; synchronises `stream`. */
 int sarssl_ctx_fp16_overflow(sarssl_ctx* ctx, int clear, void* stream);
 int sarssl_ctx_get_conv_cus(const sarssl_ctx* ctx);
+int sarssl_ctx_set_pair_kdepth(sarssl_ctx* ctx, int depth);   /* K-tile depth of sarssl_gemm_split's pair products: 32 | 64, 0 = the launcher's rule; same bits at either depth */
 int sarssl_ctx_set_clock_probe(sarssl_ctx* ctx, void* buf);   /* see the measurement aid below; NULL = off */
 int sarssl_ctx_attach_step_state(sarssl_ctx* ctx, void* state);   /* device SarsslStepState* or NULL: dropout launches add its salt */
 int sarssl_ctx_zero_arena(sarssl_ctx* ctx, const void* base, long bytes);   /* accumulators inside [base, base+bytes) are already zero */

@@ -158,6 +158,13 @@ extern "C" int sarssl_ctx_set_conv_cus(sarssl_ctx* ctx, int ncus) {
     return 0;
 }
 extern "C" int sarssl_ctx_get_conv_cus(const sarssl_ctx* ctx) { return ctx ? ctx->conv_cus_bwd : 0; }
+// K-tile depth of the pair products (sarssl_gemm_split with lo parts) issued under ctx: 32 | 64; 0 = the launcher's rule.  Both depths
+// give the same bits (csrc/gemm.hip gemm_body): the knob exists for tests and A/B timing
+extern "C" int sarssl_ctx_set_pair_kdepth(sarssl_ctx* ctx, int depth) {
+    SARSSL_REQUIRE(ctx != nullptr && (depth == 0 || depth == 32 || depth == 64), "sarssl_ctx_set_pair_kdepth");
+    ctx->pair_kdepth = depth;
+    return 0;
+}
 // clock-probe buffer (device memory, 5 slots x 4 u64) of the 3x3 forward / data-gradient launches issued under ctx; null = off
 extern "C" int sarssl_ctx_set_clock_probe(sarssl_ctx* ctx, void* buf) {
     SARSSL_REQUIRE(ctx != nullptr, "sarssl_ctx_set_clock_probe");

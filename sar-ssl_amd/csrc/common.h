@@ -29,6 +29,7 @@ int sarssl_cu_count();          // CUs of the current device (api.hip): grid siz
 struct sarssl_ctx {
     int device;
     int conv_cus_bwd;                       // workgroups of the 3x3 gradient launches (0: the default 7/8 rule)
+    int pair_kdepth;                        // K-tile depth of the pair products, 32 | 64 (0: the launcher's rule, csrc/gemm.hip launch_seg)
     unsigned long long* conv_clk;           // clock-probe buffer of the 3x3 forward / data-gradient launches, or null
     const unsigned long long* salt;         // dropout-seed addend: &SarsslStepState::salt of the attached step state, or null
     const char* zero_lo; const char* zero_hi;   // host-zeroed accumulator arena: memsets of pointers inside it are skipped

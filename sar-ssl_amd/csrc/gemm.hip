@@ -44,30 +44,59 @@ __device__ __forceinline__ uint4 load_chunk(const T* __restrict__ p, int part) {
     else { const f8 v = ld8(p); return pack8_part(v, part); }
 }
 
-// Register-staged operand tile: ROWS x 64 elements, 16-byte chunks, NCH = ROWS / 32 chunks per thread.
-//   KC  ([row][k] in memory):  chunk i of thread t = row (t >> 3) + 32 i, k-chunk t & 7
+// Row of thread t's chunk 0 in a K-contiguous tile of depth KB (KB / 8 chunks per row, 2048 / KB rows per pass of the 256 threads).
+// Depth 64: t >> 3.  Depth 32 (pitch 40 elements = 20 banks): rows r and r + 4 of a group of eight go to the two halves of an 8-lane
+// ds_write_b128 group - 16 + 16 banks that tile all 32 (neighbouring rows would overlap in 4 of them)
+template <int KB> __device__ __forceinline__ int krow(int t) {
+    if constexpr (KB == 64) return t >> 3;
+    else { const int q = t >> 2; return (q & ~7) | ((q & 1) << 2) | ((q >> 1) & 3); }
+}
+// Register-staged operand tile: ROWS x KB elements (KB = 64; 32: the shallow K-tile of the pair products), 16-byte chunks, NCH = ROWS KB / 2048
+// chunks per thread.
+//   KC  ([row][k] in memory):  chunk i of thread t = row krow(t) + (2048 / KB) i, k-chunk t & (KB / 8 - 1)
 //   !KC ([k][row] in memory):  CPR = ROWS / 8 chunks per k-row; chunk i of thread t = k (t / CPR) + i * (256 / CPR), row-chunk t % CPR
 // `p` points at this thread's chunk 0 of the current K-tile; EDGE instantiations zero-fill rows >= R and k >= Kend.
-template <typename T, typename TM, bool KC, int ROWS, bool EDGE>
+template <typename T, typename TM, bool KC, int ROWS, bool EDGE, int KB = BK>
 __device__ __forceinline__ void tile_load(const T* __restrict__ p, long ld, int r0, int k0, int R, int Kend, int part, int tid,
-                                          uint4 (&regs)[ROWS / 32]) {
-    constexpr int CPR = ROWS / 8, KPP = 256 / CPR;
+                                          uint4 (&regs)[ROWS * KB / 2048]) {
+    constexpr int CPR = ROWS / 8, KPP = 256 / CPR, RPP = 2048 / KB;
 #pragma unroll
-    for (int i = 0; i < ROWS / 32; ++i) {
-        const T* q = KC ? p + (long)(32 * i) * ld : p + (long)(KPP * i) * ld;
+    for (int i = 0; i < ROWS * KB / 2048; ++i) {
+        const T* q = KC ? p + (long)(RPP * i) * ld : p + (long)(KPP * i) * ld;
         if constexpr (EDGE) {
-            const int gr = KC ? r0 + (tid >> 3) + 32 * i : r0 + (tid % CPR) * 8;
-            const int gk = KC ? k0 + (tid & 7) * 8 : k0 + tid / CPR + KPP * i;
+            const int gr = KC ? r0 + krow<KB>(tid) + RPP * i : r0 + (tid % CPR) * 8;
+            const int gk = KC ? k0 + (tid & (KB / 8 - 1)) * 8 : k0 + tid / CPR + KPP * i;
             regs[i] = (gr < R && gk < Kend) ? load_chunk<T, TM>(q, part) : make_uint4(0, 0, 0, 0);
         } else regs[i] = load_chunk<T, TM>(q, part);
     }
 }
-template <bool KC, int ROWS>
-__device__ __forceinline__ void tile_store(uint16_t* __restrict__ s, int tid, const uint4 (&regs)[ROWS / 32]) {
-    constexpr int CPR = ROWS / 8, KPP = 256 / CPR, PT = ROWS + 32;
+// The K-contiguous 16-bit tile again, addressed as uniform base + 32-bit lane offset `voff` (bytes): the shallow pair-product tiles
+template <int ROWS, bool EDGE, int KB>
+__device__ __forceinline__ void tile_load_u(const char* __restrict__ base, uint32_t voff, long ld, int r0, int k0, int R, int Kend, int tid,
+                                            uint4 (&regs)[ROWS * KB / 2048]) {
+    constexpr int RPP = 2048 / KB;
 #pragma unroll
-    for (int i = 0; i < ROWS / 32; ++i) {
-        if (KC) *(uint4*)&s[((tid >> 3) + 32 * i) * PITCH + (tid & 7) * 8] = regs[i];
+    for (int i = 0; i < ROWS * KB / 2048; ++i) {
+        // (the row-pass base is made opaque as a scalar pair: left to itself hipcc folds it into a 64-bit per-lane address again)
+        const uint64_t bi = (uint64_t)(base + (long)(RPP * i) * ld * 2);
+        const char* sb = (const char*)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(bi >> 32)) << 32) |
+                                       (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)bi));
+        typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+        typedef const __attribute__((address_space(1))) u32x4* gptr;        // (global, not flat: the integer round trip loses the address space)
+        u32x4 v = {0u, 0u, 0u, 0u};
+        if constexpr (EDGE) {
+            const int gr = r0 + krow<KB>(tid) + RPP * i, gk = k0 + (tid & (KB / 8 - 1)) * 8;
+            if (gr < R && gk < Kend) v = *(gptr)(sb + voff);
+        } else v = *(gptr)(sb + voff);
+        regs[i] = make_uint4(v.x, v.y, v.z, v.w);
+    }
+}
+template <bool KC, int ROWS, int KB = BK>
+__device__ __forceinline__ void tile_store(uint16_t* __restrict__ s, int tid, const uint4 (&regs)[ROWS * KB / 2048]) {
+    constexpr int CPR = ROWS / 8, KPP = 256 / CPR, PT = ROWS + 32, RPP = 2048 / KB;
+#pragma unroll
+    for (int i = 0; i < ROWS * KB / 2048; ++i) {
+        if (KC) *(uint4*)&s[(krow<KB>(tid) + RPP * i) * (KB + 8) + (tid & (KB / 8 - 1)) * 8] = regs[i];
         else *(uint4*)&s[(tid / CPR + KPP * i) * PT + (tid % CPR) * 8] = regs[i];
     }
 }
@@ -88,16 +117,21 @@ __device__ __forceinline__ bf16x8 frag_tr(const uint16_t* s, int kbase, int r0, 
 
 // NSEG (sarssl_gemm_split; NT layout, fp16 operands): 2 = A B^T + A B2^T, 3 = A B^T + A2 B^T + A B2^T - the lo tiles (A2, B2) are staged
 // next to the hi tiles and every fragment read feeds two MFMAs (fp16 pairs of an f32 activation / weight: hi hi + lo hi + hi lo)
-template <typename TA, typename TB, typename TC, bool AKC, bool BKC, int FM, bool EDGE, bool CSUM = false, int NSEG = 0>
+// KB (pair products only): K-tile depth, 64 | 32.  The shallow tile halves the LDS stage and the register-staged prefetch, which is what
+// lets three workgroups share a CU (NOTES.md 20); a k-step is 16 wide at either depth and its products keep their order, so every
+// accumulator sees the same sequence of terms and the two depths agree bit for bit.
+template <typename TA, typename TB, typename TC, bool AKC, bool BKC, int FM, bool EDGE, bool CSUM = false, int NSEG = 0, int KB = BK>
 __device__ __forceinline__ void gemm_body(const GemmArgs& g, const int bid_x, const int bid_y, const int bid_z, const int grid_x,
                                           const int grid_y, const int grid_z) {
     typedef typename MfmaT<TA, TB>::type TM;
     static_assert(sizeof(TA) == 2 || (sizeof(TA) == 4 && sizeof(TB) == 4), "f32 operands come in pairs (split-bf16 passes)");
     static_assert(NSEG == 0 || ((NSEG == 2 || NSEG == 3) && AKC && BKC && sizeof(TA) == 2 && sizeof(TB) == 2 && FM <= 2), "pair products: NT layout, 16-bit operands");
+    static_assert(KB == BK || (KB == 32 && NSEG >= 2), "the shallow K-tile exists for the pair products only");
     constexpr int BM = 64 * FM;
     constexpr int PTA = BM + 32, PTB = BN + 32;
-    constexpr int A_ELEMS = AKC ? BM * PITCH : BK * PTA;
-    constexpr int B_ELEMS = BKC ? BN * PITCH : BK * PTB;
+    constexpr int PK = KB + 8;                                  // [row][k] pitch: 144 bytes at depth 64, 80 at depth 32 (both conflict-free ds_read_b128)
+    constexpr int A_ELEMS = AKC ? BM * PK : BK * PTA;
+    constexpr int B_ELEMS = BKC ? BN * PK : BK * PTB;
     constexpr int STAGE = A_ELEMS + B_ELEMS + (NSEG >= 2 ? B_ELEMS : 0) + (NSEG == 3 ? A_ELEMS : 0);
     constexpr int PC = BN + 4;                                  // f32 staging pitch of the epilogue (conflict-free 16-byte LDS writes)
     constexpr int EPI_ELEMS = 64 * PC * 2;                      // 64 x 132 f32, in 16-bit units
@@ -140,10 +174,10 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& g, const int bid_x, co
     // this thread's chunk 0 of the first K-tile; advanced by a constant per K-tile
     constexpr int CPRA = BM / 8, CPRB = BN / 8;
     const TA* pa = (const TA*)g.A + z0 * g.sA0 + z1 * g.sA1 +
-                   (AKC ? (long)(m0 + (tid >> 3)) * g.lda + k_begin + (tid & 7) * 8 : (long)(k_begin + tid / CPRA) * g.lda + m0 + (tid % CPRA) * 8);
+                   (AKC ? (long)(m0 + krow<KB>(tid)) * g.lda + k_begin + (tid & (KB / 8 - 1)) * 8 : (long)(k_begin + tid / CPRA) * g.lda + m0 + (tid % CPRA) * 8);
     const TB* pb = (const TB*)g.B + z0 * g.sB0 + z1 * g.sB1 +
-                   (BKC ? (long)(n0 + (tid >> 3)) * g.ldb + k_begin + (tid & 7) * 8 : (long)(k_begin + tid / CPRB) * g.ldb + n0 + (tid % CPRB) * 8);
-    const long stepA = AKC ? BK : (long)BK * g.lda, stepB = BKC ? BK : (long)BK * g.ldb;
+                   (BKC ? (long)(n0 + krow<KB>(tid)) * g.ldb + k_begin + (tid & (KB / 8 - 1)) * 8 : (long)(k_begin + tid / CPRB) * g.ldb + n0 + (tid % CPRB) * 8);
+    const long stepA = AKC ? KB : (long)BK * g.lda, stepB = BKC ? KB : (long)BK * g.ldb;
 
     f32x16 acc[FM][2];
 #pragma unroll
@@ -170,14 +204,18 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& g, const int bid_x, co
     // epilogue operands that do not depend on the accumulators are requested early: a thread keeps the same 8 output columns in
     // every epilogue slice, so its 8 bias values are loaded here, behind the whole K loop
     const int ch = tid & 15, n = n0 + ch * 8;
+    // (the shallow-tile pair products load them behind the K loop instead: eight registers the 168-register cap does not have)
     float bias8[8];
-    if (g.bias && (!EDGE || n + 8 <= g.N)) {
-        const float4 b0 = *(const float4*)(g.bias + n), b1 = *(const float4*)(g.bias + n + 4);
-        bias8[0] = b0.x; bias8[1] = b0.y; bias8[2] = b0.z; bias8[3] = b0.w; bias8[4] = b1.x; bias8[5] = b1.y; bias8[6] = b1.z; bias8[7] = b1.w;
-    } else {
+    auto load_bias = [&]() {
+        if (g.bias && (!EDGE || n + 8 <= g.N)) {
+            const float4 b0 = *(const float4*)(g.bias + n), b1 = *(const float4*)(g.bias + n + 4);
+            bias8[0] = b0.x; bias8[1] = b0.y; bias8[2] = b0.z; bias8[3] = b0.w; bias8[4] = b1.x; bias8[5] = b1.y; bias8[6] = b1.z; bias8[7] = b1.w;
+        } else {
 #pragma unroll
-        for (int e = 0; e < 8; ++e) bias8[e] = (g.bias && n + e < g.N) ? g.bias[n + e] : 0.f;
-    }
+            for (int e = 0; e < 8; ++e) bias8[e] = (g.bias && n + e < g.N) ? g.bias[n + e] : 0.f;
+        }
+    };
+    if constexpr (KB == BK) load_bias();
 
     // MFMA phase of one K-tile, software-pipelined by hand: the fragments of k-step kk+1 are read from LDS BEFORE the MFMAs of step kk
     // are issued (two register sets).  Left alone, hipcc sinks every ds_read next to its first use ("2 reads, wait, 2 MFMAs"), so the
@@ -229,92 +267,152 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& g, const int bid_x, co
         if (g.prio) __builtin_amdgcn_s_setprio(0);
     };
 
+    // probe builds only (tools/gemm_stamps.py): cycle stamps around the phases of the first 16 K-tiles of workgroup (0, 0, 0), both K loops
+#ifdef GEMM_STAMPS
+#define GSTAMP(k) do { if (g.stamps && bid_x == 0 && bid_y == 0 && bid_z == 0 && lane == 0 && kt < 16) g.stamps[((tid >> 6) * 16 + kt) * 8 + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
+#define GSTAMP_KT int kt = 0
+#define GSTAMP_NEXT ++kt
+#else
+#define GSTAMP(k) do {} while (0)
+#define GSTAMP_KT do {} while (0)
+#define GSTAMP_NEXT do {} while (0)
+#endif
     if constexpr (NSEG >= 2) {
         // pair products: per K-tile the hi and lo tiles of both operands are staged once; a k-step reads FM (+ FM) A fragments and 2 + 2
         // B fragments for 2 FM x NSEG MFMAs (hi hi, hi lo_B, lo_A hi) - two thirds of the fragment reads, one third of the barriers and
         // tile stores per MFMA of a plain product
         const TA* pa2 = (const TA*)g.A2 + (pa - (const TA*)g.A);
         const TB* pb2 = (const TB*)g.B2 + (pb - (const TB*)g.B);
-        uint4 ra[BM / 32], rb[BN / 32], rb2[BN / 32], ra2[NSEG == 3 ? BM / 32 : 1];
+        constexpr int NA = BM * KB / 2048, NB = BN * KB / 2048;
+        uint4 ra[NA], rb[NB], rb2[NB], ra2[NSEG == 3 ? NA : 1];
+        // depth 32: every chunk address is a uniform base (scalar registers, stepped per K-tile) plus ONE 32-bit lane offset per operand,
+        // shared by the hi and the lo tile - per-thread 64-bit pointers for four tiles do not fit under the register cap
+        const char* uA = (const char*)((const TA*)g.A + (long)m0 * g.lda + k_begin);
+        const char* uB = (const char*)((const TB*)g.B + (long)n0 * g.ldb + k_begin);
+        const char* uA2 = (const char*)((const TA*)g.A2 + (long)m0 * g.lda + k_begin);
+        const char* uB2 = (const char*)((const TB*)g.B2 + (long)n0 * g.ldb + k_begin);
+        const uint32_t vA = ((uint32_t)krow<KB>(tid) * (uint32_t)g.lda + (tid & (KB / 8 - 1)) * 8) * 2u;
+        const uint32_t vB = ((uint32_t)krow<KB>(tid) * (uint32_t)g.ldb + (tid & (KB / 8 - 1)) * 8) * 2u;
         auto load_all = [&](int k0) {
-            tile_load<TA, TM, AKC, BM, EDGE>(pa, g.lda, m0, k0, g.M, k_end, 0, tid, ra);
-            tile_load<TB, TM, BKC, BN, EDGE>(pb, g.ldb, n0, k0, g.N, k_end, 0, tid, rb);
-            tile_load<TB, TM, BKC, BN, EDGE>(pb2, g.ldb, n0, k0, g.N, k_end, 0, tid, rb2);
-            if constexpr (NSEG == 3) tile_load<TA, TM, AKC, BM, EDGE>(pa2, g.lda, m0, k0, g.M, k_end, 0, tid, ra2);
+            if constexpr (KB == BK) {
+                tile_load<TA, TM, AKC, BM, EDGE>(pa, g.lda, m0, k0, g.M, k_end, 0, tid, ra);
+                tile_load<TB, TM, BKC, BN, EDGE>(pb, g.ldb, n0, k0, g.N, k_end, 0, tid, rb);
+                tile_load<TB, TM, BKC, BN, EDGE>(pb2, g.ldb, n0, k0, g.N, k_end, 0, tid, rb2);
+                if constexpr (NSEG == 3) tile_load<TA, TM, AKC, BM, EDGE>(pa2, g.lda, m0, k0, g.M, k_end, 0, tid, ra2);
+            } else {
+                tile_load_u<BM, EDGE, KB>(uA, vA, g.lda, m0, k0, g.M, k_end, tid, ra);
+                tile_load_u<BN, EDGE, KB>(uB, vB, g.ldb, n0, k0, g.N, k_end, tid, rb);
+                tile_load_u<BN, EDGE, KB>(uB2, vB, g.ldb, n0, k0, g.N, k_end, tid, rb2);
+                if constexpr (NSEG == 3) tile_load_u<BM, EDGE, KB>(uA2, vA, g.lda, m0, k0, g.M, k_end, tid, ra2);
+            }
+        };
+        const int oa = (wm * (FM * 32) + (lane & 31)) * PK + (lane >> 5) * 8, ob = (wn * 64 + (lane & 31)) * PK + (lane >> 5) * 8;
+        auto load_hi = [&](int kk, bf16x8 (&fa)[FM], bf16x8 (&fb)[2]) {
+#pragma unroll
+            for (int i = 0; i < FM; ++i) fa[i] = *(const bf16x8*)&sA[oa + i * 32 * PK + kk * 16];
+#pragma unroll
+            for (int j = 0; j < 2; ++j) fb[j] = *(const bf16x8*)&sB[ob + j * 32 * PK + kk * 16];
+        };
+        auto load_lo = [&](int kk, bf16x8 (&fa2)[FM], bf16x8 (&fb2)[2]) {
+#pragma unroll
+            for (int j = 0; j < 2; ++j) fb2[j] = *(const bf16x8*)&sB2[ob + j * 32 * PK + kk * 16];
+            if constexpr (NSEG == 3) {
+#pragma unroll
+                for (int i = 0; i < FM; ++i) fa2[i] = *(const bf16x8*)&sA2[oa + i * 32 * PK + kk * 16];
+            }
+        };
+        auto mfmas = [&](const bf16x8 (&fa)[FM], const bf16x8 (&fa2)[FM], const bf16x8 (&fb)[2], const bf16x8 (&fb2)[2]) {
+            // (one pass over the accumulators per product type: consecutive MFMAs never wait on each other's result)
+#pragma unroll
+            for (int i = 0; i < FM; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) acc[i][j] = mfma16<TM>(fb[j], fa[i], acc[i][j]);
+#pragma unroll
+            for (int i = 0; i < FM; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) acc[i][j] = mfma16<TM>(fb2[j], fa[i], acc[i][j]);
+            if constexpr (NSEG == 3) {
+#pragma unroll
+                for (int i = 0; i < FM; ++i)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) acc[i][j] = mfma16<TM>(fb[j], fa2[i], acc[i][j]);
+            }
         };
         auto phase = [&]() {
-            auto load_frags = [&](int kk, bf16x8 (&fa)[FM], bf16x8 (&fa2)[FM], bf16x8 (&fb)[2], bf16x8 (&fb2)[2]) {
-                const int koff = kk * 16 + (lane >> 5) * 8;
-#pragma unroll
-                for (int i = 0; i < FM; ++i) {
-                    const int o = (wm * (FM * 32) + i * 32 + (lane & 31)) * PITCH + koff;
-                    fa[i] = *(const bf16x8*)&sA[o];
-                    if constexpr (NSEG == 3) fa2[i] = *(const bf16x8*)&sA2[o];
-                }
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    const int o = (wn * 64 + j * 32 + (lane & 31)) * PITCH + koff;
-                    fb[j] = *(const bf16x8*)&sB[o];
-                    fb2[j] = *(const bf16x8*)&sB2[o];
-                }
-            };
-            auto mfmas = [&](const bf16x8 (&fa)[FM], const bf16x8 (&fa2)[FM], const bf16x8 (&fb)[2], const bf16x8 (&fb2)[2]) {
-                // (one pass over the accumulators per product type: consecutive MFMAs never wait on each other's result)
-#pragma unroll
-                for (int i = 0; i < FM; ++i)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j) acc[i][j] = mfma16<TM>(fb[j], fa[i], acc[i][j]);
-#pragma unroll
-                for (int i = 0; i < FM; ++i)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j) acc[i][j] = mfma16<TM>(fb2[j], fa[i], acc[i][j]);
-                if constexpr (NSEG == 3) {
-#pragma unroll
-                    for (int i = 0; i < FM; ++i)
-#pragma unroll
-                        for (int j = 0; j < 2; ++j) acc[i][j] = mfma16<TM>(fb[j], fa2[i], acc[i][j]);
-                }
-            };
-            bf16x8 fa0[FM], fa20[FM], fb0[2], fb20[2], fa1[FM], fa21[FM], fb1[2], fb21[2];
             if (g.prio) __builtin_amdgcn_s_setprio(2);
-            load_frags(0, fa0, fa20, fb0, fb20);
+            if constexpr (KB == BK) {
+                // depth 64: four k-steps, hi and lo fragments of step kk + 1 read before the MFMAs of step kk (two register sets)
+                auto load_frags = [&](int kk, bf16x8 (&fa)[FM], bf16x8 (&fa2)[FM], bf16x8 (&fb)[2], bf16x8 (&fb2)[2]) {
 #pragma unroll
-            for (int kk = 0; kk < BK / 16; kk += 2) {
-                load_frags(kk + 1, fa1, fa21, fb1, fb21);
+                    for (int i = 0; i < FM; ++i) {
+                        fa[i] = *(const bf16x8*)&sA[oa + i * 32 * PK + kk * 16];
+                        if constexpr (NSEG == 3) fa2[i] = *(const bf16x8*)&sA2[oa + i * 32 * PK + kk * 16];
+                    }
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) {
+                        fb[j] = *(const bf16x8*)&sB[ob + j * 32 * PK + kk * 16];
+                        fb2[j] = *(const bf16x8*)&sB2[ob + j * 32 * PK + kk * 16];
+                    }
+                };
+                bf16x8 fa0[FM], fa20[FM], fb0[2], fb20[2], fa1[FM], fa21[FM], fb1[2], fb21[2];
+                load_frags(0, fa0, fa20, fb0, fb20);
+#pragma unroll
+                for (int kk = 0; kk < KB / 16; kk += 2) {
+                    load_frags(kk + 1, fa1, fa21, fb1, fb21);
+                    __builtin_amdgcn_sched_barrier(0);
+                    mfmas(fa0, fa20, fb0, fb20);
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (kk + 2 < KB / 16) load_frags(kk + 2, fa0, fa20, fb0, fb20);
+                    __builtin_amdgcn_sched_barrier(0);
+                    mfmas(fa1, fa21, fb1, fb21);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            } else {
+                // depth 32: two k-steps.  Both steps' hi fragments are resident; the lo fragments live in ONE register set that is read
+                // again between the steps - step 1's lo reads land behind its own hi hi products, which need none of them (16 registers
+                // fewer than two full sets: what the 168-register cap of three workgroups per CU asks for)
+                bf16x8 fa0[FM], fb0[2], fa1[FM], fb1[2], fa2[FM], fb2[2];
+                load_hi(0, fa0, fb0); load_lo(0, fa2, fb2);
                 __builtin_amdgcn_sched_barrier(0);
-                mfmas(fa0, fa20, fb0, fb20);
+                load_hi(1, fa1, fb1);                         // (behind step 0's reads: step 0's MFMAs wait for their own fragments only)
                 __builtin_amdgcn_sched_barrier(0);
-                if (kk + 2 < BK / 16) load_frags(kk + 2, fa0, fa20, fb0, fb20);
+                mfmas(fa0, fa2, fb0, fb2);
                 __builtin_amdgcn_sched_barrier(0);
-                mfmas(fa1, fa21, fb1, fb21);
+                load_lo(1, fa2, fb2);
+                __builtin_amdgcn_sched_barrier(0);
+                mfmas(fa1, fa2, fb1, fb2);
                 __builtin_amdgcn_sched_barrier(0);
             }
             if (g.prio) __builtin_amdgcn_s_setprio(0);
         };
         load_all(k_begin);
-        for (int k0 = k_begin; k0 < k_end; k0 += BK) {
-            tile_store<AKC, BM>(sA, tid, ra);
-            tile_store<BKC, BN>(sB, tid, rb);
-            tile_store<BKC, BN>(sB2, tid, rb2);
-            if constexpr (NSEG == 3) tile_store<AKC, BM>(sA2, tid, ra2);
+        GSTAMP_KT;
+        for (int k0 = k_begin; k0 < k_end; k0 += KB) {
+            GSTAMP(0);
+            tile_store<AKC, BM, KB>(sA, tid, ra);
+            tile_store<BKC, BN, KB>(sB, tid, rb);
+            tile_store<BKC, BN, KB>(sB2, tid, rb2);
+            if constexpr (NSEG == 3) tile_store<AKC, BM, KB>(sA2, tid, ra2);
+            GSTAMP(1);
             __syncthreads();
-            if (k0 + BK < k_end) {
-                pa += stepA; pb += stepB; pa2 += stepA; pb2 += stepB;
-                load_all(k0 + BK);
+            GSTAMP(2);
+            if (k0 + KB < k_end) {
+                if constexpr (KB == BK) { pa += stepA; pb += stepB; pa2 += stepA; pb2 += stepB; }
+                else { uA += KB * 2; uB += KB * 2; uA2 += KB * 2; uB2 += KB * 2; }
+                load_all(k0 + KB);
             }
+            GSTAMP(3);
             phase();
+            GSTAMP(4);
             __syncthreads();
+            GSTAMP(5);
+            GSTAMP_NEXT;
         }
     } else {
         uint4 ra[BM / 32], rb[BN / 32];
         tile_load<TA, TM, AKC, BM, EDGE>(pa, g.lda, m0, k_begin, g.M, k_end, g.partA, tid, ra);
         tile_load<TB, TM, BKC, BN, EDGE>(pb, g.ldb, n0, k_begin, g.N, k_end, g.partB, tid, rb);
-#ifdef GEMM_STAMPS
-#define GSTAMP(k) do { if (g.stamps && bid_x == 0 && bid_y == 0 && bid_z == 0 && lane == 0 && kt < 16) g.stamps[((tid >> 6) * 16 + kt) * 8 + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
-        int kt = 0;
-#else
-#define GSTAMP(k) do {} while (0)
-#endif
+        GSTAMP_KT;
         for (int k0 = k_begin; k0 < k_end; k0 += BK) {
             GSTAMP(0);
             tile_store<AKC, BM>(sA, tid, ra);
@@ -332,12 +430,11 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& g, const int bid_x, co
             GSTAMP(4);
             __syncthreads();
             GSTAMP(5);
-#ifdef GEMM_STAMPS
-            ++kt;
-#endif
+            GSTAMP_NEXT;
         }
     }
 
+    if constexpr (KB != BK) load_bias();
     if constexpr (CSUM) {
         if (do_cs && lane < 32) {                       // column lane of the result = row m of A; register 0 = result row 0 (fragment 0's
             float* q = g.csum_ws + (long)ks * g.M + m0 + wm * (FM * 32) + lane;     // sums), register 8 = result row 16 (fragment 1's)
@@ -415,10 +512,11 @@ template <typename TA, typename TB, typename TC, bool AKC, bool BKC, int FM, boo
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FM == 4 ? 2 : 3))) void gemm_kernel(GemmArgs g) {
     gemm_body<TA, TB, TC, AKC, BKC, FM, EDGE>(g, blockIdx.x, blockIdx.y, blockIdx.z, gridDim.x, gridDim.y, gridDim.z);
 }
-// pair products (sarssl_gemm_split): fp16 operands, NT layout, NSEG = 2 | 3 (see gemm_body); two workgroups per CU (55-74 KB of LDS)
-template <typename TC, int FM, bool EDGE, int NSEG>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void gemm_seg_kernel(GemmArgs g) {
-    gemm_body<f16, f16, TC, true, true, FM, EDGE, false, NSEG>(g, blockIdx.x, blockIdx.y, blockIdx.z, gridDim.x, gridDim.y, gridDim.z);
+// pair products (sarssl_gemm_split): fp16 operands, NT layout, NSEG = 2 | 3 (see gemm_body).  K-tile depth 64: two workgroups per CU
+// (45-74 KB of LDS, up to 228 registers); depth 32: three (27-40 KB, at most 168 registers)
+template <typename TC, int FM, bool EDGE, int NSEG, int KB>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KB == 32 ? 3 : 2))) void gemm_seg_kernel(GemmArgs g) {
+    gemm_body<f16, f16, TC, true, true, FM, EDGE, false, NSEG, KB>(g, blockIdx.x, blockIdx.y, blockIdx.z, gridDim.x, gridDim.y, gridDim.z);
 }
 
 // ---- grouped launch: up to GROUP_MAXP independent split-K weight-gradient products (A = dY [K][M], B = X [K][N], both with the
@@ -687,6 +785,18 @@ extern "C" int sarssl_gemm(const void* A, const void* B, void* C, int dtA, int d
 // cores.  The segments are a longer K loop of the plain kernel: same tiles, same epilogue, the prologue / epilogue of a short-K product
 // amortised over 2-3 times the MFMAs.  A, A_lo: [M][K] (row stride lda), B, B_lo: [N][K] (row stride ldb); A_lo / B_lo may be null.
 // C / resid / preact: dtC (fp16 | f32).
+template <typename TC, int NSEG, int KB>
+static void launch_seg_kb(const GemmArgs& g, int fm, bool edge, dim3 grid, hipStream_t st) {
+    if (fm == 1) { if (edge) gemm_seg_kernel<TC, 1, true, NSEG, KB><<<grid, 256, 0, st>>>(g); else gemm_seg_kernel<TC, 1, false, NSEG, KB><<<grid, 256, 0, st>>>(g); }
+    else { if (edge) gemm_seg_kernel<TC, 2, true, NSEG, KB><<<grid, 256, 0, st>>>(g); else gemm_seg_kernel<TC, 2, false, NSEG, KB><<<grid, 256, 0, st>>>(g); }
+}
+// K-tile depth of a pair product when the context does not force one.  Measured on MI355X inside the step (tools/step_gemm_table.py
+// --pair-kdepth 32 | 64, profiles/pair_bk_step_gemm_table_d32.txt / _d64.txt, M = 16384 / 8192; NOTES.md 20): with K <= 768 the third
+// workgroup per CU hides the prologue, the epilogue and the wait for the staged tiles (N = 2048, K = 512 x3: 174 -> 153 us; N = 768,
+// K = 256 x3: 62 -> 49 us; decoder layer 1, K = 768: 171 -> 156 us); from K = 1024 on the main loop dominates and the deep tile's
+// half as many barriers and tile-store waits per k win at either tile height (N = 1024, K = 3072 x2: 132 vs 141 us; N = 512, K = 1024
+// x3: 70 vs 77 us; N = 256, K = 1024 x3: 56 vs 64 us; N = 512, K = 2048 x2: 112 vs 113 us)
+static int pair_kdepth_rule(const GemmArgs& g) { return g.K >= 1024 ? BK : 32; }
 template <typename TC, int NSEG>
 static int launch_seg(const GemmArgs& g, hipStream_t st) {
     // 64-row tiles when 128-row tiles would leave CUs without a second workgroup (the rule of pick_fm), else 128 x 128
@@ -699,12 +809,15 @@ static int launch_seg(const GemmArgs& g, hipStream_t st) {
 #ifdef SARSSL_PROBE_ENV          // probe builds only: force a tile height, 1 | 2 (tools/hybrid_fm_ab.sh)
     { static const int force_fm = [] { const char* e = getenv("SARSSL_SPLIT_FM"); return e ? atoi(e) : 0; }(); if (force_fm) fm = force_fm; }
 #endif
+    // K-tile depth: the context's choice (sarssl_ctx_set_pair_kdepth: tests and A/B runs), else the rule below
+    const sarssl_ctx* cx = sarssl_current();
+    const int kb = (cx && cx->pair_kdepth) ? cx->pair_kdepth : pair_kdepth_rule(g);
     const int bm = 64 * fm;
     const bool vec_ok = ((g.N & 7) == 0) && ((g.ldc & 7) == 0) && (!g.resid || (g.ldr & 7) == 0);
-    const bool edge = (g.M % bm) != 0 || (g.N % BN) != 0 || (g.K % BK) != 0 || !vec_ok;
+    const bool edge = (g.M % bm) != 0 || (g.N % BN) != 0 || (g.K % kb) != 0 || !vec_ok;
     dim3 grid((g.N + BN - 1) / BN, (g.M + bm - 1) / bm, 1);
-    if (fm == 1) { if (edge) gemm_seg_kernel<TC, 1, true, NSEG><<<grid, 256, 0, st>>>(g); else gemm_seg_kernel<TC, 1, false, NSEG><<<grid, 256, 0, st>>>(g); }
-    else { if (edge) gemm_seg_kernel<TC, 2, true, NSEG><<<grid, 256, 0, st>>>(g); else gemm_seg_kernel<TC, 2, false, NSEG><<<grid, 256, 0, st>>>(g); }
+    if (kb == 32) launch_seg_kb<TC, NSEG, 32>(g, fm, edge, grid, st);
+    else launch_seg_kb<TC, NSEG, BK>(g, fm, edge, grid, st);
     SARSSL_CHECK_LAUNCH("sarssl_gemm_split");
     return 0;
 }
@@ -713,6 +826,7 @@ extern "C" int sarssl_gemm_split(const void* A, const void* A_lo, const void* B,
                                  float res_scale, void* preact, float p_drop, unsigned long long seed, void* stream) {
     SARSSL_REQUIRE(M > 0 && N > 0 && K > 0 && A && B && C, "sarssl_gemm_split");
     SARSSL_REQUIRE(K % 8 == 0 && lda % 8 == 0 && ldb % 8 == 0, "sarssl_gemm_split(alignment)");
+    SARSSL_REQUIRE(lda > 0 && ldb > 0 && lda < (1L << 24) && ldb < (1L << 24), "sarssl_gemm_split(row strides)");      // (32-bit lane offsets inside a tile)
     SARSSL_REQUIRE(dtC == SARSSL_F16 || dtC == SARSSL_F32, "sarssl_gemm_split(dtC)");
     GemmArgs g;
     g.A = A; g.B = B; g.C = C; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
@@ -728,7 +842,7 @@ extern "C" int sarssl_gemm_split(const void* A, const void* A_lo, const void* B,
     else if (B_lo) { g.A2 = nullptr; g.B2 = B_lo; g.nseg = 2; }
     else { g.A2 = nullptr; g.B2 = nullptr; g.nseg = 1; }
 #ifdef GEMM_STAMPS
-    g.stamps = nullptr;
+    g.stamps = g_gemm_stamps_host;
 #endif
     hipStream_t st = (hipStream_t)stream;
     if (g.nseg == 1) {                   // no lo parts: the plain fp16 product

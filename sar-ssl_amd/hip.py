@@ -1133,6 +1133,12 @@ def conv_cus_override(ncus):
     _lib.call("sarssl_ctx_set_conv_cus", c_void_p(_lib._make_current()), c_int(int(ncus)))
 
 
+def pair_kdepth_override(depth):
+    """K-tile depth (32 | 64) of the pair products gemm_split issues under this thread's context; 0: the library's rule per shape.  Both
+    depths give the same bits - tests and A/B timing."""
+    _lib.call("sarssl_ctx_set_pair_kdepth", c_void_p(_lib._make_current()), c_int(int(depth)))
+
+
 def _wgrad_part(B, F, T, device):
     nbytes = _lib.lib().sarssl_conv3x3_wgrad_workspace_bytes
     nbytes.restype = c_long

@@ -150,6 +150,12 @@ def main():
                 e["eff_clock_ghz"] = round(ghz, 3)
                 e["mfma_busy"] = round(m["SQ_VALU_MFMA_BUSY_CYCLES"] / (NSIMD * clk_cycles), 4)
                 e["mfma_busy_basis"] = "GRBM_GUI_ACTIVE / 8 (active cycles of the launch)"
+        if "SQ_WAVE_CYCLES" in m and "mfma.dur_ns" in m:
+            # occupancy as it was, not as the metadata allows: SQ_WAVE_CYCLES counts quad-cycles summed over the resident waves, so x 4 /
+            # (1024 SIMDs x launch cycles) is the mean number of waves resident per SIMD over the launch, tail and ramp included
+            # (launch cycles at the nominal 2.4 GHz: a lower bound, the chip never clocks above it)
+            e["waves_per_simd_mean"] = round(4.0 * m["SQ_WAVE_CYCLES"] / (NSIMD * max(m["mfma.dur_ns"] / m["n"], 1) * 2.4), 2)
+            e["waves"] = round(m.get("SQ_WAVES", 0))
         if "SQ_LDS_IDX_ACTIVE" in m:
             e["lds_conflict_rate"] = round(m["SQ_LDS_BANK_CONFLICT"] / max(m["SQ_LDS_IDX_ACTIVE"], 1), 4)
             wc = max(m.get("SQ_WAVE_CYCLES", 0), 1)

@@ -16,10 +16,13 @@ from sar_ssl_amd import hip, model, runtime, synth  # noqa: E402
 ap = argparse.ArgumentParser()
 ap.add_argument("--precision", default="fp16")
 ap.add_argument("--steps", type=int, default=6)
+ap.add_argument("--pair-kdepth", type=int, default=0, choices=[0, 32, 64], help="force the K-tile depth of the pair products (0: the library's rule)")
 ap.add_argument("--workload", default="config2", choices=["config2", "config5"], help="config5: 4 microphones x 10 s, T = 624, batch 16 x 6 pairs")
 a = ap.parse_args()
 dev = torch.device("cuda:0")
 runtime.set_precision(a.precision)
+if a.pair_kdepth:
+    hip.pair_kdepth_override(a.pair_kdepth)
 torch.manual_seed(1)
 T_, nsample_, nmic_, batch_ = (256, 65792, 2, 64) if a.workload == "config2" else (624, 160000, 4, 16)
 net = model.SARSSL(sig_shape=(256, T_, 2, 2), pretrain=True, device=dev).to(dev).train()
