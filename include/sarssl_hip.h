@@ -96,6 +96,14 @@ long sarssl_rir_mix_workspace_bytes(int nb, long ns, int nch, int lmax, int ldma
 int sarssl_rir_mix(const float* src, const float* rir, const int* rir_len, const float* rir_dp, const int* dp_len, int n0,
                    const float* noise, const float* snr_db, const float* gain, int nb, long ns, int nch, int lmax, int ldmax, void* ws,
                    float* out, void* stream);
+/*      the same with the direct-path signal stored (gen_simu.py --save_dp, utils_simu_rir_sig.py:825, 857-859): out_dp (B, ns, nch) f32 in
+ *      the layout of out, out_dp = dp / max(max|mic|, max|dp|) * gain - the item's own divisor and gain, applied as (dp / value) * gain in
+ *      f32, the operation order of out.  The same kernels as sarssl_rir_mix (which is this with out_dp = NULL): out is bit-identical between
+ *      the two.  Every element of out_dp is written: where the direct-path RIR's live partitions cannot reach a stretch of the signal the
+ *      device skips the transforms and stores 0.0 itself (out_dp is not cleared on the stream first).  out_dp = NULL is refused (-1). */
+int sarssl_rir_mix_dp(const float* src, const float* rir, const int* rir_len, const float* rir_dp, const int* dp_len, int n0,
+                      const float* noise, const float* snr_db, const float* gain, int nb, long ns, int nch, int lmax, int ldmax, void* ws,
+                      float* out, float* out_dp, void* stream);
 /*      diffuse noise field (code/data_generation/utils_noise.py:141-253): white (B, ns, M) f32 -> out (B, ns, M) f32 through
  *      scipy.signal.stft / istft's conventions (periodic Hann 256, hop 64, 128 zeros on both sides, division by the actual window-square
  *      sum) with the per-bin mix X_n = sum_m C[f][m][n] N_m, then out = noise / (max(noise) + 1e-8) (signed maximum over the item).

@@ -9,7 +9,9 @@
 // (samples [(t-1)256, (t+1)256)) are formed once per item, RIR partition spectra H_p once per RIR.  Two channels share one complex
 // transform and are NEVER separated: the source is real, so IFFT(X . FFT(h_a + i h_b)) = x*h_a + i x*h_b.  One workgroup forms 8
 // consecutive output blocks of one (item, channel pair): a thread owns one bin, keeps the 8 sliding source spectra in registers and reads
-// every H_p once.  The direct-path signal is never stored - only its power and peak are needed.
+// every H_p once.  The direct-path signal is needed for its power and peak only; sarssl_rir_mix_dp also stores it (out_dp, the layout and
+// the scale of out), from the same kernels: out_dp == nullptr is sarssl_rir_mix.  A workgroup that leaves early because its stretch of
+// the direct-path signal is exactly zero writes those zeros itself before it returns - out_dp is not cleared on the stream first.
 #include "common.h"
 #include "fft_wave.h"
 
@@ -162,11 +164,11 @@ __global__ __launch_bounds__(512) void rir_spec_kernel(const float* __restrict__
 }
 
 // Y_t = sum_p X_{t-p} H_p for TB consecutive t, inverse transform, last 256 samples.  q < npair: clean -> out (and the noise power of these
-// samples), q >= npair: direct path -> power and peak only.
+// samples), q >= npair: direct path -> power and peak, and out_dp where it is given.
 __global__ __launch_bounds__(512) void rir_conv_kernel(const float2* __restrict__ X, const float2* __restrict__ H,
                                                        const int* __restrict__ prange, const float* __restrict__ noise, long ns, int nch,
-                                                       int nT, int npair, int P, float* __restrict__ out, double* __restrict__ stats,
-                                                       unsigned* __restrict__ peak) {
+                                                       int nT, int npair, int P, float* __restrict__ out, float* __restrict__ out_dp,
+                                                       double* __restrict__ stats, unsigned* __restrict__ peak) {
     __shared__ float2 Z[TB * RZ];
     __shared__ float rsum[TB], rmax[TB];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -174,7 +176,20 @@ __global__ __launch_bounds__(512) void rir_conv_kernel(const float2* __restrict_
     const int lo = prange[(b * Q + q) * 2];
     const int upper = min(min(prange[(b * Q + q) * 2 + 1], P - 1), T0 + TB - 1);      // X_s is zero for s < 0
     const bool isdp = q >= npair;
-    if (isdp && lo > upper) return;                      // this stretch of the direct-path signal is exactly zero (uniform: before any barrier)
+    if (isdp && lo > upper) {                            // this stretch of the direct-path signal is exactly zero (uniform: before any barrier)
+        if (out_dp) {
+            const int c0 = 2 * (q % npair), c1 = c0 + 1;
+            for (int i = tid; i < TB * RB; i += 512) {
+                const long n = (long)T0 * RB + i;
+                if (n < ns) {
+                    const long o = ((long)b * ns + n) * nch;
+                    out_dp[o + c0] = 0.f;
+                    if (c1 < nch) out_dp[o + c1] = 0.f;
+                }
+            }
+        }
+        return;
+    }
 
     const float2* Xb = X + (long)b * nT * RN + tid;
     const float2* Hb = H + ((long)b * Q + q) * P * RN + tid;
@@ -232,6 +247,10 @@ __global__ __launch_bounds__(512) void rir_conv_kernel(const float2* __restrict_
                 if (isdp) {
                     s = fmaf(y0, y0, s); m = fmaxf(m, fabsf(y0));
                     if (c1 < nch) { s = fmaf(y1, y1, s); m = fmaxf(m, fabsf(y1)); }
+                    if (out_dp) {
+                        out_dp[o + c0] = y0;
+                        if (c1 < nch) out_dp[o + c1] = y1;
+                    }
                 } else {
                     out[o + c0] = y0;
                     if (c1 < nch) out[o + c1] = y1;
@@ -281,7 +300,7 @@ __global__ __launch_bounds__(256) void rir_mic_peak_kernel(const float* __restri
     __syncthreads();
     if (tid == 0) atomicMax(&peak[b * 2 + 1], __float_as_uint(fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]))));
 }
-__global__ __launch_bounds__(256) void rir_mix_final_kernel(float* __restrict__ out, const float* __restrict__ noise,
+__global__ __launch_bounds__(256) void rir_mix_final_kernel(float* __restrict__ out, float* __restrict__ out_dp, const float* __restrict__ noise,
                                                             const float* __restrict__ snr_db, const float* __restrict__ gain,
                                                             const double* __restrict__ stats, const unsigned* __restrict__ peak, long ns,
                                                             int nch) {
@@ -292,6 +311,7 @@ __global__ __launch_bounds__(256) void rir_mix_final_kernel(float* __restrict__ 
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < per; i += (long)gridDim.x * 256) {
         const float v = noise ? fmaf(g, noise[o + i], out[o + i]) : out[o + i];
         out[o + i] = v / value * gn;
+        if (out_dp) out_dp[o + i] = out_dp[o + i] / value * gn;
     }
 }
 
@@ -300,9 +320,9 @@ extern "C" long sarssl_rir_mix_workspace_bytes(int nb, long ns, int nch, int lma
     return rir_ws_layout(nullptr, nb, ns, nch, lmax, ldmax).bytes;
 }
 
-extern "C" int sarssl_rir_mix(const float* src, const float* rir, const int* rir_len, const float* rir_dp, const int* dp_len, int n0,
-                              const float* noise, const float* snr_db, const float* gain, int nb, long ns, int nch, int lmax, int ldmax,
-                              void* ws, float* out, void* stream) {
+static int rir_mix_launch(const float* src, const float* rir, const int* rir_len, const float* rir_dp, const int* dp_len, int n0,
+                          const float* noise, const float* snr_db, const float* gain, int nb, long ns, int nch, int lmax, int ldmax, void* ws,
+                          float* out, float* out_dp, void* stream) {
     SARSSL_REQUIRE(src && rir && rir_len && snr_db && gain && ws && out, "sarssl_rir_mix");
     SARSSL_REQUIRE(nb > 0 && nb <= 65535 && ns > 0 && ns < (1L << 31) - 2 * RN && nch >= 1 && nch <= 8 && lmax >= 1, "sarssl_rir_mix");
     SARSSL_REQUIRE(rir_dp ? (dp_len && ldmax >= 1) : (n0 >= 0 && ldmax == 0), "sarssl_rir_mix(explicit rir_dp + dp_len + ldmax, or a window n0 with ldmax 0)");
@@ -318,15 +338,29 @@ extern "C" int sarssl_rir_mix(const float* src, const float* rir, const int* rir
     rir_spec_kernel<<<dim3((w.P + TB - 1) / TB, w.Q, nb), 512, 0, st>>>(rir, rir_len, rir_dp, dp_len, n0, nch, lmax, ldmax, w.npair, w.P, w.nd,
                                                                       w.prange, w.H);
     SARSSL_CHECK_LAUNCH("rir_spec_kernel");
-    rir_conv_kernel<<<dim3((w.nT + TB - 1) / TB, w.Q, nb), 512, 0, st>>>(w.X, w.H, w.prange, noise, ns, nch, w.nT, w.npair, w.P, out, w.stats,
+    rir_conv_kernel<<<dim3((w.nT + TB - 1) / TB, w.Q, nb), 512, 0, st>>>(w.X, w.H, w.prange, noise, ns, nch, w.nT, w.npair, w.P, out, out_dp, w.stats,
                                                                        w.peak);
     SARSSL_CHECK_LAUNCH("rir_conv_kernel");
     long nblk = (ns * nch + 256 * 8 - 1) / (256 * 8); if (nblk > 256) nblk = 256;
     rir_mic_peak_kernel<<<dim3((int)nblk, nb), 256, 0, st>>>(out, noise, snr_db, w.stats, ns, nch, w.peak);
     SARSSL_CHECK_LAUNCH("rir_mic_peak_kernel");
-    rir_mix_final_kernel<<<dim3((int)nblk, nb), 256, 0, st>>>(out, noise, snr_db, gain, w.stats, w.peak, ns, nch);
+    rir_mix_final_kernel<<<dim3((int)nblk, nb), 256, 0, st>>>(out, out_dp, noise, snr_db, gain, w.stats, w.peak, ns, nch);
     SARSSL_CHECK_LAUNCH("rir_mix_final_kernel");
     return 0;
+}
+
+extern "C" int sarssl_rir_mix(const float* src, const float* rir, const int* rir_len, const float* rir_dp, const int* dp_len, int n0,
+                              const float* noise, const float* snr_db, const float* gain, int nb, long ns, int nch, int lmax, int ldmax,
+                              void* ws, float* out, void* stream) {
+    return rir_mix_launch(src, rir, rir_len, rir_dp, dp_len, n0, noise, snr_db, gain, nb, ns, nch, lmax, ldmax, ws, out, nullptr, stream);
+}
+
+// the same launches with the direct-path signal stored: out_dp (B, ns, nch) f32 = dp / max(max|mic|, max|dp|) * gain
+extern "C" int sarssl_rir_mix_dp(const float* src, const float* rir, const int* rir_len, const float* rir_dp, const int* dp_len, int n0,
+                                 const float* noise, const float* snr_db, const float* gain, int nb, long ns, int nch, int lmax, int ldmax,
+                                 void* ws, float* out, float* out_dp, void* stream) {
+    SARSSL_REQUIRE(out_dp, "sarssl_rir_mix_dp(out_dp)");
+    return rir_mix_launch(src, rir, rir_len, rir_dp, dp_len, n0, noise, snr_db, gain, nb, ns, nch, lmax, ldmax, ws, out, out_dp, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ diffuse noise field

@@ -691,11 +691,13 @@ def _i32(t):
     return t
 
 
-def rir_mix(src, rir, rir_len, snr_db, gain, *, rir_dp=None, dp_len=None, n0=None, noise=None, out=None):
+def rir_mix(src, rir, rir_len, snr_db, gain, *, rir_dp=None, dp_len=None, n0=None, noise=None, out=None, out_dp=None):
     """src (B, Ns), rir (B, nch, Lmax) + rir_len int32 (B), the direct path as (rir_dp (B, nch, Ldmax) + dp_len) or a window half-width
     ``n0`` around each channel's signed maximum, noise (B, Ns, nch) or None, snr_db / gain f32 (B) -> (B, Ns, nch) f32 (the layout
-    data_preprocess takes).  See include/sarssl_hip.h for the arithmetic."""
-    _need_cuda(src, rir, rir_len, rir_dp, dp_len, noise, snr_db, gain, out)
+    data_preprocess takes).  out_dp: a (B, Ns, nch) f32 tensor that receives the direct-path signal at the scale of the result
+    (sarssl_rir_mix_dp; every element is written, the result is bit-identical with and without it).  See include/sarssl_hip.h for the
+    arithmetic."""
+    _need_cuda(src, rir, rir_len, rir_dp, dp_len, noise, snr_db, gain, out, out_dp)
     if (rir_dp is None) == (n0 is None):
         raise _lib.SarsslHipError("rir_mix: give either rir_dp + dp_len or n0")
     B, Ns = src.shape
@@ -715,9 +717,16 @@ def rir_mix(src, rir, rir_len, snr_db, gain, *, rir_dp=None, dp_len=None, n0=Non
     if out is None:
         out = torch.empty((B, Ns, nch), dtype=torch.float32, device=src.device)
     assert out.shape == (B, Ns, nch) and out.dtype == torch.float32 and out.is_contiguous()
-    _lib.call("sarssl_rir_mix", _p(src), _p(rir), _p(_i32(rir_len)), _p(rir_dp), _p(_i32(dp_len) if dp_len is not None else None),
+    if out_dp is None:
+        _lib.call("sarssl_rir_mix", _p(src), _p(rir), _p(_i32(rir_len)), _p(rir_dp), _p(_i32(dp_len) if dp_len is not None else None),
+                  c_int(n0 if n0 is not None else 0), _p(noise), _p(snr_db), _p(gain), c_int(B), c_long(Ns), c_int(nch), c_int(Lmax),
+                  c_int(Ldmax), _p(ws), _p(out), _stream())
+        return out
+    assert out_dp.shape == (B, Ns, nch) and out_dp.dtype == torch.float32 and out_dp.is_contiguous()
+    assert out_dp.data_ptr() != out.data_ptr()
+    _lib.call("sarssl_rir_mix_dp", _p(src), _p(rir), _p(_i32(rir_len)), _p(rir_dp), _p(_i32(dp_len) if dp_len is not None else None),
               c_int(n0 if n0 is not None else 0), _p(noise), _p(snr_db), _p(gain), c_int(B), c_long(Ns), c_int(nch), c_int(Lmax),
-              c_int(Ldmax), _p(ws), _p(out), _stream())
+              c_int(Ldmax), _p(ws), _p(out), _p(out_dp), _stream())
     return out
 
 

@@ -52,8 +52,12 @@ GATES = {
 # restatement_vs_f20: the same distance between the f64 restatement and fixture F20 of the real reference (mixed f32 / f64 arithmetic, stored
 # as f32), measured on the CPU (tests/test_rirsynth_cpu.py prints it), x4, one digit; the renderer is held to gate + restatement_vs_f20
 # against F20 (triangle inequality).
+# The stored direct-path signal (sarssl_rir_mix_dp's out_dp, tests/test_gpu_simsig_dp.py) is held to the same gate as out - the same
+# transforms over fewer partitions - and restate_sig(with_dp=True) against fixture F24 of the real reference to restatement_vs_f20 - the
+# same two fftconvolve calls (tests/test_simsig_dp_cpu.py); rir_mix_dp and restatement_dp_vs_f24 record what those tests measure.
 RIRMIX = dict(gate=2e-6, cap=1.5e-5, restatement_vs_f20=8e-7,
-              measured=dict(rir_mix=2.8e-7, diffuse_noise=2.9e-7, loader=3.1e-7, restatement_vs_f20=1.9e-7))
+              measured=dict(rir_mix=2.8e-7, diffuse_noise=2.9e-7, loader=3.1e-7, restatement_vs_f20=1.9e-7, rir_mix_dp=2.7e-7,
+                            restatement_dp_vs_f24=7.5e-9))
 
 
 # The image-source renderer (csrc/ism.hip) against the f64 numpy restatement roomsim.restate_ism: max |difference| over an RIR relative to

@@ -34,8 +34,9 @@ def direct_path_window(rir, n0):
     return rir * ((n >= nd - n0) & (n <= nd + n0))
 
 
-def restate_mix(src, rir, rir_dp=None, n0=None, noise=None, snr_db=0.0, gain=1.0):
-    """One item in f64: src (Ns,), rir (nch, L), rir_dp (nch, Ld) or a window half-width n0, noise (Ns, nch) or None -> (Ns, nch)."""
+def restate_mix(src, rir, rir_dp=None, n0=None, noise=None, snr_db=0.0, gain=1.0, return_dp=False):
+    """One item in f64: src (Ns,), rir (nch, L), rir_dp (nch, Ld) or a window half-width n0, noise (Ns, nch) or None -> (Ns, nch);
+    return_dp=True: -> (that, the direct-path signal (Ns, nch) at the same scale, dp / value * gain)."""
     import scipy.signal
     src = np.asarray(src, np.float64)
     rir = np.asarray(rir, np.float64)
@@ -50,7 +51,7 @@ def restate_mix(src, rir, rir_dp=None, n0=None, noise=None, snr_db=0.0, gain=1.0
     p_n = np.mean(np.sum(noise ** 2, axis=0) / ns)
     mic = clean + np.sqrt(p_dp / (10 ** (snr_db / 10))) / (np.sqrt(p_n) + 1e-10) * noise
     value = max(np.abs(mic).max(), np.abs(dp).max())
-    return mic / value * gain
+    return (mic / value * gain, dp / value * gain) if return_dp else mic / value * gain
 
 
 def mixing_table(mic_pos, fs=FS, c=343.0, nfft=256):
@@ -336,13 +337,14 @@ def read_noise(path, start, nsample, nch, fs=FS):
 
 
 # ---------------------------------------------------------------------------------------------------------------- batch loader
-def mix_simulated(src, rir, rir_len, dp, dp_len, white, C, snr, gain, out=None):
+def mix_simulated(src, rir, rir_len, dp, dp_len, white, C, snr, gain, out=None, out_dp=None):
     """The mix of a batch of simulated items on the current stream: ``white`` (B, Ns, nch) becomes, in place, the diffuse field of the
-    mixing tables C (B, 129, nch, nch), and hip.rir_mix adds it to src * rir at snr dB against the direct path dp -> (B, Ns, nch).
+    mixing tables C (B, 129, nch, nch), and hip.rir_mix adds it to src * rir at snr dB against the direct path dp -> (B, Ns, nch);
+    out_dp (B, Ns, nch), where given, receives the direct-path signal at the same scale.
     Where ``white`` comes from stays with the caller: the loader and roomsim.simulate_signals key their device draws differently."""
     from . import hip
     field = hip.diffuse_noise(white, C, out=white)
-    return hip.rir_mix(src, rir, rir_len, snr, gain, rir_dp=dp, dp_len=dp_len, noise=field, out=out)
+    return hip.rir_mix(src, rir, rir_len, snr, gain, rir_dp=dp, dp_len=dp_len, noise=field, out=out, out_dp=out_dp)
 
 
 class RirSynthLoader:

@@ -473,11 +473,11 @@ def check_noise_type(noise_type):
     return noise_type
 
 
-def restate_sig(plan, tail_noise=None, rir=None, rir_dp=None, pcm=True, fs=FS, c=343.0, ism_db=12, noise_type="diffuse_white"):
+def restate_sig(plan, tail_noise=None, rir=None, rir_dp=None, pcm=True, fs=FS, c=343.0, ism_db=12, noise_type="diffuse_white", with_dp=False):
     """One item of the generator in f64 from the existing restatements: the RIR and the direct path of plan['cfg'] (restate_cfg; or the
     given ``rir`` / ``rir_dp`` (nch, L)), the diffuse field of the plan's white noise (noise_type="spatial_white": the white noise as
-    drawn, utils_noise.py:65-66), the mix at gain 0.9, and with pcm=True the PCM rule -> (Ns, nch) int16 (float64 with pcm=False).  The
-    authority for the GPU tests."""
+    drawn, utils_noise.py:65-66), the mix at gain 0.9, and with pcm=True the PCM rule -> (Ns, nch) int16 (float64 with pcm=False);
+    with_dp=True: -> (that, the direct-path signal of ``{idx}_dp.wav`` in the same form).  The authority for the GPU tests."""
     from . import rirsynth
     cfg = plan["cfg"]
     if rir is None:
@@ -488,8 +488,10 @@ def restate_sig(plan, tail_noise=None, rir=None, rir_dp=None, pcm=True, fs=FS, c
         noise = np.asarray(plan["white"], np.float64)
     else:
         noise = rirsynth.restate_diffuse(plan["white"], rirsynth.mixing_table(cfg["mic_pos"], fs, c))
-    mic = rirsynth.restate_mix(plan["src"], rir, rir_dp=rir_dp, noise=noise, snr_db=plan["snr"], gain=PCM_GAIN)
-    return pcm16(mic) if pcm else mic
+    sigs = rirsynth.restate_mix(plan["src"], rir, rir_dp=rir_dp, noise=noise, snr_db=plan["snr"], gain=PCM_GAIN, return_dp=with_dp)
+    if with_dp:
+        return tuple(pcm16(x) if pcm else x for x in sigs)
+    return pcm16(sigs) if pcm else sigs
 
 
 def sig_info(cfg, plan, T60_edc, DRR, C50, c=343.0):
@@ -725,11 +727,14 @@ def sig_lmax(T60_range, fs=FS):
 
 
 def simulate_signals(save_to, stage="pretrain", data_num=1, src_dir="", mic_array_cfg=None, device="cuda", noise="device", batch=16,
-                     T=4.112, snr_range=(15, 30), sort_sources=False, nthreads=0, log=None, **ranges):
+                     T=4.112, snr_range=(15, 30), sort_sources=False, nthreads=0, log=None, save_dp=False, **ranges):
     """GenerateRandomMicSig (gen_simu.py:178-360) with generate_microphone_signal (utils_simu_rir_sig.py:749-861): ``data_num`` items of
     ``stage`` (pretrain | preval | pretest | pretest_ins*: its seed, and src_dir + /tr | /dt | /et, as there) as ``{idx}.wav`` PCM-16
     (int(T fs), nch) and ``{idx}_info.npz`` (configuration, T60_edc, SNR, src_idx, TDOA / DRR / C50 with the reference's dtypes) under
-    ``save_to/stage``, with ``all_info.npz`` as in ``simulate_bank``.
+    ``save_to/stage``, with ``all_info.npz`` as in ``simulate_bank``.  save_dp=True (any stage; the reference documents it for
+    pretest_ins*, whose test stage opens the files): the direct-path signal at the item's scale, dp / max(max|mic|, max|dp|) 0.9, as
+    ``{idx}_dp.wav`` beside every ``{idx}.wav`` (utils_simu_rir_sig.py:825, 857-859); all_info.npz's args then record save_dp=True, and
+    nothing else that is written changes.
 
     The generator loop (``_generate``: ``render_items``, ``judge_on_device``, one small read-back of the labels, retries) on a side
     stream, with a sink that never takes the RIR off the device: a gather of the accepted items, the white noise (noise="device":
@@ -751,16 +756,20 @@ def simulate_signals(save_to, stage="pretrain", data_num=1, src_dir="", mic_arra
     sources = rirsynth.SourceBank(src_dir + "/" + SIG_SRC_SUBDIR[base], args["fs"], sort=sort_sources)
     out_dir, cfgs = _rooms(save_to, stage, seed, data_num, mic_array_cfg, args)
     return _signals("simulate_signals", out_dir, stage, cfgs, seed, args, sources, lambda idx: os.path.join(out_dir, "%d" % idx), device, noise,
-                    batch, T, snr_range, mic_array_cfg["mic_pos_relative"].shape[0], nthreads, log, recorded=dict(src_dir=src_dir))
+                    batch, T, snr_range, mic_array_cfg["mic_pos_relative"].shape[0], nthreads, log, recorded=dict(src_dir=src_dir),
+                    save_dp=save_dp)
 
 
 def _signals(who, out_dir, stage, cfgs, seed, args, sources, stem, device, noise, batch, T, snr_range, nmic, nthreads, log, table="host",
-             noise_type="diffuse_white", saved_cfgs=None, recorded=None):
+             noise_type="diffuse_white", saved_cfgs=None, recorded=None, save_dp=False):
     """The signal generators' run of ``_generate`` (see ``simulate_signals``): item idx of ``cfgs``, planned by plan_sig after seed + idx,
     goes to ``stem(idx)`` + .wav and _info.npz.  table: where the diffuse field's mixing table is formed - "host": rirsynth.mixing_table
     while the GPU renders, uploaded with the source; "device": hip.mixing_table of the batch's uploaded microphone positions.
     noise_type="spatial_white": the white noise goes into hip.rir_mix as it is (no field, no division by its maximum).
-    recorded: what all_info.npz's args hold beside the ranges, T and snr_range."""
+    recorded: what all_info.npz's args hold beside the ranges, T and snr_range.  save_dp: the mix also stores the direct-path signal
+    (hip.rir_mix's out_dp); it is packed and copied with the microphone signal - the pinned buffers take both, the batch's signals and
+    then their direct paths - and written as ``stem(idx)`` + _dp.wav in the same write_wav_batch call; all_info.npz's args then hold
+    save_dp=True."""
     import torch
     from concurrent.futures import ThreadPoolExecutor
     from . import hip, rirsynth
@@ -773,7 +782,8 @@ def _signals(who, out_dir, stage, cfgs, seed, args, sources, stem, device, noise
     rs = np.random.RandomState()
     dev = torch.device(device)
     side = torch.cuda.Stream(dev)
-    pinned = [torch.empty((batch, ns, nmic), dtype=torch.int16, pin_memory=True) for _ in range(2)]
+    nsig = 2 if save_dp else 1                                # signals per item: the microphones', then the direct path's
+    pinned = [torch.empty((nsig, batch, ns, nmic), dtype=torch.int16, pin_memory=True) for _ in range(2)]
     busy = [None, None]                                       # the writer job that still reads each pinned buffer
     sig_plans, nbatch = {}, 0
 
@@ -787,7 +797,10 @@ def _signals(who, out_dir, stage, cfgs, seed, args, sources, stem, device, noise
 
     def write(ev, buf, ids, infos):
         ev.synchronize()
-        write_wav_batch([stem(i) + ".wav" for i in ids], buf[:len(ids)], fs, nthreads)
+        paths = [stem(i) + ".wav" for i in ids]
+        if save_dp:
+            paths += [stem(i) + "_dp.wav" for i in ids]
+        write_wav_batch(paths, buf, fs, nthreads)
         for i, info in zip(ids, infos):
             np.savez(stem(i) + "_info.npz", **info)
 
@@ -815,30 +828,34 @@ def _signals(who, out_dir, stage, cfgs, seed, args, sources, stem, device, noise
         rir_len = torch.tensor([b.plans[j]["n_len"] for j in acc], dtype=torch.int32, device=dev)
         dp_len = torch.tensor([b.plans_dp[j]["n_len"] for j in acc], dtype=torch.int32, device=dev)
         gain = torch.full((A,), PCM_GAIN, dtype=torch.float32, device=dev)
+        sig = torch.empty((nsig, A, ns, nmic), dtype=torch.float32, device=dev)
+        out_dp = sig[1] if save_dp else None
         if not diffuse:
-            mic = hip.rir_mix(src, rir_dev, rir_len, snr, gain, rir_dp=dp_dev, dp_len=dp_len, noise=white)
+            hip.rir_mix(src, rir_dev, rir_len, snr, gain, rir_dp=dp_dev, dp_len=dp_len, noise=white, out=sig[0], out_dp=out_dp)
         else:
             if ntab:
                 C = up[:, ns + 1:].reshape(A, 129, nmic, nmic).contiguous()
             else:
                 mic_pos = np.ascontiguousarray(np.stack([cfgs[i]["mic_pos"] for i in aids]), np.float64)    # (the draws leave them column-major)
                 C = hip.mixing_table(torch.from_numpy(mic_pos).to(dev), float(fs), float(c))
-            mic = rirsynth.mix_simulated(src, rir_dev, rir_len, dp_dev, dp_len, white, C, snr, gain)
-        pcm = hip.pcm16_pack(mic)
+            rirsynth.mix_simulated(src, rir_dev, rir_len, dp_dev, dp_len, white, C, snr, gain, out=sig[0], out_dp=out_dp)
+        pcm = hip.pcm16_pack(sig)
         k = nbatch % 2
         nbatch += 1
         if busy[k] is not None:
             busy[k].result()                                  # the buffer's previous batch is on disk
-        pinned[k][:A].copy_(pcm, non_blocking=True)
+        staged = pinned[k].view(-1)[:nsig * A * ns * nmic].view(nsig * A, ns, nmic)      # dense: the A signals, then their A direct paths
+        staged.copy_(pcm.view(nsig * A, ns, nmic), non_blocking=True)
         ev = torch.cuda.Event()
         ev.record(side)
         infos = [sig_info(cfgs[i], sig_plans.pop(i), lab["t60_edc"][j], lab["drr"][j], lab["c50"][j], c) for i, j in zip(aids, acc)]
-        busy[k] = writer.submit(write, ev, pinned[k], aids, infos)
+        busy[k] = writer.submit(write, ev, staged, aids, infos)
         return aids
 
     with ThreadPoolExecutor(max_workers=1) as writer, torch.cuda.stream(side):
         res = _generate(who, out_dir, stage, cfgs, seed, args, dev, noise, batch, "device", sink, log, prepare,
-                        sig_lmax(args["T60_range"], fs), saved_cfgs, T=T, snr_range=tuple(snr_range), **(recorded or {}))
+                        sig_lmax(args["T60_range"], fs), saved_cfgs, T=T, snr_range=tuple(snr_range), **(recorded or {}),
+                        **(dict(save_dp=True) if save_dp else {}))
         for f in busy:
             if f is not None:
                 f.result()
@@ -1038,15 +1055,17 @@ def main(argv=None):
             sig_stage(a.stage)
         except ValueError as e:
             ap.error(str(e))
-        if a.save_dp:
-            ap.error("--save_dp True: the direct-path signal is not written (the mix kernel never stores it)")
+        if a.save_dp and "pretest_ins" not in a.stage:
+            ap.error("--save_dp True: the direct-path companions {idx}_dp.wav are written for the pretest_ins* stages only, where the "
+                     "reference documents the flag and run_pretrain.py --test --test-mode ins reads them; nothing reads them on "
+                     "pretrain / preval / pretest, whose corpora they would double")
         if a.noise_type != "diffuse_white":
             ap.error("--noise_type %s: diffuse_white only" % a.noise_type)
         _shared_sig_refusals(ap, a)
     device, ranges = _shared_refusals(ap, a)
     if a.mode == "sig":
         res = simulate_signals(a.save_to, a.stage, a.data_num, a.src_dir, MIC_ARRAYS[a.mic_array], device=device,
-                               noise=a.noise, batch=a.batch, T=a.T, snr_range=tuple(a.snr_range), **ranges)
+                               noise=a.noise, batch=a.batch, T=a.T, snr_range=tuple(a.snr_range), save_dp=a.save_dp, **ranges)
         print("%d microphone signals written to %s, %d skipped" % (len(res["written"]), os.path.join(a.save_to, a.stage), len(res["skipped"])))
         return 0
     res = simulate_bank(a.save_to, a.stage, a.data_num, MIC_ARRAYS[a.mic_array], device=device, noise=a.noise, batch=a.batch,

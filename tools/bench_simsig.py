@@ -1,6 +1,6 @@
 """Throughput of the generators with the accept test on the device -> profiles/simsig.txt
 
-    python tools/bench_simsig.py [--items 32] [--sig-items 64] [--out profiles/simsig.txt]
+    python tools/bench_simsig.py [--items 32] [--sig-items 64] [--save_dp] [--out profiles/simsig.txt]
 
 1. gen_simu.py --mode rir at batch 1 / 4 / 16, default ranges, stage train: RIRs/s of a whole pass of the generator's own loop (plan,
    render, accept test, read-back; one attempt, no file is written) with roomsim.judge_on_host against roomsim.judge_on_device
@@ -8,6 +8,7 @@
 2. gen_simu.py --mode sig at batch 16, default ranges, T = 4.112 s, device noise, on a synthetic speech tree: items/s of
    roomsim.simulate_signals as a whole, and in a second, profiled pass the time per item of every stage - the GPU stages between events
    (hip.profile_start(all_calls=True): every C-ABI call under its entry point's name), the host stages by wall clock.
+   --save_dp: part 2 at stage pretest_ins_T1000 with save_dp=True ({idx}_dp.wav beside every item: the mix is sarssl_rir_mix_dp).
 Also the distances of parity.RIRLABELS over the cases of tests/simsig_cases.py.
 """
 import argparse
@@ -40,12 +41,12 @@ def rir_pass(roomsim, torch, dev, cfgs, seed, bs, where):
     return time.perf_counter() - t0
 
 
-def speech_tree(root, nspk=4, nutt=4, seconds=6.0, fs=16000):
+def speech_tree(root, nspk=4, nutt=4, seconds=6.0, fs=16000, sub="tr"):
     from sar_ssl_amd.dataset import write_wav_pcm16
     rs = np.random.RandomState(0)
     for s in range(nspk):
         for u in range(nutt):
-            path = os.path.join(root, "tr", "si_tr_s", "spk%d" % s, "utt%d.wav" % u)
+            path = os.path.join(root, sub, "si_tr_s", "spk%d" % s, "utt%d.wav" % u)
             os.makedirs(os.path.dirname(path), exist_ok=True)
             x = np.cumsum(rs.standard_normal(int(seconds * fs))) * 200 + rs.standard_normal(int(seconds * fs)) * 2000
             write_wav_pcm16(path, np.clip(x, -30000, 30000).astype(np.int16)[:, None], fs)
@@ -75,6 +76,7 @@ def main():
     ap.add_argument("--items", type=int, default=32)
     ap.add_argument("--sig-items", type=int, default=64)
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--save_dp", action="store_true", help="--mode sig at stage pretest_ins_T1000 with the direct-path files")
     ap.add_argument("--out", type=str, default=os.path.join(ROOT, "profiles", "simsig.txt"))
     a = ap.parse_args()
     seed, dev = roomsim.STAGE_SEEDS["train"], torch.device("cuda:0")
@@ -132,12 +134,13 @@ def main():
 
     # --mode sig
     with tempfile.TemporaryDirectory() as tmp:
-        src = speech_tree(os.path.join(tmp, "src"))
+        stage, kw, mix = ("pretest_ins_T1000", dict(save_dp=True), "sarssl_rir_mix_dp") if a.save_dp else ("pretrain", {}, "sarssl_rir_mix")
+        src = speech_tree(os.path.join(tmp, "src"), sub=roomsim.SIG_SRC_SUBDIR[roomsim.sig_stage(stage)])
         n = a.sig_items
-        roomsim.simulate_signals(os.path.join(tmp, "warm"), "pretrain", 16, src, device="cuda:0", batch=16, log=lambda s: None)
+        roomsim.simulate_signals(os.path.join(tmp, "warm"), stage, 16, src, device="cuda:0", batch=16, log=lambda s: None, **kw)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        res = roomsim.simulate_signals(os.path.join(tmp, "a"), "pretrain", n, src, device="cuda:0", batch=16, log=lambda s: None)
+        res = roomsim.simulate_signals(os.path.join(tmp, "a"), stage, n, src, device="cuda:0", batch=16, log=lambda s: None, **kw)
         t_all = time.perf_counter() - t0
         walls = {}
         for mod, name in ((roomsim, "random_spatial_acoustics"), (roomsim, "plan_sig"), (rirsynth, "mixing_table"), (roomsim, "judge_on_device"),
@@ -146,7 +149,7 @@ def main():
             setattr(mod, name, walls[name])
         hip.profile_start(all_calls=True)
         t0 = time.perf_counter()
-        roomsim.simulate_signals(os.path.join(tmp, "b"), "pretrain", n, src, device="cuda:0", batch=16, log=lambda s: None)
+        roomsim.simulate_signals(os.path.join(tmp, "b"), stage, n, src, device="cuda:0", batch=16, log=lambda s: None, **kw)
         t_prof = time.perf_counter() - t0
         prof = hip.profile_stop()
         for mod, name in ((roomsim, "random_spatial_acoustics"), (roomsim, "plan_sig"), (rirsynth, "mixing_table"), (roomsim, "judge_on_device"),
@@ -171,7 +174,7 @@ def main():
                   ("tail + white noise (sarssl_gauss_fill)", gpu("sarssl_gauss_fill")),
                   ("labels (sarssl_rir_labels)", gpu("sarssl_rir_labels")),
                   ("diffuse field (sarssl_diffuse_noise)", gpu("sarssl_diffuse_noise")),
-                  ("mix (sarssl_rir_mix)", gpu("sarssl_rir_mix")),
+                  ("mix (%s)" % mix, gpu(mix)),
                   ("pack (sarssl_pcm16_pack)", gpu("sarssl_pcm16_pack")),
                   ("copy to the pinned buffer (measured apart, 16 items per copy)", t_copy)]
         host = [("room draws (random_spatial_acoustics, before the first batch)", walls["random_spatial_acoustics"].t / n * 1e3),
@@ -180,8 +183,8 @@ def main():
                 ("wait for the labels (judge_on_device, includes the render it waits for)", walls["judge_on_device"].t / n * 1e3),
                 ("file write, writer thread (write_wav_batch)", walls["write_wav_batch"].t / n * 1e3),
                 ("info files, writer thread (np.savez)", walls["savez"].t / n * 1e3)]
-        lines += ["--mode sig, stage pretrain idx 0..%d, batch 16, default ranges, T = 4.112 s (65 792 samples), device noise: %d written, %d skipped, "
-                  "%d renders" % (n - 1, nw, len(res["skipped"]), sum(res["attempts"].values())),
+        lines += ["--mode sig, stage %s%s idx 0..%d, batch 16, default ranges, T = 4.112 s (65 792 samples), device noise: %d written, %d skipped, "
+                  "%d renders" % (stage, " with save_dp" if a.save_dp else "", n - 1, nw, len(res["skipped"]), sum(res["attempts"].values())),
                   "whole call: %.2f s = %.1f items/s (%.1f ms per item; the room draws alone, measured above: %.1f ms per item)"
                   % (t_all, nw / t_all, 1e3 * t_all / nw, 1e3 * t_cfg),
                   "profiled pass (%.2f s; every C-ABI call between two events), ms per item:" % t_prof]

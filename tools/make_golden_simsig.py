@@ -51,7 +51,10 @@ def canned_rir(k, cfg):
     return h.astype(np.float32), dp.astype(np.float32)
 
 
-def main():
+def run_reference(save_dp=False):
+    """The reference's generate_microphone_signal(..., save_dp=save_dp) for the ITEMS items -> (F22's arrays, {file name: (the float
+    array handed to soundfile.write, fs)}).  The generation loop of F22, and of F24 (tools/make_golden_simsig_dp.py: save_dp=True, the
+    same draws)."""
     import ref_shim
     from sar_ssl_amd import roomsim
     f20._install_stubs()
@@ -135,7 +138,7 @@ def main():
             log.clear()
             del f20.READS[:]
             gen.generate_microphone_signal(idx=k, sa_cfgs=[dict(c) for c in cfgs], fs=FS, c=C, roomir=roomir, srcdataset=src, noidataset=noi,
-                                           snr_range=SNR_RANGE, save_to=out_dir, save_dp=False, gpu_conv=False, seed=SEED)
+                                           snr_range=SNR_RANGE, save_to=out_dir, save_dp=save_dp, gpu_conv=False, seed=SEED)
             sig, fs = written["%d.wav" % k]
             assert fs == FS and sig.shape == (NS, NMIC)
             pre = "item/%d/" % k
@@ -153,6 +156,12 @@ def main():
     store["consts"] = np.array([FS, NS, NMIC, SEED, ITEMS])
     store["T"], store["snr_range"], store["c"], store["ism_db"] = np.array(T), np.array(SNR_RANGE), np.array(C), np.array(ISM_DB)
     store["small_room_sz_range"], store["small_T60_range"] = np.array(SMALL["room_sz_range"]), np.array(SMALL["T60_range"])
+    os.listdir, ref_src.pad_cut_sig_samespk = listdir, pad_orig
+    return store, written
+
+
+def main():
+    store, _ = run_reference()
     out = os.path.join(GOLD, "f22_simsig.npz")
     np.savez_compressed(out, **store)
     print(out, os.path.getsize(out), "bytes")
