@@ -159,6 +159,24 @@ int sarssl_rir_labels(const float* rir, const int* n_len, const float* rir_dp, c
  *      is libsndfile's float -> PCM-16 rule with normalisation on AS THIS PROJECT READS IT: soundfile is not available to pin it against
  *      (UNPINNED).  The product is exact in f64, so the result is bit-equal to numpy's.  in 16-byte, out 8-byte aligned. */
 int sarssl_pcm16_pack(const float* in, long n, short* out, void* stream);
+/* ---- polyphase resampling of measured recordings (csrc/resample.hip): scipy.signal.resample_poly(x, up, down, axis=0) at its defaults
+ *      (window ('kaiser', 5.0), padtype 'constant') as code/data_generation/gen_real_rir.py:1052-1054, 1160-1161 calls it, every channel
+ *      of a file in one launch.  up / down are REDUCED by their gcd, half = 10 max(up, down), taps f32[ntaps = 2 half + 1] =
+ *      up firwin(ntaps, 1 / max(up, down), window=('kaiser', 5.0)) built by the caller in f64 (no window maths on the device),
+ *      n_out = ceil(n_in up / down) and
+ *        y[m][c] = sum over n in [0, n_in) with |m down - n up| <= half of x[n][c] taps[m down - n up + half].
+ *      x: interleaved rows [row0, row0 + nrows) of the (n_in, nch) signal, x pointing at row row0; in_dtype SARSSL_F32 or SARSSL_I16 (PCM-16,
+ *      scaled by 1 / 32768).  out: interleaved rows [m0, m1) of the (n_out, nch) result, out pointing at row m0; out_dtype SARSSL_F32 or
+ *      SARSSL_I16 (sarssl_pcm16_pack's rule on the f32 sum: rint(32767 y), ties to even, saturated to +-32767).  The rows present must
+ *      cover what [m0, m1) reads - a chunk carries a halo of ceil(half / up) rows on either side, clipped to the signal.
+ *      One f32 accumulator per output takes its terms in ascending n, one fmaf each; rows outside the signal are skipped.  The result
+ *      depends neither on nch (a column of a 32-channel call is bit-equal to that column alone) nor on the chunking nor on the tile.
+ *      realrir.restate_resample is this in f64 numpy, and the authority.  Refused (-1, nothing launched): nch outside 1..32, up or down
+ *      outside 1..441 or not reduced (sarssl_resample_poly_supported answers 0), ntaps != 2 half + 1, n_in or nrows <= 0,
+ *      n_out != ceil(n_in up / down), an empty or outlying [m0, m1), rows that do not cover it, any other dtype. */
+int sarssl_resample_poly_supported(int nch, int up, int down);
+int sarssl_resample_poly(const void* x, int in_dtype, long row0, long nrows, long n_in, int nch, int up, int down, const float* taps,
+                         int ntaps, long n_out, long m0, long m1, void* out, int out_dtype, void* stream);
 
 /* ---- generic batched MFMA GEMM with fused epilogue: nn.Linear / Conv1d(k=1) / patch conv / attention bmm
  *      (code/common/conformer/modules.py:35-48, feed_forward.py:47-54, attention.py:82-103, convolution.py:138,143,

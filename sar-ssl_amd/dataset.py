@@ -42,6 +42,55 @@ def read_wav_pcm16(path):
     return x[: (x.size // nch) * nch].reshape(-1, nch), fs
 
 
+_WAV_TAGS = {1: "PCM", 3: "IEEE float"}
+
+
+def read_wav(path, raw_pcm16=False):
+    """-> (float64 array (nsample, nch), fs) of a measured corpus's file, what soundfile.read returns: PCM-16 / 24 / 32 scaled by
+    2^-(bits-1) as libsndfile's float read does, IEEE float-32 widened; plain or WAVE_FORMAT_EXTENSIBLE.  raw_pcm16: a PCM-16 file
+    comes back as its int16 samples (half the upload; the kernels scale by 1 / 32768 themselves).  Any other format tag or width is
+    refused by name."""
+    with open(path, "rb") as f:
+        data = f.read()
+    if data[:4] != b"RIFF" or data[8:12] != b"WAVE":
+        raise ValueError("%s: not a RIFF/WAVE file" % path)
+    pos, fmt, raw = 12, None, None
+    while pos + 8 <= len(data):
+        cid, size = data[pos:pos + 4], struct.unpack("<I", data[pos + 4:pos + 8])[0]
+        body = data[pos + 8:pos + 8 + size]
+        if cid == b"fmt ":
+            if len(body) < 16:
+                raise ValueError("%s: fmt chunk of %d bytes, 16 at least" % (path, len(body)))
+            tag, nch, fs, _, _, bits = struct.unpack("<HHIIHH", body[:16])
+            if tag == 0xFFFE and len(body) >= 26:
+                tag = struct.unpack("<H", body[24:26])[0]
+            fmt = (tag, nch, fs, bits)
+        elif cid == b"data":
+            raw = body
+        pos += 8 + size + (size & 1)
+    if fmt is None or raw is None:
+        raise ValueError("%s: missing fmt/data chunk" % path)
+    tag, nch, fs, bits = fmt
+    if (tag, bits) not in ((1, 16), (1, 24), (1, 32), (3, 32)):
+        names = {6: "A-law", 7: "mu-law", 2: "MS ADPCM", 17: "IMA ADPCM", 0x55: "MPEG layer 3"}
+        raise ValueError("%s: %s, %d bits (format tag 0x%04x) is not read: PCM-16 / 24 / 32 and IEEE float-32 are"
+                         % (path, _WAV_TAGS.get(tag) or names.get(tag, "unknown format"), bits, tag))
+    nframe = len(raw) // (nch * (bits // 8))
+    raw = raw[:nframe * nch * (bits // 8)]
+    if tag == 3:
+        x = np.frombuffer(raw, dtype="<f4").astype(np.float64)
+    elif bits == 16:
+        x = np.frombuffer(raw, dtype="<i2")
+        x = x if raw_pcm16 else x.astype(np.float64) / 32768.0
+    elif bits == 32:
+        x = np.frombuffer(raw, dtype="<i4").astype(np.float64) / 2147483648.0
+    else:
+        b = np.zeros((len(raw) // 3, 4), np.uint8)                # the three bytes as the upper ones of an int32: sample * 256, sign kept
+        b[:, 1:] = np.frombuffer(raw, dtype=np.uint8).reshape(-1, 3)
+        x = b.view("<i4")[:, 0].astype(np.float64) / 2147483648.0
+    return x.reshape(-1, nch), fs
+
+
 def write_wav_pcm16(path, pcm, fs=16000):
     """pcm: int16 (nsample, nch)."""
     pcm = np.ascontiguousarray(pcm.astype("<i2"))

@@ -863,6 +863,70 @@ def pcm16_pack(x, out=None):
     return out
 
 
+# ---- polyphase resampling of measured recordings (csrc/resample.hip) ------------------------------------------------------------------
+def resample_ratio(up, down):
+    """(up, down) divided by their gcd: the ratio the kernel and the tap table are defined for."""
+    import math
+    up, down = int(up), int(down)
+    if up < 1 or down < 1:
+        raise _lib.SarsslHipError("resample_poly: up = %d, down = %d" % (up, down))
+    g = math.gcd(up, down)
+    return up // g, down // g
+
+
+def resample_taps(up, down):
+    """f64 (2 half + 1,) taps of scipy.signal.resample_poly's default filter for a REDUCED ratio: up firwin(2 half + 1,
+    1 / max(up, down), window=('kaiser', 5.0)), half = 10 max(up, down).  The ratio 1 : 1, where scipy returns a copy and firwin has
+    no cutoff to offer, gets the unit impulse."""
+    import numpy as np
+    import scipy.signal
+    mx = max(up, down)
+    if mx == 1:
+        return np.eye(1, 21, 10)[0]
+    return up * scipy.signal.firwin(2 * 10 * mx + 1, 1.0 / mx, window=("kaiser", 5.0))
+
+
+def resample_poly_supported(nch, up, down):
+    up, down = resample_ratio(up, down)
+    return bool(_lib.lib().sarssl_resample_poly_supported(c_int(nch), c_int(up), c_int(down)))
+
+
+RESAMPLE_TILE = 64           # outputs per workgroup (csrc/resample.hip RS_T): the tests put lengths on either side of it
+_resample_taps = {}          # (up, down, device) -> f32 device tensor
+
+
+def resample_poly(x, up, down, out_dtype=torch.float32, out=None, *, n_in=None, row0=0, m0=0, m1=None):
+    """scipy.signal.resample_poly(x, up, down, axis=0) at its defaults for x (n, nch) f32 or int16 (PCM-16, scaled by 1 / 32768) on the
+    GPU -> (n_out, nch) of ``out_dtype`` (f32, or int16 by roomsim.pcm16's rule), n_out = ceil(n up / down), nch <= 32, reduced up and
+    down <= 441.  Chunks: x holds rows [row0, row0 + len(x)) of a signal of ``n_in`` rows and the call forms outputs [m0, m1) ->
+    (m1 - m0, nch); with a halo of ceil(10 max(up, down) / up) rows (reduced ratio) the pieces are bit-equal to the one-shot result.  A refused shape raises and
+    leaves ``out`` untouched.  See include/sarssl_hip.h for the arithmetic (realrir.restate_resample is its f64 statement)."""
+    _need_cuda(x, out)
+    if x.dim() != 2 or x.dtype not in (torch.float32, torch.int16) or not x.is_contiguous():
+        raise _lib.SarsslHipError("resample_poly: x must be a contiguous (n, nch) f32 or int16 tensor")
+    if out_dtype not in (torch.float32, torch.int16):
+        raise _lib.SarsslHipError("resample_poly: out_dtype must be float32 or int16")
+    up, down = resample_ratio(up, down)
+    nrows, nch = x.shape
+    n_in = nrows if n_in is None else int(n_in)
+    n_out = -(-n_in * up // down)
+    m1 = n_out if m1 is None else int(m1)
+    if nrows == 0 or not resample_poly_supported(nch, up, down):
+        raise _lib.SarsslHipError("resample_poly: unsupported shape (n=%d, nch=%d, up=%d, down=%d): nch 1..32, reduced up and down 1..441, "
+                                  "no empty input" % (nrows, nch, up, down))
+    key = (up, down, x.device)
+    taps = _resample_taps.get(key)
+    if taps is None:
+        taps = _resample_taps[key] = torch.from_numpy(resample_taps(up, down).astype("float32")).to(x.device)
+    if out is None:
+        out = torch.empty((max(m1 - m0, 0), nch), dtype=out_dtype, device=x.device)
+    if out.shape != (m1 - m0, nch) or out.dtype != out_dtype or not out.is_contiguous():
+        raise _lib.SarsslHipError("resample_poly: out must be a contiguous (%d, %d) %s tensor (n_out mismatch)" % (m1 - m0, nch, out_dtype))
+    _lib.call("sarssl_resample_poly", _p(x), c_int(dt(x)), c_long(row0), c_long(nrows), c_long(n_in), c_int(nch), c_int(up), c_int(down),
+              _p(taps), c_int(taps.numel()), c_long(n_out), c_long(m0), c_long(m1), _p(out), c_int(_DT[out_dtype]), _stream())
+    return out
+
+
 # ------------------------------------------------------------------------------------------------
 # conv stem
 def _f32ws(n, device, tag):

@@ -99,6 +99,17 @@ SIMSIG = dict(pcm_step=1, share_bound=2 * RIRMIX["gate"] * 32767, measured=dict(
 #             (0: the f32 tables are bit-identical for every geometry of the test, so the test asserts equality)
 MIXTABLE = dict(cap=2.0 ** -22, measured=0.0, gate=0.0)
 
+# The polyphase resampler (csrc/resample.hip) against the f64 numpy restatement realrir.restate_resample on the input as the kernel reads
+# it: max |difference| of a case relative to the case's absolute peak (tests/test_gpu_resample.py).  Both sides use the same taps - the
+# kernel their f32 rounding - and the same order of the sum; they differ in the f32 products and the f32 accumulator.
+#   cap       a condition, not a measurement: half a PCM-16 step of full scale, as for RIRMIX
+#   ceiling   the gate may not exceed RIRMIX's, the gate of the same kind of f32 sum
+#   measured  on an MI355X over the test's cases (profiles/resample.txt, next to scipy's own float32 path on the same inputs)
+#   gate      about 5x the largest measured distance, one digit, never above the ceiling (5 x 4.3e-7 = 2.2e-6 -> 2e-6); the tolerance of
+#             a case is min(gate, ceiling, cap) x peak.  scipy's float32 path measures 2.1 - 4.3e-7 on the same inputs
+RESAMPLE = dict(cap=1.5e-5, ceiling=2e-6, measured=dict(kernel=4.3e-7, scipy_f32=4.3e-7, realrir_rir=1.6e-7, realrir_drr_db=2.6e-6,
+                                                         realrir_c50_db=1.7e-6), gate=2e-6)
+
 # The row / elementwise kernels (csrc/elementwise.hip, the row kernels of csrc/dwconv.hip, csrc/head.hip) against the f64 restatements of
 # tests/rowkernel_refs.py on the operands as stored: max |got - ref| / max |ref| (tests/test_gpu_rowkernels.py).  Keyed by kernel family,
 # then by the storage dtype of a forward kernel or the (gradient, saved activation) pairing of a backward kernel: f32, bf16, fp16,
