@@ -177,6 +177,17 @@ int sarssl_pcm16_pack(const float* in, long n, short* out, void* stream);
 int sarssl_resample_poly_supported(int nch, int up, int down);
 int sarssl_resample_poly(const void* x, int in_dtype, long row0, long nrows, long n_in, int nch, int up, int down, const float* taps,
                          int ntaps, long n_out, long m0, long m1, void* out, int out_dtype, void* stream);
+/*      The same for a batch of crops at ONE reduced ratio in one launch (realsig.RealMixLoader: the recordings of a training batch).
+ *      x: (nb, n_max, nch) interleaved, contiguous; n_in int[nb] ON THE DEVICE, the rows of item b that count (clamped to [0, n_max] by
+ *      the kernel; rows past n_in[b] are not read).  out: (nb, n_out_max = ceil(n_max up / down), nch); item b holds the result of
+ *      x[b][0 .. n_in[b]) in its first ceil(n_in[b] up / down) rows - BIT-EQUAL to sarssl_resample_poly of that item alone: one tile body
+ *      serves both launches, the batch index is the grid's y - and 0 in the rows behind.  The kernel writes every element of out;
+ *      nothing is cleared on the stream first.  Refused (-1, nothing launched, out untouched): nb outside 1..65535, the single-file
+ *      bounds on nch, up, down (sarssl_resample_poly_batch_supported answers 0), ntaps != 2 half + 1, n_max <= 0,
+ *      n_out_max != ceil(n_max up / down), any other dtype. */
+int sarssl_resample_poly_batch_supported(int nb, int nch, int up, int down);
+int sarssl_resample_poly_batch(const void* x, int in_dtype, const int* n_in, int nb, long n_max, int nch, int up, int down,
+                               const float* taps, int ntaps, long n_out_max, void* out, int out_dtype, void* stream);
 
 /* ---- generic batched MFMA GEMM with fused epilogue: nn.Linear / Conv1d(k=1) / patch conv / attention bmm
  *      (code/common/conformer/modules.py:35-48, feed_forward.py:47-54, attention.py:82-103, convolution.py:138,143,

@@ -22,6 +22,9 @@
 // them would double that - not built: the corpus this serves is recorded at 48 kHz).  Consecutive lanes take
 // consecutive channels of one output, so a 32-lane group reads 32 consecutive LDS words (nch = 32) and one tap (a broadcast); the
 // sub-filter an output uses is the phase (m down + half) mod up, reached as the tap index m down - n up + half stepping down by `up`.
+//
+// sarssl_resample_poly_batch is the same tile body over B crops of a training batch in one launch (realsig.RealMixLoader: B recordings cut
+// at random, each at most a few seconds): the batch index is the grid's y and changes no arithmetic, the crop lengths are read on the device.
 #include "common.h"
 
 #define RS_T 64                     // outputs per workgroup
@@ -50,18 +53,17 @@ __device__ __host__ __forceinline__ long rs_last(long m, int up, int down, int h
     return b < n_in - 1 ? b : n_in - 1;
 }
 
+// Outputs [mt0, mt1) (at most RS_T of them) of a signal of n_in rows whose row row0 is x[0], written to out[0 ...]: the one body of the
+// single-file and of the batched launch, so that an item of a batch cannot differ from the same signal resampled alone.
 template <typename TI, typename TO>
-__global__ __launch_bounds__(RS_THREADS) void resample_poly_kernel(const TI* __restrict__ x, long row0, long n_in, int nch, int up, int down,
-                                                                    int half, const float* __restrict__ taps, long m0, long m1,
-                                                                    TO* __restrict__ out) {
+__device__ __forceinline__ void rs_tile(const TI* __restrict__ x, long row0, long n_in, int nch, int up, int down, int half,
+                                        const float* __restrict__ taps, long mt0, long mt1, TO* __restrict__ out) {
     extern __shared__ float rs_lds[];
     const int ntaps = 2 * half + 1;
     float* accs = rs_lds;                                   // [RS_T * RS_MAXCH]
     float* xs = accs + RS_T * RS_MAXCH;                     // [RS_STAGE]
     float* hs = xs + RS_STAGE;                              // [ntaps]
     const int tid = threadIdx.x;
-    const long mt0 = m0 + (long)blockIdx.x * RS_T;
-    const long mt1 = mt0 + RS_T < m1 ? mt0 + RS_T : m1;
     const int nitem = (int)(mt1 - mt0) * nch;
     for (int i = tid; i < ntaps; i += RS_THREADS) hs[i] = taps[i];
     for (int it = tid; it < nitem; it += RS_THREADS) accs[it] = 0.f;
@@ -97,7 +99,37 @@ __global__ __launch_bounds__(RS_THREADS) void resample_poly_kernel(const TI* __r
         }
     }
     __syncthreads();
-    for (int it = tid; it < nitem; it += RS_THREADS) rs_store(out, (mt0 - m0) * nch + it, accs[it]);
+    for (int it = tid; it < nitem; it += RS_THREADS) rs_store(out, it, accs[it]);
+}
+
+template <typename TI, typename TO>
+__global__ __launch_bounds__(RS_THREADS) void resample_poly_kernel(const TI* __restrict__ x, long row0, long n_in, int nch, int up, int down,
+                                                                    int half, const float* __restrict__ taps, long m0, long m1,
+                                                                    TO* __restrict__ out) {
+    const long mt0 = m0 + (long)blockIdx.x * RS_T;
+    const long mt1 = mt0 + RS_T < m1 ? mt0 + RS_T : m1;
+    rs_tile(x, row0, n_in, nch, up, down, half, taps, mt0, mt1, out + (mt0 - m0) * nch);
+}
+
+// A batch of crops, one ratio: blockIdx.y is the item, blockIdx.x the tile of its (n_out_max, nch) slot.  Item b is n_in[b] rows (clamped to
+// [0, n_max]: the lengths live on the device, nothing on the host has seen them) at x + b n_max nch; its ceil(n_in[b] up / down) outputs
+// are rs_tile's, the rows of the slot behind them are written as zeros by the workgroup that owns their tile - the slot is never cleared.
+template <typename TI, typename TO>
+__global__ __launch_bounds__(RS_THREADS) void resample_poly_batch_kernel(const TI* __restrict__ x, const int* __restrict__ n_in, long n_max,
+                                                                          int nch, int up, int down, int half,
+                                                                          const float* __restrict__ taps, long n_out_max,
+                                                                          TO* __restrict__ out) {
+    const long b = blockIdx.y;
+    long n = n_in[b];
+    n = n < 0 ? 0 : (n > n_max ? n_max : n);
+    const long n_out = (n * up + down - 1) / down;          // <= n_out_max, as n <= n_max
+    const long mt0 = (long)blockIdx.x * RS_T;
+    const long me = mt0 + RS_T < n_out_max ? mt0 + RS_T : n_out_max;        // the tile's end in the slot
+    const long mt1 = me < n_out ? me : n_out;                               // ... and in the item
+    TO* o = out + (b * n_out_max + mt0) * nch;
+    if (mt0 < mt1) rs_tile(x + b * n_max * nch, 0, n, nch, up, down, half, taps, mt0, mt1, o);      // (uniform over the workgroup)
+    const int z0 = mt0 < mt1 ? (int)(mt1 - mt0) * nch : 0, z1 = (int)(me - mt0) * nch;
+    for (int it = z0 + (int)threadIdx.x; it < z1; it += RS_THREADS) rs_store(o, it, 0.f);
 }
 
 static bool rs_ratio_ok(int nch, int up, int down) {
@@ -137,5 +169,38 @@ extern "C" int sarssl_resample_poly(const void* x, int in_dtype, long row0, long
     else
         resample_poly_kernel<short, short><<<grid, RS_THREADS, lds, st>>>((const short*)x, row0, n_in, nch, up, down, half, taps, m0, m1, (short*)out);
     SARSSL_CHECK_LAUNCH("resample_poly_kernel");
+    return 0;
+}
+
+// 1: sarssl_resample_poly_batch takes this (nb, nch, up, down); 0: it refuses (the single-file bounds, or nb outside 1..65535 = the grid's y)
+extern "C" int sarssl_resample_poly_batch_supported(int nb, int nch, int up, int down) {
+    return nb >= 1 && nb <= 65535 && rs_ratio_ok(nch, up, down) ? 1 : 0;
+}
+
+extern "C" int sarssl_resample_poly_batch(const void* x, int in_dtype, const int* n_in, int nb, long n_max, int nch, int up, int down,
+                                          const float* taps, int ntaps, long n_out_max, void* out, int out_dtype, void* stream) {
+    SARSSL_REQUIRE(x && n_in && taps && out, "sarssl_resample_poly_batch");
+    SARSSL_REQUIRE(nb >= 1 && nb <= 65535, "sarssl_resample_poly_batch(1..65535 items)");
+    SARSSL_REQUIRE(rs_ratio_ok(nch, up, down), "sarssl_resample_poly_batch(nch 1..32, up and down 1..441 and reduced by their gcd)");
+    SARSSL_REQUIRE((in_dtype == SARSSL_F32 || in_dtype == SARSSL_I16) && (out_dtype == SARSSL_F32 || out_dtype == SARSSL_I16),
+                   "sarssl_resample_poly_batch(f32 or PCM-16 in and out)");
+    SARSSL_REQUIRE(n_max > 0 && n_max <= (1L << 40), "sarssl_resample_poly_batch(empty input)");
+    const int half = 10 * (up > down ? up : down);
+    SARSSL_REQUIRE(ntaps == 2 * half + 1, "sarssl_resample_poly_batch(2 * 10 max(up, down) + 1 taps)");
+    SARSSL_REQUIRE(n_out_max == (n_max * up + down - 1) / down, "sarssl_resample_poly_batch(n_out_max = ceil(n_max up / down))");
+    const long nblk = (n_out_max + RS_T - 1) / RS_T;
+    SARSSL_REQUIRE(nblk <= 0x7fffffffl, "sarssl_resample_poly_batch");
+    const size_t lds = (size_t)(RS_T * RS_MAXCH + RS_STAGE + ntaps) * sizeof(float);
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)nblk, (unsigned)nb);
+    if (in_dtype == SARSSL_F32 && out_dtype == SARSSL_F32)
+        resample_poly_batch_kernel<float, float><<<grid, RS_THREADS, lds, st>>>((const float*)x, n_in, n_max, nch, up, down, half, taps, n_out_max, (float*)out);
+    else if (in_dtype == SARSSL_F32)
+        resample_poly_batch_kernel<float, short><<<grid, RS_THREADS, lds, st>>>((const float*)x, n_in, n_max, nch, up, down, half, taps, n_out_max, (short*)out);
+    else if (out_dtype == SARSSL_F32)
+        resample_poly_batch_kernel<short, float><<<grid, RS_THREADS, lds, st>>>((const short*)x, n_in, n_max, nch, up, down, half, taps, n_out_max, (float*)out);
+    else
+        resample_poly_batch_kernel<short, short><<<grid, RS_THREADS, lds, st>>>((const short*)x, n_in, n_max, nch, up, down, half, taps, n_out_max, (short*)out);
+    SARSSL_CHECK_LAUNCH("resample_poly_batch_kernel");
     return 0;
 }

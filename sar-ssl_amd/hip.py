@@ -927,6 +927,42 @@ def resample_poly(x, up, down, out_dtype=torch.float32, out=None, *, n_in=None, 
     return out
 
 
+def resample_poly_batch_supported(nb, nch, up, down):
+    up, down = resample_ratio(up, down)
+    return bool(_lib.lib().sarssl_resample_poly_batch_supported(c_int(nb), c_int(nch), c_int(up), c_int(down)))
+
+
+def resample_poly_batch(x, n_in, up, down, out_dtype=torch.float32, out=None):
+    """A batch of crops at one ratio in one launch: x (B, n_max, nch) f32 or int16 (PCM-16, scaled by 1 / 32768), n_in int32 (B,) on the
+    device (rows past n_in[b] are not read) -> (B, ceil(n_max up / down), nch) of ``out_dtype``.  Item b holds resample_poly(x[b, :n_in[b]],
+    up, down) in its first ceil(n_in[b] up / down) rows, bit for bit, and 0 behind them; every element of ``out`` is written by the kernel.
+    B <= 65535 and resample_poly's bounds; a refused shape raises and leaves ``out`` untouched."""
+    _need_cuda(x, n_in, out)
+    if x.dim() != 3 or x.dtype not in (torch.float32, torch.int16) or not x.is_contiguous():
+        raise _lib.SarsslHipError("resample_poly_batch: x must be a contiguous (B, n_max, nch) f32 or int16 tensor")
+    if out_dtype not in (torch.float32, torch.int16):
+        raise _lib.SarsslHipError("resample_poly_batch: out_dtype must be float32 or int16")
+    B, n_max, nch = x.shape
+    if n_in.dtype != torch.int32 or n_in.shape != (B,) or not n_in.is_contiguous():
+        raise _lib.SarsslHipError("resample_poly_batch: n_in must be a contiguous int32 (%d,) tensor" % B)
+    up, down = resample_ratio(up, down)
+    if n_max == 0 or not resample_poly_batch_supported(B, nch, up, down):
+        raise _lib.SarsslHipError("resample_poly_batch: unsupported shape (B=%d, n_max=%d, nch=%d, up=%d, down=%d): B 1..65535, nch 1..32, "
+                                  "reduced up and down 1..441, no empty input" % (B, n_max, nch, up, down))
+    n_out = -(-n_max * up // down)
+    key = (up, down, x.device)
+    taps = _resample_taps.get(key)
+    if taps is None:
+        taps = _resample_taps[key] = torch.from_numpy(resample_taps(up, down).astype("float32")).to(x.device)
+    if out is None:
+        out = torch.empty((B, n_out, nch), dtype=out_dtype, device=x.device)
+    if out.shape != (B, n_out, nch) or out.dtype != out_dtype or not out.is_contiguous():
+        raise _lib.SarsslHipError("resample_poly_batch: out must be a contiguous (%d, %d, %d) %s tensor" % (B, n_out, nch, out_dtype))
+    _lib.call("sarssl_resample_poly_batch", _p(x), c_int(dt(x)), _p(n_in), c_int(B), c_long(n_max), c_int(nch), c_int(up), c_int(down),
+              _p(taps), c_int(taps.numel()), c_long(n_out), _p(out), c_int(_DT[out_dtype]), _stream())
+    return out
+
+
 # ------------------------------------------------------------------------------------------------
 # conv stem
 def _f32ws(n, device, tag):

@@ -14,6 +14,7 @@ class opt_pretrain():
         self.work_dir = os.path.abspath(os.path.expanduser(r"~"))
         self.work_dir_local = self.work_dir
         self.acoustic_setting = {"sound_speed": 343.0, "fs": 16000, "T": 4.112, "nmic": 2, "mic_dist_range": [0.03, 0.20]}
+        self.simu_exp = False
 
     def parse(self, argv=None):
         p = argparse.ArgumentParser(description="Self-supervised learing for multi-channel audio processing")
@@ -38,11 +39,15 @@ class opt_pretrain():
         p.add_argument("--lr", type=float, default=0.001, metavar="LR", help="learning rate (default:0.001)")
         p.add_argument("--test", action="store_true", default=False, help="change to test stage")
         p.add_argument("--test-mode", type=str, default="all", metavar="TestMode", help="test mode (default: all)")
+        p.add_argument("--data-num", type=int, nargs=2, default=None, metavar=("Train", "Val"),
+                       help="items per epoch and per validation of real-data pretraining (build-side override for a short run; "
+                            "default: the reference's 512000 and 8000)")
         args = p.parse_args(argv)
         assert (args.pretrain + args.pretrain_frozen_encoder + args.test) == 1, "Pretraining stage (pretrain or test) is undefined"
         assert args.test_mode in ["all", "ins"], "Test mode is undefined"
         self.time, self.work_dir = args.time, os.path.abspath(os.path.expanduser(args.work_dir))
         self.work_dir_local = self.work_dir
+        self.simu_exp = bool(args.simu_exp)
         args.acoustic_setting = self.acoustic_setting
         return args
 
@@ -54,6 +59,16 @@ class opt_pretrain():
         dirs["micsig_simu_preval"] = dirs["gerdata"] + "/MicSig/simu/preval"
         dirs["micsig_simu_pretest"] = dirs["gerdata"] + "/MicSig/simu/pretest"
         dirs["micsig_simu_pretest_ins"] = [dirs["gerdata"] + "/MicSig/simu/pretest_ins_T1000"]
+        if not self.simu_exp:                                                                    # code/opt.py:82-109
+            real, rec = dirs["gerdata"] + "/MicSig/real/", dirs["data"] + "/MicSig/"
+            recordings = {"LOCATA": rec + "LOCATA", "MCWSJ": rec + "MC_WSJ_AV", "LibriCSS": rec + "LibriCSS", "AMI": rec + "AMI",
+                          "AISHELL4": rec + "AISHELL-4", "M2MeT": rec + "M2MeT", "RealMAN": rec + "RealMAN",
+                          "RealMANOri": rec + "aligned_static_high_\u7cbe\u7ec6\u5bf9\u9f50_correctDPRIR_filtered3"}
+            dirs["micsig_real_pretrain"] = {n: real + "pretrain/" + n for n in ("DCASE", "MIR", "Mesh", "BUTReverb", "dEchorate", "ACE")}
+            dirs["micsig_real_pretrain"].update(recordings)
+            dirs["micsig_real_preval"] = {n: real + "preval/" + n for n in ("DCASE", "BUTReverb")}
+            dirs["micsig_real_preval"].update({n: recordings[n] for n in ("AISHELL4", "M2MeT", "RealMAN", "RealMANOri")})
+            dirs["micsig_real_pretest"] = {"ACE": real + "pretrain/ACE", "LOCATA": recordings["LOCATA"]}
         dirs["log_pretrain"] = dirs["exp"] + "/pretrain/" + self.time
         dirs["log_pretrain_frozen_encoder"] = dirs["exp"] + "/pretrain_frozen_encoder/" + self.time            # code/opt.py:113
         return dirs

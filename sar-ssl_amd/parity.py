@@ -55,9 +55,11 @@ GATES = {
 # The stored direct-path signal (sarssl_rir_mix_dp's out_dp, tests/test_gpu_simsig_dp.py) is held to the same gate as out - the same
 # transforms over fewer partitions - and restate_sig(with_dp=True) against fixture F24 of the real reference to restatement_vs_f20 - the
 # same two fftconvolve calls (tests/test_simsig_dp_cpu.py); rir_mix_dp and restatement_dp_vs_f24 record what those tests measure.
+# realsig.restate_item (the measured variant at gain 0.9, the generator of gen_sig_from_real_rir.py) is held to restatement_vs_f20 against
+# fixture F26 of the real reference's MicSigFromRIRDataset (tests/test_realsig_cpu.py); restatement_vs_f26 records what it measures.
 RIRMIX = dict(gate=2e-6, cap=1.5e-5, restatement_vs_f20=8e-7,
               measured=dict(rir_mix=2.8e-7, diffuse_noise=2.9e-7, loader=3.1e-7, restatement_vs_f20=1.9e-7, rir_mix_dp=2.7e-7,
-                            restatement_dp_vs_f24=7.5e-9))
+                            restatement_dp_vs_f24=7.5e-9, restatement_vs_f26=1.5e-7))
 
 
 # The image-source renderer (csrc/ism.hip) against the f64 numpy restatement roomsim.restate_ism: max |difference| over an RIR relative to

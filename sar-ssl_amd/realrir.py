@@ -308,7 +308,7 @@ def main(argv=None):
     a = ap.parse_args(argv)
     for name in a.dataset:
         if name in UNBUILT:
-            ap.error("--dataset %s: only ACE is built; DCASE, Mesh, MIR, dEchorate and BUTReverb feed real-data pretraining, which is not" % name)
+            ap.error("--dataset %s: only ACE is built; the banks of DCASE, Mesh, MIR, dEchorate and BUTReverb that gen_sig_from_real_rir.py reads come from the reference's gen_real_rir.py" % name)
         if name != "ACE":
             ap.error("--dataset %s: dataset not found" % name)
     for t in a.data_type:

@@ -5,6 +5,9 @@
     python run_pretrain.py --pretrain --simu-exp --gpu-id 0,1,2,3,4,5,6,7 [--use-amp]       # eight GPUs, the reference's own form
     torchrun --nproc-per-node 8 run_pretrain.py --pretrain --simu-exp --gpu-id 0,1,2,3,4,5,6,7 [--use-amp]     # same thing
 
+``--pretrain`` without ``--simu-exp`` is the reference's real-data branch (code/run_pretrain.py:117-199): realsig.RealMixLoader over the
+corpora of the reference's list that are built here (LOCATA recordings and the six measured-RIR corpora of gen_sig_from_real_rir.py) and
+present on disk, one GPU, the reference's fixed learning rate 1e-4 (:247), validation key ``loss_val_real``.
 The ``--simu-exp`` branches (fixed pre-generated simulated segments) are implemented: ``--pretrain`` - the path BASELINE.json names -,
 ``--test`` and ``--pretrain-frozen-encoder`` (code/run_pretrain.py:315-402: the encoders of the pretraining run's best checkpoint, frozen,
 under a fresh decoder that learns to reconstruct the masked channel; launch by launch on one GPU).  Multi-GPU = one process per GPU over RCCL, not DataParallel (code/learner.py:25-31): with more than one id in ``--gpu-id``
@@ -32,6 +35,11 @@ def main(argv=None):
     if frozen and (len(gpu_ids) > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1):
         raise SystemExit("--pretrain-frozen-encoder runs on one GPU (its step has no data-parallel form): give --gpu-id a single id, "
                          "e.g. `--gpu-id 0,`")
+    real = bool(args.pretrain) and not args.simu_exp
+    if real and (len(gpu_ids) > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1):
+        raise SystemExit("--pretrain without --simu-exp (real data) runs on one GPU (its loader has no data-parallel form): give --gpu-id "
+                         "a single id, e.g. `--gpu-id 0,`")
+    mixes = real_mixes(args, dirs) if real else None             # host only: an empty corpus list ends the run before the GPU is touched
     if not launch.launched():
         if len(gpu_ids) > 1 and not args.no_cuda and not args.test:
             # one rank per listed GPU; this process only waits for them (it has not initialised HIP and never will)
@@ -45,7 +53,7 @@ def main(argv=None):
 
     if args.no_cuda or not torch.cuda.is_available():
         raise SystemExit("run_pretrain.py (sar_ssl_amd) needs an MI355X GPU: the HIP path has no CPU fallback")
-    if not (args.pretrain or args.test or frozen) or not args.simu_exp:
+    if not (args.pretrain or args.test or frozen) or not (args.simu_exp or real):
         raise SystemExit("only `--pretrain --simu-exp`, `--pretrain-frozen-encoder --simu-exp` and `--test --simu-exp` are implemented on this path")
     rank, world, local = sdist.init_from_env()
     device = torch.device("cuda", local)
@@ -71,7 +79,14 @@ def main(argv=None):
     data_num = {"train": 5120 * 100, "val": 4000 * 2}
     native = os.environ.get("SARSSL_NATIVE_LOADER", "1") != "0"
     sampler = None
-    if native:
+    if real:
+        from sar_ssl_amd import realsig
+        num = args.data_num or [data_num["train"], data_num["val"]]
+        (_, c_train, w_train, _), (_, c_val, w_val, _) = mixes
+        dl_train = realsig.RealMixLoader(c_train, w_train, num[0], args.bs[0], T, fs, 2, device=device, nthreads=max(1, args.workers))
+        dl_val = realsig.RealMixLoader(c_val, w_val, num[1], args.bs[1], T, fs, 2, device=device, nthreads=max(1, args.workers))
+        native = False
+    elif native:
         # threaded int16 reader -> pinned buffers -> copy stream (dataset.PcmSegmentLoader); same file listing, same
         # rank-strided shuffling as DataLoader + DistributedSampler below
         nsample = int(T * fs)
@@ -115,7 +130,7 @@ def main(argv=None):
                                                 linear_end=1e-6)
     log = open(os.path.join(log_dir, "scalars.jsonl"), "a") if rank == 0 else None
     for epoch in range(learner.start_epoch, args.nepoch + 1):
-        lr = float(lr_schedule(epoch))
+        lr = 0.0001 if real else float(lr_schedule(epoch))                                 # code/run_pretrain.py:244-247
         set_random_seed(seeds["train"] + epoch + 1000003 * rank)                              # per-rank mask / dropout streams
         if sampler is not None:
             sampler.set_epoch(epoch)
@@ -134,14 +149,30 @@ def main(argv=None):
             stop_flag, is_best = learner.early_stopping(current_score=-loss_val, patience=100)
         learner.save_checkpoint(epoch=epoch, checkpoints_dir=log_dir, is_best_epoch=is_best, save_extra_hist=not frozen)
         if rank == 0:
-            rec = {"epoch": epoch, "lr": lr, "loss_train": loss_train, "diff_train": diff_train, "loss_val": loss_val,
-                   "diff_val": diff_val, "nparam_M": nparam_sum}
+            rec = {"epoch": epoch, "lr": lr, "loss_train": loss_train, "diff_train": diff_train,
+                   "loss_val_real" if real else "loss_val": loss_val, "diff_val_real" if real else "diff_val": diff_val, "nparam_M": nparam_sum}
             print(json.dumps(rec), flush=True)
             log.write(json.dumps(rec) + "\n"); log.flush()
         if stop_flag:
             break
     if rank == 0:
         print("\nFrozen Pre-Training finished\n" if frozen else "\nPre-Training finished\n")
+
+
+def real_mixes(args, dirs):
+    """The train and the validation mix of the real branch (realsig.build_mix over the reference's two lists), or SystemExit naming the
+    directories that were looked for and the commands that write them.  Host only."""
+    from sar_ssl_amd import realsig
+    fs, T = args.acoustic_setting["fs"], args.acoustic_setting["T"]
+    rng, nmic = args.acoustic_setting["mic_dist_range"], args.acoustic_setting["nmic"]
+    out = []
+    for stage, names, probs, key in (("train", realsig.TRAIN_LIST, realsig.TRAIN_PROBS, "micsig_real_pretrain"),
+                                     ("val", realsig.VAL_LIST, realsig.VAL_PROBS, "micsig_real_preval")):
+        mix = realsig.build_mix(names, probs, dirs[key], stage, T, fs, rng, nmic, log=print)
+        if not mix[0]:
+            raise SystemExit(realsig.missing_message(stage, names, dirs[key]))
+        out.append(mix)
+    return out
 
 
 def run_test(args, dirs, net, device, fs, stft_cfg):
