@@ -9,12 +9,12 @@ batches (hip.rir_mix / diffuse_noise / gauss_fill, csrc/rirmix.hip; ``mix_simula
 """
 import math
 import os
-import queue
-import threading
 import warnings
 from pathlib import Path
 
 import numpy as np
+
+from .pipeline import EpochLoader
 
 FS = 16000
 DP_TIME_MS = 2.5                 # gen_sig_from_real_rir.py:231
@@ -347,26 +347,23 @@ def mix_simulated(src, rir, rir_len, dp, dp_len, white, C, snr, gain, out=None, 
     return hip.rir_mix(src, rir, rir_len, snr, gain, rir_dp=dp, dp_len=dp_len, noise=field, out=out, out_dp=out_dp)
 
 
-class RirSynthLoader:
+class RirSynthLoader(EpochLoader):
     """Batches of RandomMicSigFromRIRDataset items, rendered on the GPU: yields ``(mic_sig (B, Ns, nch) f32 on the device,
     {task: (B,) f32 tensor})`` in the shape Learner.train_epoch / test_epoch iterate.
 
-    A producer thread plans the items (one host stream, the reference's order with num_workers=0, continued from numpy's global state
-    at the start of each iteration - the epoch's set_random_seed) and reads sources and noise segments; the consumer enqueues the render of
-    batch i + 1 on a side stream before it hands out batch i.  noise="numpy": the simulated variant's white noise is the reference's host
-    draw (parity); noise="device" (default): sarssl_gauss_fill keyed by (seed, running item index) - not numpy's stream, and the SNR draw
-    then follows the source crop directly."""
+    pipeline.EpochLoader's producer thread plans the items (``plan_item``: the reference's draws on the epoch's one host stream) and reads
+    sources and noise segments; the consumer enqueues the render of batch i + 1 on a side stream before it hands out batch i.
+    noise="numpy": the simulated variant's white noise is the reference's host draw (parity); noise="device" (default):
+    sarssl_gauss_fill keyed by (seed, running item index) - not numpy's stream, and the SNR draw then follows the source crop directly."""
 
     def __init__(self, measured, simulated, sources, dataset_sz, batch_size, T, fs=FS, nmic=2, snr_range=(15, 30), real_sim_ratio=(1, 0),
                  seed=1, noise="device", device="cuda", c=343.0, drop_last=False, prefetch=2):
-        import torch
         assert noise in ("numpy", "device")
+        super().__init__(dataset_sz, batch_size, device, drop_last, prefetch)
         self.variants = variants_of(real_sim_ratio)
         assert ("measured" not in self.variants or measured is not None) and ("simulated" not in self.variants or simulated is not None)
         self.measured, self.simulated, self.sources = measured, simulated, sources
-        self.dataset_sz, self.batch_size, self.T, self.fs, self.nmic = int(dataset_sz), int(batch_size), T, fs, nmic
-        self.snr_range, self.seed, self.noise, self.drop_last, self.prefetch = tuple(snr_range), seed, noise, drop_last, max(1, prefetch)
-        self.device = torch.device(device)
+        self.T, self.fs, self.nmic, self.snr_range, self.seed, self.noise = T, fs, nmic, tuple(snr_range), seed, noise
         self.nsample = int(T * fs)
         for bank in (measured, simulated):
             if bank is not None:
@@ -374,22 +371,13 @@ class RirSynthLoader:
                     raise ValueError("RIRs with %d channels, nmic = %d" % (bank.nch, nmic))
                 if not hasattr(bank, "dev_rir") or bank.dev_rir.device != self.device:
                     bank.to_device(self.device)
-        self.side = torch.cuda.Stream(self.device) if self.device.type == "cuda" else None
 
-    def __len__(self):
-        n = self.dataset_sz // self.batch_size
-        return n if self.drop_last or self.dataset_sz % self.batch_size == 0 else n + 1
+    def plan_item(self, rs):
+        return plan_random(rs, self.variants, self.seed, self.measured, self.simulated, self.sources, self.T, self.fs, self.snr_range,
+                           self.nmic, draw_white=self.noise == "numpy")
 
-    def plan_batches(self):
-        """Generator of the epoch's plans, batch by batch (host only)."""
-        rs = np.random.RandomState()
-        rs.set_state(np.random.get_state())
-        left = self.dataset_sz
-        for _ in range(len(self)):
-            n = min(self.batch_size, left)
-            left -= n
-            yield [plan_random(rs, self.variants, self.seed, self.measured, self.simulated, self.sources, self.T, self.fs, self.snr_range,
-                               self.nmic, draw_white=self.noise == "numpy") for _ in range(n)]
+    def handout(self, res):
+        return res, [res[0]] + list(res[1].values())
 
     def host_batch(self, plans):
         """Pinned host tensors of one batch: what the render uploads.  Filled through their numpy views (no torch op runs on the host)."""
@@ -463,58 +451,3 @@ class RirSynthLoader:
                 out.index_copy_(0, sel, dst)
         labels = {k: v.to(dev, non_blocking=True) for k, v in h["labels"].items()}
         return out, labels
-
-    def __iter__(self):
-        import torch
-        ready = queue.Queue(maxsize=self.prefetch)
-        stop = threading.Event()
-
-        def producer():
-            try:
-                for plans in self.plan_batches():
-                    if stop.is_set():
-                        return
-                    ready.put(self.host_batch(plans))
-                ready.put(None)
-            except BaseException as e:                       # surface planning / reader errors in the consumer
-                ready.put(e)
-
-        th = threading.Thread(target=producer, daemon=True)
-        th.start()
-        cuda = self.side is not None
-        try:
-            prev, i = None, 0
-            while True:
-                h = ready.get()
-                if isinstance(h, BaseException):
-                    raise h
-                cur = None
-                if h is not None:
-                    if cuda:
-                        with torch.cuda.stream(self.side):
-                            res = self.render(h, item0=i * self.batch_size)
-                            ev = torch.cuda.Event()
-                            ev.record(self.side)
-                        cur = (res, ev)
-                    else:
-                        cur = (self.render(h, item0=i * self.batch_size), None)
-                    i += 1
-                if prev is not None:
-                    (sig, labels), ev = prev
-                    if ev is not None:
-                        st = torch.cuda.current_stream(self.device)
-                        st.wait_event(ev)
-                        for t in [sig] + list(labels.values()):
-                            t.record_stream(st)
-                    yield sig, labels
-                prev = cur
-                if h is None:
-                    break
-        finally:
-            stop.set()
-            while th.is_alive():
-                try:
-                    ready.get(timeout=0.05)
-                except queue.Empty:
-                    pass
-            th.join()

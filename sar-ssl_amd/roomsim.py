@@ -767,13 +767,13 @@ def _signals(who, out_dir, stage, cfgs, seed, args, sources, stem, device, noise
     while the GPU renders, uploaded with the source; "device": hip.mixing_table of the batch's uploaded microphone positions.
     noise_type="spatial_white": the white noise goes into hip.rir_mix as it is (no field, no division by its maximum).
     recorded: what all_info.npz's args hold beside the ranges, T and snr_range.  save_dp: the mix also stores the direct-path signal
-    (hip.rir_mix's out_dp); it is packed and copied with the microphone signal - the pinned buffers take both, the batch's signals and
-    then their direct paths - and written as ``stem(idx)`` + _dp.wav in the same write_wav_batch call; all_info.npz's args then hold
+    (hip.rir_mix's out_dp); it is packed and copied with the microphone signal - pipeline.StagedWriter's buffers take both, the batch's
+    signals and then their direct paths - and written as ``stem(idx)`` + _dp.wav in the same write_wav_batch call; all_info.npz's args then hold
     save_dp=True."""
     import torch
-    from concurrent.futures import ThreadPoolExecutor
     from . import hip, rirsynth
     from .dataset import write_wav_batch
+    from .pipeline import StagedWriter, src_snr_rows
     assert table in ("host", "device") and noise_type in NOISE_TYPES
     fs, c = args["fs"], args["c"]
     ns = sig_samples(T, fs)
@@ -783,9 +783,7 @@ def _signals(who, out_dir, stage, cfgs, seed, args, sources, stem, device, noise
     dev = torch.device(device)
     side = torch.cuda.Stream(dev)
     nsig = 2 if save_dp else 1                                # signals per item: the microphones', then the direct path's
-    pinned = [torch.empty((nsig, batch, ns, nmic), dtype=torch.int16, pin_memory=True) for _ in range(2)]
-    busy = [None, None]                                       # the writer job that still reads each pinned buffer
-    sig_plans, nbatch = {}, 0
+    sig_plans = {}
 
     def prepare(ids):                                         # (host work while the GPU renders)
         for idx in ids:
@@ -795,8 +793,7 @@ def _signals(who, out_dir, stage, cfgs, seed, args, sources, stem, device, noise
                     p["C"] = rirsynth.mixing_table(cfgs[idx]["mic_pos"], fs, c).astype(np.float32)
                 sig_plans[idx] = p
 
-    def write(ev, buf, ids, infos):
-        ev.synchronize()
+    def write(buf, ids, infos):
         paths = [stem(i) + ".wav" for i in ids]
         if save_dp:
             paths += [stem(i) + "_dp.wav" for i in ids]
@@ -805,19 +802,12 @@ def _signals(who, out_dir, stage, cfgs, seed, args, sources, stem, device, noise
             np.savez(stem(i) + "_info.npz", **info)
 
     def sink(b, acc, lab):
-        nonlocal nbatch
         A, aids = len(acc), [b.ids[j] for j in acc]
         rir_dev, dp_dev = b.rir, b.dp
         if A < len(b.ids):
             sel = torch.tensor(acc, device=dev)
             rir_dev, dp_dev = rir_dev.index_select(0, sel), dp_dev.index_select(0, sel)
-        host = torch.empty((A, ns + 1 + ntab), dtype=torch.float32, pin_memory=True)                   # src | snr | C of each item
-        hn = host.numpy()
-        for j, i in enumerate(aids):
-            hn[j, :ns], hn[j, ns] = sig_plans[i]["src"], sig_plans[i]["snr"]
-            if ntab:
-                hn[j, ns + 1:] = sig_plans[i]["C"].reshape(-1)
-        up = host.to(dev, non_blocking=True)
+        up = src_snr_rows([sig_plans[i] for i in aids], ns, ntab).to(dev, non_blocking=True)           # src | snr | C of each item
         if noise == "numpy":
             white = torch.from_numpy(np.stack([sig_plans[i]["white"] for i in aids]).astype(np.float32)).to(dev)
         else:
@@ -839,27 +829,15 @@ def _signals(who, out_dir, stage, cfgs, seed, args, sources, stem, device, noise
                 mic_pos = np.ascontiguousarray(np.stack([cfgs[i]["mic_pos"] for i in aids]), np.float64)    # (the draws leave them column-major)
                 C = hip.mixing_table(torch.from_numpy(mic_pos).to(dev), float(fs), float(c))
             rirsynth.mix_simulated(src, rir_dev, rir_len, dp_dev, dp_len, white, C, snr, gain, out=sig[0], out_dp=out_dp)
-        pcm = hip.pcm16_pack(sig)
-        k = nbatch % 2
-        nbatch += 1
-        if busy[k] is not None:
-            busy[k].result()                                  # the buffer's previous batch is on disk
-        staged = pinned[k].view(-1)[:nsig * A * ns * nmic].view(nsig * A, ns, nmic)      # dense: the A signals, then their A direct paths
-        staged.copy_(pcm.view(nsig * A, ns, nmic), non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record(side)
+        pcm = hip.pcm16_pack(sig).view(nsig * A, ns, nmic)    # dense: the A signals, then their A direct paths
         infos = [sig_info(cfgs[i], sig_plans.pop(i), lab["t60_edc"][j], lab["drr"][j], lab["c50"][j], c) for i, j in zip(aids, acc)]
-        busy[k] = writer.submit(write, ev, staged, aids, infos)
+        writer.stage(pcm, write, aids, infos)
         return aids
 
-    with ThreadPoolExecutor(max_workers=1) as writer, torch.cuda.stream(side):
-        res = _generate(who, out_dir, stage, cfgs, seed, args, dev, noise, batch, "device", sink, log, prepare,
-                        sig_lmax(args["T60_range"], fs), saved_cfgs, T=T, snr_range=tuple(snr_range), **(recorded or {}),
-                        **(dict(save_dp=True) if save_dp else {}))
-        for f in busy:
-            if f is not None:
-                f.result()
-    return res
+    with StagedWriter(nsig * batch, ns, nmic) as writer, torch.cuda.stream(side):
+        return _generate(who, out_dir, stage, cfgs, seed, args, dev, noise, batch, "device", sink, log, prepare,
+                         sig_lmax(args["T60_range"], fs), saved_cfgs, T=T, snr_range=tuple(snr_range), **(recorded or {}),
+                         **(dict(save_dp=True) if save_dp else {}))
 
 
 # ---------------------------------------------------------------------------------------------------------------- fixed rooms

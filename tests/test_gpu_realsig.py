@@ -23,10 +23,10 @@ def tree(tmp_path_factory):
     return dict(cases.build_all(root), root=root)
 
 
-def _main(tree, save, stage, names, batch=BATCH):
+def _main(tree, save, stage, names, batch=BATCH, data_num=DATA_NUM):
     from sar_ssl_amd import realsig
     return realsig.main(["--stage", stage, "--dataset"] + names + ["--T", str(cases.T), "--src_dir", tree["src"], "--rir_dir", tree["rir"],
-                         "--save_dir", save, "--data_num", str(DATA_NUM), "--batch", str(batch)])
+                         "--save_dir", save, "--data_num", str(data_num), "--batch", str(batch)])
 
 
 @pytest.fixture(scope="module")
@@ -78,6 +78,19 @@ def test_a_second_run_writes_the_same_bytes(tree, generated, tmp_path):
         assert a == b, i
     assert _main(tree, save, "pretrain", ["ACE"], batch=5) == 0                              # over existing files, without a prompt;
     for i in range(DATA_NUM):                                                                # a file does not depend on the batch it was in
+        a, b = (open(os.path.join(d, "pretrain", "ACE", "%d.wav" % i), "rb").read() for d in (generated, save))
+        assert a == b, i
+
+
+def test_the_staged_writer_reuses_both_buffers_and_writes_a_ragged_last_batch(tree, generated, tmp_path):
+    """pipeline.StagedWriter under the generator: 7 items in batches of 2 are four batches, so each pinned buffer is staged twice and the
+    last batch fills the dense prefix of one row; every file equals, byte for byte, the one the module's run wrote at batch 3."""
+    save = str(tmp_path / "staged")
+    assert _main(tree, save, "pretrain", ["ACE"], batch=2, data_num=7) == 0
+    out_dir = os.path.join(save, "pretrain", "ACE")
+    assert sorted(os.listdir(out_dir)) == sorted("%d.wav" % i for i in range(7))              # all seven, and no *.tmp left behind
+    assert not [f for _, _, files in os.walk(save) for f in files if f.endswith(".tmp")]
+    for i in range(7):
         a, b = (open(os.path.join(d, "pretrain", "ACE", "%d.wav" % i), "rb").read() for d in (generated, save))
         assert a == b, i
 
