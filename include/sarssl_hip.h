@@ -188,6 +188,24 @@ int sarssl_resample_poly(const void* x, int in_dtype, long row0, long nrows, lon
 int sarssl_resample_poly_batch_supported(int nb, int nch, int up, int down);
 int sarssl_resample_poly_batch(const void* x, int in_dtype, const int* n_in, int nb, long n_max, int nch, int up, int down,
                                const float* taps, int ntaps, long n_out_max, void* out, int out_dtype, void* stream);
+/* ---- the LOCATA TDOA corpus generator (csrc/locata.hip; code/data_generation/utils_LOCATA.py:113-118, 257-260): one workgroup per
+ *      item, no atomics, fixed fold orders - an item's result does not depend on its place in the batch.
+ *      sarssl_peak_scale: x (nb, ns, nch) f32 IN PLACE, x[b] *= 0.9f / (peak[b] + 1e-8f) with peak[b] = max |x[b]| over all channels,
+ *      stored in peak (nb,) f32.  A sample that is not finite makes peak[b] (and with it the item) NaN.  Refused (-1): nb outside
+ *      1..65535, ns nch outside 1..2^31 - 1. */
+int sarssl_peak_scale(float* x, int nb, long ns, int nch, float* peak, void* stream);
+/*      sarssl_interp_mean: a ragged batch of tables - item b owns rows [offsets[b], offsets[b + 1]) of ts (ntotal,) f64 (ascending) and
+ *      val (ntotal, ncol) f64 - and per item the sample times t0[b] + k dt[b], k < n[b]:
+ *        out[b][c] = mean over k of np.interp(t0[b] + k dt[b], ts_b, val_b[:, c])      (b, ncol) f64
+ *      with numpy's end rules (the end values outside the table, the left node's value exactly at a node) and its arithmetic (slope by
+ *      one division per interval, slope (t - ts[j]) + val[j] in separately rounded steps).  A thread sums a contiguous run of k in f64, the
+ *      256 partials are folded in thread order.  offsets (nb + 1), t0, dt, n are HOST arrays: they are checked, packed and copied to
+ *      ws (device, sarssl_interp_mean_workspace_bytes(nb) bytes; -1 for a refused nb) on the stream, and that copy is waited for
+ *      before the call returns.  Refused (-1, nothing launched, out untouched): nb outside 1..65535, ncol outside 1..8, a table
+ *      without a row, offsets that do not start at 0 or end at ntotal, n[b] < 1, t0 or dt not finite, dt < 0. */
+long sarssl_interp_mean_workspace_bytes(int nb);
+int sarssl_interp_mean(const int* offsets, const double* t0, const double* dt, const int* n, int nb, int ncol, long ntotal,
+                       const double* ts, const double* val, void* ws, double* out, void* stream);
 
 /* ---- generic batched MFMA GEMM with fused epilogue: nn.Linear / Conv1d(k=1) / patch conv / attention bmm
  *      (code/common/conformer/modules.py:35-48, feed_forward.py:47-54, attention.py:82-103, convolution.py:138,143,

@@ -14,6 +14,8 @@ import numpy as np
 import torch
 from torch.utils.data import Dataset
 
+from .pipeline import EpochLoader
+
 
 def read_wav_pcm16(path):
     """-> (int16 array (nsample, nch), fs).  Supports plain PCM-16 and WAVE_FORMAT_EXTENSIBLE PCM-16."""
@@ -113,6 +115,24 @@ class Selecting(object):
         return mic_sig[self.select_range[0]:self.select_range[1], ...]
 
 
+TASKS = ("TDOA", "T60", "DRR", "C50", "ABS")
+
+
+def simulated_annos(info):
+    """The labels FixMicSigDataset forms from a simulated segment's ``_info.npz`` (code/dataset.py:153-170); ABS by Sabine's formula."""
+    vol = info["room_sz"][0] * info["room_sz"][1] * info["room_sz"][2]
+    sur = info["room_sz"][0] * info["room_sz"][1] + info["room_sz"][0] * info["room_sz"][2] + info["room_sz"][1] * info["room_sz"][2]
+    return {"TDOA": info["TDOA"].astype(np.float32), "T60": info["T60_edc"].astype(np.float32),
+            "DRR": info["DRR"].astype(np.float32), "C50": info["C50"].astype(np.float32),
+            "ABS": np.array(0.161 * vol / sur / info["T60_edc"]).astype(np.float32)}
+
+
+def locata_annos(info):
+    """The labels of a LOCATA segment (code/dataset.py:221-227): its TDOA, NaN for the room-acoustics tasks."""
+    return {"TDOA": info["TDOA"].astype(np.float32), "T60": np.array(np.nan), "DRR": np.array(np.nan), "C50": np.array(np.nan),
+            "ABS": np.array(np.nan)}
+
+
 class FixMicSigDataset(Dataset):
     def __init__(self, data_dir, fs, load_anno, dataset_sz, load_dp=False, transforms=None, raw_pcm=False):
         dirs = data_dir if isinstance(data_dir, list) else [data_dir]
@@ -145,12 +165,7 @@ class FixMicSigDataset(Dataset):
                 mic_sig = t(mic_sig)
         return_data = [mic_sig.astype(np.float32)]
         if self.load_anno:
-            info = dict(np.load(file_name.replace(".wav", "_info.npz")))
-            vol = info["room_sz"][0] * info["room_sz"][1] * info["room_sz"][2]
-            sur = info["room_sz"][0] * info["room_sz"][1] + info["room_sz"][0] * info["room_sz"][2] + info["room_sz"][1] * info["room_sz"][2]
-            return_data += [{"TDOA": info["TDOA"].astype(np.float32), "T60": info["T60_edc"].astype(np.float32),
-                             "DRR": info["DRR"].astype(np.float32), "C50": info["C50"].astype(np.float32),
-                             "ABS": np.array(0.161 * vol / sur / info["T60_edc"]).astype(np.float32)}]
+            return_data += [simulated_annos(dict(np.load(file_name.replace(".wav", "_info.npz"))))]
         if self.load_dp:
             dp, fs_dp = read_wav_pcm16(file_name.replace(".wav", "_dp.wav"))
             dp_sig = dp.astype(np.float32) / 32768.0
@@ -316,3 +331,113 @@ def segment_files(data_dir):
         files += list(Path(d).rglob("*.wav"))
         dp |= set(Path(d).rglob("*_dp.wav"))
     return [f for f in files if f not in dp]
+
+
+# ---------------------------------------------------------------------------------------------------------------- LOCATA TDOA corpus
+class FixMicSigDatasetLOCATA(Dataset):
+    """FixMicSigDatasetLOCATA (code/dataset.py:180-230): the ``{idx}.wav`` segments gen_LOCATA.py wrote (16 kHz PCM-16) with their
+    ``{idx}_info.npz`` - TDOA, and NaN for T60 / DRR / C50 / ABS.  The files are at ``fs`` already: one at another rate raises (the
+    reference would resample it per item)."""
+
+    def __init__(self, data_dir, fs, load_anno, dataset_sz, transforms=None):
+        if isinstance(data_dir, list):
+            self.files = []
+            for d in data_dir:
+                self.files += list(Path(d).rglob("*.wav"))
+            np.random.shuffle(self.files)
+        else:
+            self.files = list(Path(data_dir).rglob("*.wav"))
+        self.dataset_sz = len(self.files) if dataset_sz is None else int(np.min([len(self.files), dataset_sz]))
+        self.fs, self.load_anno, self.transforms = fs, load_anno, transforms
+
+    def __len__(self):
+        return self.dataset_sz
+
+    def __getitem__(self, idx):
+        file_name = str(self.files[idx])
+        pcm, fs = read_wav_pcm16(file_name)
+        if self.fs != fs:
+            raise ValueError("%s: sampled at %d Hz, the LOCATA TDOA corpus is read at %d Hz and not resampled (gen_LOCATA.py writes %d Hz)"
+                             % (file_name, fs, self.fs, self.fs))
+        mic_sig = pcm.astype(np.float32) / 32768.0
+        if self.transforms is not None:
+            for t in self.transforms:
+                mic_sig = t(mic_sig)
+        return_data = [mic_sig.astype(np.float32)]
+        if self.load_anno:
+            return_data += [locata_annos(dict(np.load(file_name.replace(".wav", "_info.npz"))))]
+        return return_data
+
+
+def _select_range(transforms, what):
+    """(first sample, one past the last) of ``transforms`` for a batch reader, or None for the whole file: nothing or one ``Selecting``."""
+    if not transforms:
+        return None
+    if len(transforms) != 1 or not isinstance(transforms[0], Selecting):
+        raise ValueError("%s reads a batch straight into one buffer: its transforms are None or [Selecting(...)]" % what)
+    a, b = transforms[0].select_range
+    return int(a), int(b)
+
+
+class RandomMicSigDataset(EpochLoader):
+    """RandomMicSigDataset (code/dataset.py:232-285) as a batch loader: yields ``(mic_sig (B, Ns, 2) f32 on the device, {task: (B,) f32
+    tensor})`` in the shape Learner.train_epoch / test_epoch iterate.  The reference's constructor arguments, then the loader's.
+
+    Per item the host draws the dataset - ``randint(0, len(dataset_list))`` over [simulated, LOCATA] by ``real_sim_ratio`` - and the
+    instance ``randint(0, len(dataset))`` on the epoch's one host stream (pipeline.EpochLoader.plan_batches: continued from numpy's
+    global state, the reference's order with num_workers=0).  The producer thread reads the batch's PCM-16 through the native reader into
+    ONE pinned buffer - Selecting's range only - and the labels from the ``_info.npz`` files; the consumer uploads and scales by
+    1 / 32768 (exact; what soundfile's float read gives).  A file at another rate than ``fs`` raises."""
+
+    def __init__(self, real_sig_dir, sim_sig_dir, real_sim_ratio, fs, stage, load_anno, dataset_sz, transforms=None, batch_size=16,
+                 device="cuda", drop_last=False, prefetch=2, nthreads=4):
+        import os
+        super().__init__(dataset_sz, batch_size, device, drop_last, prefetch)
+        realdataset = FixMicSigDatasetLOCATA(data_dir=os.path.join(real_sig_dir, stage), load_anno=load_anno, dataset_sz=None, fs=fs,
+                                             transforms=transforms)
+        simdataset = FixMicSigDataset(data_dir=sim_sig_dir, load_anno=load_anno, dataset_sz=None, fs=fs, transforms=transforms)
+        real_sim_ratio = list(real_sim_ratio)
+        assert real_sim_ratio in [[0, 1], [1, 0], [1, 1]], real_sim_ratio
+        self.dataset_list = {(0, 1): [simdataset], (1, 0): [realdataset], (1, 1): [simdataset, realdataset]}[tuple(real_sim_ratio)]
+        for d in self.dataset_list:
+            if len(d) == 0:
+                raise ValueError("RandomMicSigDataset: no segments below %s" % (sim_sig_dir if d is simdataset else os.path.join(real_sig_dir, stage),))
+        self.fs, self.load_anno, self.nthreads = fs, load_anno, nthreads
+        self.range = _select_range(transforms, "RandomMicSigDataset")
+        if self.range is None:
+            self.range = (0, wav_probe(str(self.dataset_list[0].files[0]))[2])
+
+    def plan_item(self, rs):
+        d = int(rs.randint(0, len(self.dataset_list)))
+        dataset = self.dataset_list[d]
+        idx = int(rs.randint(0, len(dataset)))
+        return dict(dataset=d, idx=idx, path=str(dataset.files[idx]), real=isinstance(dataset, FixMicSigDatasetLOCATA))
+
+    def handout(self, res):
+        if not self.load_anno:
+            return res, [res]
+        return res, [res[0]] + list(res[1].values())
+
+    def host_batch(self, plans):
+        pin = self.device.type == "cuda"
+        a, b = self.range
+        buf = torch.empty((len(plans), b - a, 2), dtype=torch.int16, pin_memory=pin)
+        read_wav_batch([p["path"] for p in plans], b - a, 2, self.fs, a, out=buf, nthreads=self.nthreads)
+        h = {"plans": plans, "pcm": buf}
+        if self.load_anno:
+            lab = torch.empty((len(TASKS), len(plans)), dtype=torch.float32, pin_memory=pin)
+            ln = lab.numpy()
+            for j, p in enumerate(plans):
+                info = dict(np.load(p["path"].replace(".wav", "_info.npz")))
+                annos = locata_annos(info) if p["real"] else simulated_annos(info)
+                for k, task in enumerate(TASKS):
+                    ln[k, j] = np.asarray(annos[task], np.float32).reshape(())
+            h["labels"] = lab
+        return h
+
+    def render(self, h, item0=0):
+        sig = h["pcm"].to(self.device, non_blocking=True).to(torch.float32).mul_(1.0 / 32768.0)
+        if not self.load_anno:
+            return sig
+        lab = h["labels"].to(self.device, non_blocking=True)
+        return sig, {task: lab[k] for k, task in enumerate(TASKS)}

@@ -963,6 +963,52 @@ def resample_poly_batch(x, n_in, up, down, out_dtype=torch.float32, out=None):
     return out
 
 
+# ---- the LOCATA TDOA corpus generator (csrc/locata.hip) -------------------------------------------------------------------------------
+def peak_scale(x, peak=None):
+    """x (B, Ns, nch) f32, IN PLACE: x[b] *= 0.9f / (max|x[b]| + 1e-8f) -> the peaks (B,) f32.  A sample that is not finite makes its
+    item's peak (and the item) NaN.  A refused shape raises."""
+    _need_cuda(x, peak)
+    if x.dim() != 3 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise _lib.SarsslHipError("peak_scale: x must be a contiguous (B, Ns, nch) f32 tensor")
+    B, ns, nch = x.shape
+    if peak is None:
+        peak = torch.empty((B,), dtype=torch.float32, device=x.device)
+    if peak.shape != (B,) or peak.dtype != torch.float32 or not peak.is_contiguous():
+        raise _lib.SarsslHipError("peak_scale: peak must be a contiguous (%d,) f32 tensor" % B)
+    _lib.call("sarssl_peak_scale", _p(x), c_int(B), c_long(ns), c_int(nch), _p(peak), _stream())
+    return peak
+
+
+def interp_mean(offsets, ts, val, t0, dt, n, out=None):
+    """Per item b the mean over k < n[b] of np.interp(t0[b] + k dt[b], ts_b, val_b[:, c]) -> (B, ncol) f64 on the device.  ts (ntotal,)
+    and val (ntotal, ncol <= 8) are f64 device tensors, item b owning rows offsets[b] .. offsets[b + 1]; offsets (B + 1), t0, dt, n are
+    HOST sequences (the call checks them and waits for their small upload on the current stream).  A refused shape raises and leaves
+    ``out`` untouched.  See include/sarssl_hip.h for the arithmetic."""
+    import numpy as np
+    _need_cuda(ts, val, out)
+    if ts.dim() != 1 or val.dim() != 2 or ts.dtype != torch.float64 or val.dtype != torch.float64 or val.shape[0] != ts.shape[0] \
+            or not ts.is_contiguous() or not val.is_contiguous():
+        raise _lib.SarsslHipError("interp_mean: ts (ntotal,) and val (ntotal, ncol) must be contiguous f64 tensors")
+    off = np.ascontiguousarray(offsets, np.int32)
+    B, ncol = off.shape[0] - 1, val.shape[1]
+    t0a, dta, na = (np.ascontiguousarray(t0, np.float64), np.ascontiguousarray(dt, np.float64), np.ascontiguousarray(n, np.int32))
+    if off.ndim != 1 or t0a.shape != (B,) or dta.shape != (B,) or na.shape != (B,):
+        raise _lib.SarsslHipError("interp_mean: offsets (B + 1,), t0, dt and n (B,) do not agree")
+    fn = _lib.lib().sarssl_interp_mean_workspace_bytes
+    fn.restype = c_long
+    nbytes = fn(c_int(B))
+    if nbytes < 0:
+        raise _lib.SarsslHipError("interp_mean: unsupported batch (B=%d): 1..65535" % B)
+    ws = workspace(nbytes, ts.device, "interp_mean")
+    if out is None:
+        out = torch.empty((B, ncol), dtype=torch.float64, device=ts.device)
+    if out.shape != (B, ncol) or out.dtype != torch.float64 or not out.is_contiguous():
+        raise _lib.SarsslHipError("interp_mean: out must be a contiguous (%d, %d) f64 tensor" % (B, ncol))
+    _lib.call("sarssl_interp_mean", c_void_p(off.ctypes.data), c_void_p(t0a.ctypes.data), c_void_p(dta.ctypes.data), c_void_p(na.ctypes.data),
+              c_int(B), c_int(ncol), c_long(ts.shape[0]), _p(ts), _p(val), _p(ws), _p(out), _stream())
+    return out
+
+
 # ------------------------------------------------------------------------------------------------
 # conv stem
 def _f32ws(n, device, tag):

@@ -1,6 +1,6 @@
 """Command-line options and directory layouts of the entry points: same flag names / defaults as ``opt_pretrain``
-(code/opt.py:6-115) and ``opt_downstream`` (code/opt.py:117-320: the simulated-data branch and, for T60 / DRR / C50 / ABS, the real-data
-branch) in the reference."""
+(code/opt.py:6-115) and ``opt_downstream`` (code/opt.py:117-320: the simulated-data branch and the real-data branch - T60 / DRR / C50 /
+ABS on signals synthesised from stored RIRs, TDOA on the LOCATA corpus ``gen_LOCATA.py`` writes) in the reference."""
 import argparse
 import os
 import time
@@ -76,7 +76,8 @@ class opt_pretrain():
 
 class opt_downstream():
     """Downstream (TDOA / DRR / C50 / T60 / ABS regression on the pretrained encoders) options: the simulated-data branch (--simu-exp) and
-    the real-data branch of the room-acoustics tasks (signals synthesised from stored RIRs, rirsynth.py).
+    the real-data branch: the room-acoustics tasks on signals synthesised from stored RIRs (rirsynth.py), TDOA on the LOCATA corpus
+    (locatads.py, dataset.RandomMicSigDataset).
     ``--ds-nepoch/--ds-num/--ds-lr-set/--ds-bs-set/--ds-eval-num`` are build-side overrides of the reference's hard-wired sweep
     (code/opt.py:197-209) so that a short run is possible; left unset, the reference's values apply."""
 
@@ -139,9 +140,13 @@ class opt_downstream():
         self.extra_info = "R" + str(args.ds_nsimroom)
         return args
 
-    REFUSE_TDOA_REAL = ("the LOCATA TDOA real-data branch (RandomMicSigDataset, code/run_downstream.py:213-230) is not built: it is file "
-                        "loading only and needs its own corpus layout.  Without --simu-exp the tasks T60, DRR, C50 and ABS run (microphone "
-                        "signals synthesised from stored RIRs); TDOA runs with --simu-exp")
+    REFUSE_TDOA_REAL = ("the LOCATA TDOA real-data branch (RandomMicSigDataset, code/run_downstream.py:213-230) reads the pre-generated "
+                        "corpus %s/{train,val,test}/{idx}.wav + {idx}_info.npz, and %s/train holds no segment.  Write it with\n"
+                        "  python gen_LOCATA.py --stage train val test --data-dir <data>/MicSig/LOCATA --save-to %s\n"
+                        "(TDOA also runs on simulated data with --simu-exp; without it T60, DRR, C50 and ABS run on signals synthesised "
+                        "from stored RIRs)")
+    REFUSE_TDOA_MIXED = ("--ds-task TDOA together with %s: on real data TDOA trains on the LOCATA corpus at T = 1.04 s and the "
+                         "room-acoustics tasks on signals synthesised from stored RIRs at T = 4.112 s - run them one after the other")
     REFUSE_TEST_REAL = ("--ds-test is simulated-only, as in the reference (code/run_downstream.py:383 asserts --simu-exp): "
                         "`--ds-test --simu-exp` evaluates what `--ds-train --simu-exp` left")
 
@@ -150,11 +155,19 @@ class opt_downstream():
         real / simulated ratio; the cross-validation trials are counted by run_downstream from the rooms on disk."""
         if args.ds_test:
             raise SystemExit(self.REFUSE_TEST_REAL)
-        if "TDOA" in args.ds_task:
-            raise SystemExit(self.REFUSE_TDOA_REAL)
+        locata = "TDOA" in args.ds_task
+        if locata:
+            if len(args.ds_task) > 1:
+                raise SystemExit(self.REFUSE_TDOA_MIXED % ", ".join(t for t in args.ds_task if t != "TDOA"))
+            if len([g for g in args.gpu_id.split(",") if g != ""]) > 1:
+                raise SystemExit("--gpu-id %s: the LOCATA TDOA branch runs on one GPU (data-parallel downstream is not built)" % args.gpu_id)
+            corpus = self.work_dir_local + "/SAR-SSL/data/MicSig/real_ds_locata"                 # dir()'s micsig_real
+            train = os.path.join(corpus, "train")
+            if not (os.path.isdir(train) and any(f.endswith(".wav") for f in os.listdir(train))):
+                raise SystemExit(self.REFUSE_TDOA_REAL % (corpus, corpus, corpus))
         ratio = list(args.ds_real_sim_ratio)
-        assert ratio in [[0, 1], [1, 0], [1, 1]], ratio                                          # code/dataset.py:358
-        self.ds_specifics.update(data="real_ace", real_sim_ratio=ratio)
+        assert ratio in [[0, 1], [1, 0], [1, 1]], ratio                                          # code/dataset.py:262, 358
+        self.ds_specifics.update(data="real_locata" if locata else "real_ace", real_sim_ratio=ratio)   # code/opt.py:190-195
         table = {"finetune": {(1, 0): 1600, (1, 1): 3200, (0, 1): 32000}, "scratchLOW": {(1, 0): 1600, (1, 1): 16000, (0, 1): 32000}}
         if args.ds_trainmode not in table:
             raise Exception("Undefined trainmode for the number of real-world training data")
@@ -183,6 +196,8 @@ class opt_downstream():
             dirs["srcsig_test"] = dirs["data"] + "/SrcSig/wsj0/et"
             dirs["rir_real"] = dirs["gerdata"] + "/RIR/real/ACE"
             dirs["rir_train_simu"] = dirs["gerdata"] + "/RIR/simu/train"
+            dirs["micsig_real"] = dirs["gerdata"] + "/MicSig/real_ds_locata"                      # LOCATA TDOA: code/opt.py:303-306
+            dirs["micsig_train_simu"] = dirs["gerdata"] + "/MicSig/simu_ds/train"
             r = self.ds_specifics["real_sim_ratio"]
             flag = "real_train" + str(r[0]) + "real" + str(r[1]) + "sim_valreal"
         dirs["log_pretrain"] = dirs["exp"] + "/pretrain/" + self.time

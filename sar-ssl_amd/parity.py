@@ -112,6 +112,27 @@ MIXTABLE = dict(cap=2.0 ** -22, measured=0.0, gate=0.0)
 RESAMPLE = dict(cap=1.5e-5, ceiling=2e-6, measured=dict(kernel=4.3e-7, scipy_f32=4.3e-7, realrir_rir=1.6e-7, realrir_drr_db=2.6e-6,
                                                          realrir_c50_db=1.7e-6), gate=2e-6)
 
+# The LOCATA TDOA corpus (locatads.py, csrc/locata.hip).
+#   label / signal    locatads.TdoaCorpus.restate_item against the reference's LOCATADataset.__getitem__ over the items of fixture F27
+#                     (tests/test_locatads_cpu.py).  The label: |float32(restatement) - reference's float32 label| relative to the label's
+#                     magnitude; both sides form the same f64 expressions in numpy, measured 0 on all 24 items, so the gate is 0 (equality)
+#                     and the cap, a condition, is one float32 unit (2^-23).  The signal: max |restatement - reference| relative to the
+#                     item's peak 0.9 - the reference resamples in float32 (scipy keeps the input's dtype), the restatement in f64;
+#                     measured 3.5e-7, the gate 4x that, under RESAMPLE's ceiling
+#   interp_mean       hip.interp_mean against np.interp(...).mean(axis=0) in f64 (tests/test_gpu_locatads.py): |difference| relative to the
+#                     column's largest |value|.  Same values term by term; numpy sums pairwise, the kernel in runs of ceil(n / 256) and
+#                     then over 256 partials.  ulps: the gate in units of 2^-52 log2(max(n, 2)) - "a few f64 ulp times log2(n)";
+#                     measured: the largest distance seen in those units on an MI355X
+#   peak_scale        hip.peak_scale against numpy in f32, operation for operation (max|x|; 0.9f / (peak + 1e-8f); one product per
+#                     sample): the peak and - measured - the scaled samples are bit-equal, so the gate is 0 (equality); cap: one float32
+#                     unit of the item's peak 0.9
+#   generate          the files of locatads.generate against restate_item: half a PCM-16 step plus RESAMPLE's gate at full scale, in
+#                     PCM-16 steps; the labels (float32) against float32(restate_item's): the kernel's gate in f64 moves a float32
+#                     rounding only where the f64 value sits on a boundary, so one float32 unit
+LOCATADS = dict(label=dict(cap=2.0 ** -23, measured=0.0, gate=0.0), signal=dict(ceiling=RESAMPLE["ceiling"], measured=3.5e-7, gate=1.4e-6),
+                interp_mean=dict(ulps=4.0, measured=3.3), peak_scale=dict(cap=2.0 ** -23, measured=0.0, gate=0.0),
+                generate=dict(pcm_steps=0.5 + RESAMPLE["gate"] * 32767, label=2.0 ** -23, measured=dict(pcm_steps=0.511, label=0.0)))
+
 # The row / elementwise kernels (csrc/elementwise.hip, the row kernels of csrc/dwconv.hip, csrc/head.hip) against the f64 restatements of
 # tests/rowkernel_refs.py on the operands as stored: max |got - ref| / max |ref| (tests/test_gpu_rowkernels.py).  Keyed by kernel family,
 # then by the storage dtype of a forward kernel or the (gradient, saved activation) pairing of a backward kernel: f32, bf16, fp16,

@@ -4,10 +4,14 @@ the real-data training branch of the room-acoustics tasks:
     python run_downstream.py --ds-train --simu-exp --ds-trainmode finetune --ds-task TDOA --ds-nsimroom 8 --time <pretrain tag>
     python run_downstream.py --ds-test --simu-exp --test-mode cal_metric --ds-trainmode finetune --ds-task TDOA --ds-nsimroom 8 --time <tag>
     python run_downstream.py --ds-train --ds-trainmode finetune --ds-task T60 --ds-real-sim-ratio 1 1 --time <pretrain tag>
+    python run_downstream.py --ds-train --ds-trainmode finetune --ds-task TDOA --ds-real-sim-ratio 1 1 --time <pretrain tag>
 
 Without ``--simu-exp`` (T60 / DRR / C50 / ABS) every item is synthesised on the GPU from stored RIRs (``RealData``, rirsynth.py); one
-cross-validation trial per measured room; everything after the loaders is the same sweep.  Out of scope and refused by the option parser:
-the LOCATA TDOA real-data branch and ``--ds-test`` without ``--simu-exp`` (opt.py).
+cross-validation trial per measured room; everything after the loaders is the same sweep.  TDOA without ``--simu-exp`` reads the LOCATA
+corpus ``gen_LOCATA.py`` wrote (``LocataData``, dataset.RandomMicSigDataset): training mixed with the simulated downstream corpus by
+``--ds-real-sim-ratio``, validation and test LOCATA only, one trial.  Refused by the option parser (opt.py): that branch while its corpus
+is missing (the message holds the command that writes it), TDOA next to another task or on several GPUs without ``--simu-exp``, and
+``--ds-test`` without ``--simu-exp``.
 
 ``--ds-train``.  Per task and per (trial, batch size, learning rate) of the sweep: train / validate / test every epoch, early stopping on the
 smoothed validation loss with one learning-rate decay (code/run_downstream.py:262-308), ensembling of the last five epochs up to
@@ -198,6 +202,28 @@ class RealData:
                                        noise="device", device=self.device, c=ac["sound_speed"])
 
 
+class LocataData:
+    """The real-data branch's datasets for TDOA (code/run_downstream.py:213-230): per stage a dataset.RandomMicSigDataset batch loader over
+    the corpus gen_LOCATA.py wrote under ``dirs['micsig_real']`` - training mixed with the simulated segments of
+    ``dirs['micsig_train_simu']`` by ``--ds-real-sim-ratio``, validation, test and test_large LOCATA only (``test_large`` reads the
+    ``test`` directory, as every ``stage.split('_')[0]`` of the reference does).  One trial."""
+
+    def __init__(self, args, dirs, fs, selecting, device):
+        self.dirs, self.fs, self.selecting, self.device = dirs, fs, selecting, device
+        self.ratios = {"train": list(args.ds_specifics["real_sim_ratio"]), "val": [1, 0], "test": [1, 0]}
+
+    def new_task(self):
+        return 1
+
+    def loader(self, trial_idx, stage, dataset_sz, batch_size):
+        from sar_ssl_amd import dataset as at_dataset
+        st = stage.split("_")[0]
+        return at_dataset.RandomMicSigDataset(real_sig_dir=self.dirs["micsig_real"],
+                                              sim_sig_dir=self.dirs["micsig_" + st + "_simu"] if stage == "train" else [],
+                                              real_sim_ratio=self.ratios[st], fs=self.fs, stage=st, load_anno=True, dataset_sz=dataset_sz,
+                                              transforms=[self.selecting], batch_size=batch_size, device=self.device)
+
+
 def main(argv=None):
     from sar_ssl_amd.opt import opt_downstream
     opts = opt_downstream()
@@ -234,7 +260,10 @@ def main(argv=None):
 
     log_dir = "log_task_" + args.ds_trainmode
     init_state_dict = copy.deepcopy(net.state_dict())
-    real = None if args.simu_exp else RealData(args, dirs, T, fs, seeds, device)
+    real = None
+    if not args.simu_exp:
+        real = (LocataData(args, dirs, fs, selecting, device) if args.ds_specifics["data"] == "real_locata"
+                else RealData(args, dirs, T, fs, seeds, device))
     for task in args.ds_task:
         set_seed(args.seed)
         task_time_dir = dirs["log_task"].replace("TASK", task)
