@@ -159,6 +159,19 @@ int sarssl_rir_labels(const float* rir, const int* n_len, const float* rir_dp, c
  *      is libsndfile's float -> PCM-16 rule with normalisation on AS THIS PROJECT READS IT: soundfile is not available to pin it against
  *      (UNPINNED).  The product is exact in f64, so the result is bit-equal to numpy's.  in 16-byte, out 8-byte aligned. */
 int sarssl_pcm16_pack(const float* in, long n, short* out, void* stream);
+/* ---- source crops from a corpus on the device (csrc/srcbank.hip; rirsynth.DeviceSourceBank, onlinesig.OnlineSignalLoader): bank is the
+ *      corpus' utterances as one flat PCM-16 array of bank_len samples ON THE DEVICE.  Item b is the concatenation of its nseg[b] segments
+ *      bank[seg_off[b][s] .. + seg_len[b][s]) - the utterances of one speaker from the drawn one on, wrapping to the speaker's first - and
+ *        out[b][i] = float(x[crop_start[b] + i] / 32768 - mean),  mean = (sum of the crop's x / 32768) / ns,  i < ns       (nb, ns) f32
+ *      with the division by 32768, the sum, the mean and the subtraction in f64, rounded to f32 once: what rirsynth.SourceBank.draw
+ *      returns (WSJ0Dataset, utils_src.py:65-122), astype(float32).  The sum is formed as a 64-bit integer, which is exact, so the result is
+ *      BIT-EQUAL to numpy's and depends neither on the batch position nor on a fold order; one workgroup per item, no atomics.
+ *      seg_off long (nb, 32), seg_len int (nb, 32), nseg int[nb] and crop_start long[nb] are HOST arrays: they are checked, packed and
+ *      copied to ws (device, 392 bytes per item; ws_bytes says how many there are) on the stream, and that copy is waited for before the
+ *      call returns.  Refused (-1, nothing launched, out untouched): nb outside 1..65535, ns < 1, nseg outside 1..32, a segment that is
+ *      empty or reaches past bank_len, a crop start below 0, segments that do not cover crop_start + ns samples, ws_bytes < 392 nb. */
+int sarssl_src_gather(const short* bank, long bank_len, const long* seg_off, const int* seg_len, const int* nseg, const long* crop_start,
+                      int nb, long ns, void* ws, long ws_bytes, float* out, void* stream);
 /* ---- polyphase resampling of measured recordings (csrc/resample.hip): scipy.signal.resample_poly(x, up, down, axis=0) at its defaults
  *      (window ('kaiser', 5.0), padtype 'constant') as code/data_generation/gen_real_rir.py:1052-1054, 1160-1161 calls it, every channel
  *      of a file in one launch.  up / down are REDUCED by their gcd, half = 10 max(up, down), taps f32[ntaps = 2 half + 1] =

@@ -863,6 +863,34 @@ def pcm16_pack(x, out=None):
     return out
 
 
+# ---- source crops from a corpus on the device (csrc/srcbank.hip) ------------------------------------------------------------------------
+SRC_MAXSEG = 32                  # csrc/srcbank.hip SB_MAXSEG
+_SRC_ITEM_BYTES = 392            # sizeof(SrcItem) there; the library refuses a smaller workspace
+
+
+def src_gather(bank, seg_off, seg_len, nseg, crop_start, ns, out=None):
+    """bank: the corpus as one flat int16 device tensor; per item its segments seg_off int64 (B, 32) / seg_len int32 (B, 32) / nseg int32 (B)
+    and crop_start int64 (B) over their concatenation, as HOST numpy arrays -> out (B, ns) f32: s / 32768 minus the crop's mean, f64
+    arithmetic rounded once - bit-equal to rirsynth.SourceBank.draw(...)[0].astype(float32).  The call waits for its small table upload.
+    A refused shape (nseg outside 1..32, a segment past the bank's end, ns < 1, segments shorter than the crop) raises and leaves ``out``
+    untouched."""
+    import numpy as np
+    _need_cuda(bank, out)
+    assert bank.dtype == torch.int16 and bank.dim() == 1 and bank.is_contiguous()
+    B = int(nseg.shape[0])
+    seg_off, seg_len = np.ascontiguousarray(seg_off, np.int64), np.ascontiguousarray(seg_len, np.int32)
+    nseg, crop_start = np.ascontiguousarray(nseg, np.int32), np.ascontiguousarray(crop_start, np.int64)
+    assert seg_off.shape == (B, SRC_MAXSEG) and seg_len.shape == (B, SRC_MAXSEG) and nseg.shape == (B,) and crop_start.shape == (B,)
+    if out is None:
+        out = torch.empty((B, max(int(ns), 0)), dtype=torch.float32, device=bank.device)
+    assert out.shape == (B, max(int(ns), 0)) and out.dtype == torch.float32 and out.is_contiguous()
+    ws = workspace(B * _SRC_ITEM_BYTES, bank.device, "src_gather")
+    _lib.call("sarssl_src_gather", _p(bank), c_long(bank.numel()), c_void_p(seg_off.ctypes.data), c_void_p(seg_len.ctypes.data),
+              c_void_p(nseg.ctypes.data), c_void_p(crop_start.ctypes.data), c_int(B), c_long(ns), _p(ws), c_long(B * _SRC_ITEM_BYTES),
+              _p(out), _stream())
+    return out
+
+
 # ---- polyphase resampling of measured recordings (csrc/resample.hip) ------------------------------------------------------------------
 def resample_ratio(up, down):
     """(up, down) divided by their gcd: the ratio the kernel and the tap table are defined for."""

@@ -9,6 +9,10 @@ import numpy as np
 
 
 class opt_pretrain():
+    REFUSE_ONLINE = ("--simu-online (with --simu-online-reuse / --simu-online-bank-gb) renders the TRAINING batches of simulated pretraining "
+                     "on the GPU and is valid only with `--pretrain --simu-exp`; this command has %s (validation, --test and "
+                     "--pretrain-frozen-encoder read their corpora from disk)")
+
     def __init__(self):
         self.time = time.strftime("%m%d%H%M", time.localtime(time.time()))
         self.work_dir = os.path.abspath(os.path.expanduser(r"~"))
@@ -42,9 +46,28 @@ class opt_pretrain():
         p.add_argument("--data-num", type=int, nargs=2, default=None, metavar=("Train", "Val"),
                        help="items per epoch and per validation of real-data pretraining (build-side override for a short run; "
                             "default: the reference's 512000 and 8000)")
+        p.add_argument("--simu-online", action="store_true", default=False,
+                       help="with --pretrain --simu-exp: render every training batch on the GPU while the previous step runs "
+                            "(onlinesig.OnlineSignalLoader over <work-dir>/data/SrcSig/wsj0/tr) instead of reading MicSig/simu/pretrain; "
+                            "nothing is written and no room repeats; --data-num sets the items per epoch; validation reads preval from disk")
+        p.add_argument("--simu-online-reuse", type=int, default=1, metavar="K",
+                       help="--simu-online: every rendered room serves K consecutive items that differ in source, noise and SNR "
+                            "(K divides the training batch size; default: 1)")
+        p.add_argument("--simu-online-bank-gb", type=float, default=8.0, metavar="G",
+                       help="--simu-online: the most the source corpus may take on the device, in GiB; a larger corpus is refused, "
+                            "never truncated (default: 8)")
         args = p.parse_args(argv)
         assert (args.pretrain + args.pretrain_frozen_encoder + args.test) == 1, "Pretraining stage (pretrain or test) is undefined"
         assert args.test_mode in ["all", "ins"], "Test mode is undefined"
+        online = args.simu_online or args.simu_online_reuse != 1 or args.simu_online_bank_gb != 8.0
+        if online and (args.test or args.pretrain_frozen_encoder or not args.simu_exp):
+            raise SystemExit(self.REFUSE_ONLINE % ("--test" if args.test else "--pretrain-frozen-encoder" if args.pretrain_frozen_encoder
+                                                   else "no --simu-exp"))
+        if online and not args.simu_online:
+            raise SystemExit("--simu-online-reuse / --simu-online-bank-gb set what --simu-online renders: give --simu-online with them")
+        if args.simu_online_reuse < 1 or args.bs[0] % args.simu_online_reuse != 0:
+            raise SystemExit("--simu-online-reuse %d does not divide the training batch size %d: the items of a room share one batch"
+                             % (args.simu_online_reuse, args.bs[0]))
         self.time, self.work_dir = args.time, os.path.abspath(os.path.expanduser(args.work_dir))
         self.work_dir_local = self.work_dir
         self.simu_exp = bool(args.simu_exp)
@@ -59,6 +82,7 @@ class opt_pretrain():
         dirs["micsig_simu_preval"] = dirs["gerdata"] + "/MicSig/simu/preval"
         dirs["micsig_simu_pretest"] = dirs["gerdata"] + "/MicSig/simu/pretest"
         dirs["micsig_simu_pretest_ins"] = [dirs["gerdata"] + "/MicSig/simu/pretest_ins_T1000"]
+        dirs["srcsig_train"] = dirs["data"] + "/SrcSig/wsj0/tr"                                    # --simu-online's sources (code/opt.py:273)
         if not self.simu_exp:                                                                    # code/opt.py:82-109
             real, rec = dirs["gerdata"] + "/MicSig/real/", dirs["data"] + "/MicSig/"
             recordings = {"LOCATA": rec + "LOCATA", "MCWSJ": rec + "MC_WSJ_AV", "LibriCSS": rec + "LibriCSS", "AMI": rec + "AMI",

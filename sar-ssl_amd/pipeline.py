@@ -1,6 +1,7 @@
 """The concurrency the data pipelines share: the one-ahead epoch iterator of the GPU-rendering loaders (rirsynth.RirSynthLoader,
 realsig.RealMixLoader) and the double-buffered PCM writer of the generators (roomsim._signals, realsig.generate).  Planning, rendering
-and what a job writes stay with the callers.  dataset.PcmSegmentLoader uploads from its producer thread and keeps its own iterator.
+and what a job writes stay with the callers.  dataset.PcmSegmentLoader uploads from its producer thread and keeps its own iterator;
+onlinesig.OnlineSignalLoader renders whole chunks on its worker thread (the judge's read-back blocks there) and keeps its own too.
 """
 import queue
 import threading

@@ -6,6 +6,8 @@ to a drawn SNR against the direct-path power, peak normalisation.  Here the host
 reference's numpy draw order, call for call; ``draw_item`` is the part all items share, roomsim.plan_sig's too) and the GPU renders whole
 batches (hip.rir_mix / diffuse_noise / gauss_fill, csrc/rirmix.hip; ``mix_simulated`` is also roomsim.simulate_signals' mix).
 ``restate_*`` are the f64 numpy / scipy restatement of one item that the kernels and the reference fixture are checked against.
+``DeviceSourceBank`` is ``SourceBank`` with the corpus on the device: it plans a crop from its length table and hip.src_gather
+(csrc/srcbank.hip) cuts it there - the online loader's source (onlinesig.py).
 """
 import math
 import os
@@ -156,6 +158,100 @@ class SourceBank:
         s = sig[st:st + nsample].copy()
         s -= s.mean()
         return s, {"utt_idx": utt_idx, "crop_start": st, "utt_files": used}
+
+
+MAXSEG = 32                      # utterances a crop may run through (csrc/srcbank.hip SB_MAXSEG)
+
+
+class DeviceSourceBank:
+    """``SourceBank``'s corpus kept on the device: every utterance is read once (``min(16, workers)`` threads) into ONE flat int16 tensor
+    on ``device``; the host keeps each utterance's offset and length and each speaker's utterances in ``SourceBank``'s order.  ``plan``
+    makes ``SourceBank.draw``'s draws from the length table alone - no file is opened - and hip.src_gather (csrc/srcbank.hip) cuts the
+    crops on the device, bit-equal to ``draw(...)[0].astype(float32)``.  A corpus of more than ``max_bytes`` bytes of PCM-16 is refused
+    (never truncated); files at another rate or with several channels raise as in ``SourceBank``."""
+
+    def __init__(self, path, fs=FS, device="cuda", sort=False, max_bytes=8 << 30, workers=8):
+        import torch
+        from concurrent.futures import ThreadPoolExecutor
+        from .dataset import read_wav_pcm16
+        names = SourceBank(path, fs, sort)
+        self.fs, self.paths, self.spk_ids = fs, names.paths, names.spk_ids
+        index = {p: k for k, p in enumerate(self.paths)}
+        self.spk_utts = [[index[p] for p in utts] for utts in names.spk_wavs]
+        on_disk = sum(os.path.getsize(p) for p in self.paths)
+        if on_disk - 4096 * len(self.paths) > max_bytes:          # (no header is that long: refused before anything is read)
+            raise ValueError("%s: the corpus' files hold %d bytes, the device-resident bank is limited to max_bytes = %d: nothing is "
+                             "truncated - raise the limit (--simu-online-bank-gb) or use a smaller corpus" % (path, on_disk, max_bytes))
+
+        def read(p):
+            pcm, wav_fs = read_wav_pcm16(p)
+            if wav_fs != fs:
+                raise ValueError("%s: sampling rate %d, expected %d (the reference raises here too, utils_src.py:52-54)" % (p, wav_fs, fs))
+            if pcm.shape[1] != 1:
+                raise ValueError("%s: %d channels, a source utterance has one" % (p, pcm.shape[1]))
+            return np.ascontiguousarray(pcm[:, 0])
+        with ThreadPoolExecutor(max_workers=max(1, min(16, int(workers)))) as pool:
+            utts = list(pool.map(read, self.paths))
+        self.lengths = np.array([u.shape[0] for u in utts], np.int64)
+        self.offsets = np.concatenate([[0], np.cumsum(self.lengths)[:-1]]).astype(np.int64)
+        nbytes = 2 * int(self.lengths.sum())
+        if nbytes > max_bytes:
+            raise ValueError("%s: the corpus holds %d bytes of PCM-16, the device-resident bank is limited to max_bytes = %d: nothing is "
+                             "truncated - raise the limit (--simu-online-bank-gb) or use a smaller corpus" % (path, nbytes, max_bytes))
+        if any(self.lengths[u].sum() == 0 for u in self.spk_utts):
+            raise ValueError("%s: a speaker without a single sample" % path)
+        self.flat = torch.from_numpy(np.concatenate(utts)).to(torch.device(device))
+        self.device = self.flat.device
+
+    def __len__(self):
+        return len(self.spk_ids)
+
+    def plan(self, rs, idx, nsample):
+        """``SourceBank.draw``'s draws on ``rs`` - utterance index, then the crop start over the same-speaker concatenation from that
+        utterance on (it wraps to the speaker's first) - -> its record {'utt_idx', 'crop_start', 'utt_files'} with 'segments':
+        [(offset, length), ...] of the utterances the crop covers in the bank, and 'seg_start': the crop's first sample inside the first."""
+        utts = self.spk_utts[idx % len(self.spk_ids)]
+        utt_idx = int(rs.randint(0, len(utts)))
+        total, used, cur = 0, [], utt_idx
+        while total < nsample:
+            used.append(utts[cur])
+            total += int(self.lengths[utts[cur]])
+            cur = cur + 1 if cur + 1 < len(utts) else 0
+        st = int(rs.randint(0, total - nsample + 1))
+        segments, pos, seg_start = [], 0, 0
+        for k in used:
+            n = int(self.lengths[k])
+            if n and pos + n > st and pos < st + nsample:
+                if not segments:
+                    seg_start = st - pos
+                segments.append((int(self.offsets[k]), n))
+            pos += n
+        if len(segments) > MAXSEG:
+            raise ValueError("a crop of %d samples of speaker %s runs through %d utterances, more than MAXSEG = %d: the speaker's utterances "
+                             "are too short for this segment length" % (nsample, self.spk_ids[idx % len(self.spk_ids)], len(segments), MAXSEG))
+        return {"utt_idx": utt_idx, "crop_start": st, "utt_files": [self.paths[k] for k in used], "segments": segments, "seg_start": seg_start}
+
+    def host_crop(self, rec, nsample):
+        """The crop of a ``plan`` record as ``SourceBank.draw`` returns it ((nsample,) f64, mean removed), gathered in numpy."""
+        sig = np.concatenate([self.flat[o:o + n].cpu().numpy() for o, n in rec["segments"]]).astype(np.float64) / 32768.0
+        s = sig[rec["seg_start"]:rec["seg_start"] + nsample].copy()
+        s -= s.mean()
+        return s
+
+    @staticmethod
+    def tables(recs):
+        """The host arrays hip.src_gather takes for a batch of ``plan`` records -> (seg_off (B, 32) i64, seg_len (B, 32) i32, nseg, start)."""
+        B = len(recs)
+        off, ln = np.zeros((B, MAXSEG), np.int64), np.zeros((B, MAXSEG), np.int32)
+        for b, r in enumerate(recs):
+            n = len(r["segments"])
+            off[b, :n], ln[b, :n] = [s[0] for s in r["segments"]], [s[1] for s in r["segments"]]
+        return (off, ln, np.array([len(r["segments"]) for r in recs], np.int32), np.array([r["seg_start"] for r in recs], np.int64))
+
+    def gather(self, recs, nsample, out=None):
+        """(B, nsample) f32 on the device: the crops of a batch of ``plan`` records (hip.src_gather)."""
+        from . import hip
+        return hip.src_gather(self.flat, *self.tables(recs), nsample, out=out)
 
 
 def _static_rir(path, rir):

@@ -13,6 +13,9 @@ WSJ0-style source, mixed with the diffuse white-noise field at a drawn SNR, conv
 ``{idx}_info.npz`` without the RIR leaving the GPU; ``plan_sig`` restates the reference's draws and ``restate_sig`` one item in f64
 (fixture F22, tools/make_golden_simsig.py).  The float -> PCM-16 rule is this project's reading of libsndfile's and UNPINNED (``pcm16``).
 Both generators are one loop (``_generate``: ``render_items``, the judge on the host or the device, retries) with their own sink.
+The signals' sink (``_signal_sink``: gather of the accepted rows, noise, mix, pack) also serves onlinesig.OnlineSignalLoader, which hands
+the packed batches to the training step instead of a writer (run_pretrain.py --simu-online) and draws its rooms with
+``random_room(beta_solver="closed")``: Sabine's equation solved exactly instead of by scipy.optimize.minimize.
 
 ``gen_simu_certain_room.py --mode rir | sig`` (GenerateRandomRIROfCertainRoom / GenerateRandomMicSigOfCertainRoom) is ``simulate_room_bank``
 / ``simulate_room_signals``: a fixed number of rooms drawn once each (``random_room``), placements on each room
@@ -186,6 +189,24 @@ def _beta_sabine_estimation(room_sz, T60, abs_weights):
     return np.sqrt(1 - result.x * abs_weights).astype(np.float32)
 
 
+def sabine_x_closed(room_sz, T60, abs_weights):
+    """The exact minimiser of ``_beta_sabine_estimation``'s t60error over [0, 1]: T60 = 0.161 V / (x S_w) solved for x and clipped, with
+    w = abs_weights / max(abs_weights) and S_w = (w0 + w1) Ly Lz + (w2 + w3) Lx Lz + (w4 + w5) Lx Ly -> (x, w), f64."""
+    w = np.asarray(abs_weights, np.float64) / np.max(abs_weights)
+    Sw = (w[0] + w[1]) * room_sz[1] * room_sz[2] + (w[2] + w[3]) * room_sz[0] * room_sz[2] + (w[4] + w[5]) * room_sz[0] * room_sz[1]
+    return float(np.clip(0.161 * np.prod(room_sz) / (T60 * Sw), 0.0, 1.0)), w
+
+
+def _beta_sabine_closed(room_sz, T60, abs_weights):
+    """``_beta_sabine_estimation`` without the optimiser (beta_solver="closed"): its exact solution, float32 as there.  Within 1.1e-3 of
+    the minimiser's beta - the minimiser's own imprecision - and never further from the wanted T60."""
+    x, w = sabine_x_closed(room_sz, T60, abs_weights)
+    return np.sqrt(1 - x * w).astype(np.float32)
+
+
+BETA_SOLVERS = {"minimize": "_beta_sabine_estimation", "closed": "_beta_sabine_closed"}
+
+
 def _t60_is_valid(room_sz, T60, alpha, c, ism_db, th=0.005, eps=1e-4):
     """utils_simu_rir_sig.py:116-131; alpha arrives as float32 (1 - beta^2), as there."""
     Sa = (alpha[0] + alpha[1]) * room_sz[1] * room_sz[2] + \
@@ -207,35 +228,42 @@ def _draw_ranges(room_sz_range, T60_range, abs_weights_range):
             DEFAULTS["abs_weights_range"] if abs_weights_range is None else abs_weights_range)
 
 
-def random_room(rs, room_sz_range=None, T60_range=None, abs_weights_range=None, c=343.0, ism_db=12):
+def random_room(rs, room_sz_range=None, T60_range=None, abs_weights_range=None, c=343.0, ism_db=12, beta_solver="minimize"):
     """SpatialAcoustics.random_room with room_cfg=None (utils_simu_rir_sig.py:74-98) on the RandomState ``rs`` where it stands, draw for
-    draw: the room size, then the T60 / abs_weights retry loop -> dict(room_sz, T60_sabine, beta, T60_specify)."""
+    draw: the room size, then the T60 / abs_weights retry loop -> dict(room_sz, T60_sabine, beta, T60_specify).
+    beta_solver: "minimize" - the reference's scipy.optimize.minimize (2.6-12 ms a room); "closed" - its exact solution
+    (``_beta_sabine_closed``; the online loader's, which draws rooms at training rate).  The draws and the accept test are the same."""
+    if beta_solver not in BETA_SOLVERS:
+        raise ValueError("beta_solver %r: one of %s" % (beta_solver, sorted(BETA_SOLVERS)))
+    solve = globals()[BETA_SOLVERS[beta_solver]]
     room_sz_range, T60_range, abs_weights_range = _draw_ranges(room_sz_range, T60_range, abs_weights_range)
     room_sz = [rs.uniform(*r) for r in room_sz_range]
     valid = False
     while not valid:
         T60_specify = rs.uniform(*T60_range)
         abs_weights = [rs.uniform(*r) for r in abs_weights_range]
-        beta = _beta_sabine_estimation(room_sz, T60_specify, abs_weights)
+        beta = solve(room_sz, T60_specify, abs_weights)
         valid, T60_sabine = _t60_is_valid(room_sz, T60_specify, 1 - beta ** 2, c, ism_db)
     return {"room_sz": room_sz, "T60_sabine": T60_sabine, "beta": beta, "T60_specify": T60_specify}
 
 
 def random_spatial_acoustics(rs, seed, idx, mic_array_cfg=None, room_sz_range=None, T60_range=None, abs_weights_range=None,
                              array_pos_ratio_range=None, num_source_range=(1, 1), source_state="static", min_src_array_dist=0.3,
-                             min_src_boundary_dist=0.3, c=343.0, ism_db=12, room_cfg=None):
+                             min_src_boundary_dist=0.3, c=343.0, ism_db=12, room_cfg=None, beta_solver="minimize", reseed=True):
     """SpatialAcoustics.generate_random_spatial_acoustics (utils_simu_rir_sig.py:23-131, 143-378) on the RandomState ``rs``, draw for
-    draw, after seed + idx: the room (``random_room``; with a ``room_cfg`` that room is taken and only what follows is drawn, :43-70),
-    the array, one static source.  Returns the reference's dictionary."""
+    draw, after seed + idx: the room (``random_room``, with its ``beta_solver``; with a ``room_cfg`` that room is taken and only what
+    follows is drawn, :43-70), the array, one static source.  Returns the reference's dictionary.
+    reseed=False: ``rs`` is taken where it stands (the online loader seeds it per item with an array; seed and idx are then unused)."""
     mic_array_cfg = MIC_ARRAY_CFG_2CH if mic_array_cfg is None else mic_array_cfg
     array_pos_ratio_range = DEFAULTS["array_pos_ratio_range"] if array_pos_ratio_range is None else array_pos_ratio_range
     if source_state != "static":
         raise ValueError("static sources only (source_state %r): moving sources are out of scope" % (source_state,))
     if mic_array_cfg["array_type"] != "planar_linear":
         raise ValueError("Undefined array type~")
-    rs.seed(seed + idx)
+    if reseed:
+        rs.seed(seed + idx)
     if room_cfg is None:
-        room_cfg = random_room(rs, room_sz_range, T60_range, abs_weights_range, c, ism_db)
+        room_cfg = random_room(rs, room_sz_range, T60_range, abs_weights_range, c, ism_db, beta_solver)
     room_sz = room_cfg["room_sz"]
     # random_mic_array
     array_pos = np.array([rs.uniform(array_pos_ratio_range[i][0] * room_sz[i], array_pos_ratio_range[i][1] * room_sz[i]) for i in range(3)])
@@ -552,9 +580,22 @@ def device_noise(plans, ids, seed, attempt, device, lmax=None):
     from . import hip
     nch, lmax = plans[0]["mic"].shape[0], _row_length(plans, lmax)
     white = torch.empty((len(plans), lmax, nch), dtype=torch.float32, device=device)
-    for b, idx in enumerate(ids):
-        hip.gauss_fill(white[b:b + 1], (int(seed) & 0xffffffff) | (int(attempt) << 32), int(idx))
+    gauss_fill_items(white, ids, (int(seed) & 0xffffffff) | (int(attempt) << 32))
     return white.transpose(1, 2).contiguous()
+
+
+def gauss_fill_items(white, ids, key):
+    """white[b] = sarssl_gauss_fill's values of (key, ids[b]): one launch per run of consecutive ids (the kernel keys row b of a launch by
+    item0 + b, so a run is one call with the same values as a call per item)."""
+    from . import hip
+    ids = [int(i) for i in ids]
+    j = 0
+    while j < len(ids):
+        k = j + 1
+        while k < len(ids) and ids[k] == ids[k - 1] + 1:
+            k += 1
+        hip.gauss_fill(white[j:k], key, ids[j])
+        j = k
 
 
 def host_noise(plans, ids, seed, attempt, device, lmax=None):
@@ -640,16 +681,17 @@ def read_back_accepted(batch, acc, lab):
 
 
 def _generate(who, out_dir, stage, cfgs, seed, args, device, noise, batch, where, sink, log=None, prepare=None, lmax=None, saved_cfgs=None,
-              **recorded):
+              ids=None, **recorded):
     """The loop of both generators: the pending items are rendered in batches (``render_items``), judged (where="host": ``judge_on_host``,
     "device": ``judge_on_device``) and, where accepted (flags == 3), handed to ``sink(batch, accepted positions, labels) -> ids written``;
     the others are rendered again with the next attempt's noise and skipped with a logged line after MAX_ATTEMPTS.  ``prepare(ids)`` runs
     between the enqueue of a batch's renders and the wait for its labels: host work there overlaps the render.  all_info.npz (``args``,
     the stage's and ``recorded``; every configuration - ``saved_cfgs`` where the caller stores them in another shape -; the skipped ids) is
-    written unless out_dir is None.  -> dict(written, skipped, attempts)."""
+    written unless out_dir is None.  ids: the items to render where they are not 0 .. len(cfgs) - 1 (the online loader's chunks: ``cfgs``
+    is then a dictionary by id).  -> dict(written, skipped, attempts)."""
     fs, c = args["fs"], args["c"]
     log = log or (lambda s: print(s, file=sys.stderr, flush=True))
-    pending, written, attempts = list(range(len(cfgs))), [], {}
+    pending, written, attempts = list(range(len(cfgs))) if ids is None else list(ids), [], {}
     for attempt in range(MAX_ATTEMPTS):
         failed = []
         for i0 in range(0, len(pending), batch):
@@ -760,63 +802,63 @@ def simulate_signals(save_to, stage="pretrain", data_num=1, src_dir="", mic_arra
                     save_dp=save_dp)
 
 
-def _signals(who, out_dir, stage, cfgs, seed, args, sources, stem, device, noise, batch, T, snr_range, nmic, nthreads, log, table="host",
-             noise_type="diffuse_white", saved_cfgs=None, recorded=None, save_dp=False):
-    """The signal generators' run of ``_generate`` (see ``simulate_signals``): item idx of ``cfgs``, planned by plan_sig after seed + idx,
-    goes to ``stem(idx)`` + .wav and _info.npz.  table: where the diffuse field's mixing table is formed - "host": rirsynth.mixing_table
-    while the GPU renders, uploaded with the source; "device": hip.mixing_table of the batch's uploaded microphone positions.
-    noise_type="spatial_white": the white noise goes into hip.rir_mix as it is (no field, no division by its maximum).
-    recorded: what all_info.npz's args hold beside the ranges, T and snr_range.  save_dp: the mix also stores the direct-path signal
-    (hip.rir_mix's out_dp); it is packed and copied with the microphone signal - pipeline.StagedWriter's buffers take both, the batch's
-    signals and then their direct paths - and written as ``stem(idx)`` + _dp.wav in the same write_wav_batch call; all_info.npz's args then hold
-    save_dp=True."""
+def _signal_sink(cfgs, seed, args, dev, noise, T, nmic, plan, emit, load=None, items=None, table="host", noise_type="diffuse_white",
+                 save_dp=False):
+    """``prepare`` and ``sink`` of a ``_generate`` run that turns accepted RIRs into packed PCM-16 signals without the RIR leaving the
+    device: a gather of the accepted rows, the white noise (noise="device": sarssl_gauss_fill keyed by (seed, item); "numpy": the plan's
+    host draw, uploaded), rirsynth.mix_simulated against the direct path at gain 0.9, hip.pcm16_pack.  What differs between the
+    generators that write files (``_signals``) and the online loader (onlinesig.OnlineSignalLoader) comes in as functions:
+
+    * ``plan(i)``: the signal plan of item i - ``snr``, with noise="numpy" ``white``, and ``src`` unless ``load`` brings the sources;
+      called once per item from ``prepare`` (host work while the GPU renders) and kept across attempts,
+    * ``items(idx)``: the items a rendered id serves (default: itself; the online loader's ``reuse`` gives several),
+    * ``load(plans) -> (A, ns) f32 on the device``: the sources of a batch (default: the plans' host crops, uploaded with the SNRs),
+    * ``emit(pcm, aids, rows, lab, plans)``: pcm (nsig A, ns, nmic) int16 on the device - the A signals, then with save_dp their A direct
+      paths -, the items' ids, their rows in the judged batch (``lab``'s index) and their plans."""
     import torch
     from . import hip, rirsynth
-    from .dataset import write_wav_batch
-    from .pipeline import StagedWriter, src_snr_rows
+    from .pipeline import src_snr_rows
     assert table in ("host", "device") and noise_type in NOISE_TYPES
     fs, c = args["fs"], args["c"]
     ns = sig_samples(T, fs)
     diffuse = noise_type == "diffuse_white"
     ntab = 129 * nmic * nmic if diffuse and table == "host" else 0
-    rs = np.random.RandomState()
-    dev = torch.device(device)
-    side = torch.cuda.Stream(dev)
+    assert load is None or not ntab, "sources that are loaded on the device go with table='device'"
+    items = items or (lambda idx: [idx])
     nsig = 2 if save_dp else 1                                # signals per item: the microphones', then the direct path's
     sig_plans = {}
 
     def prepare(ids):                                         # (host work while the GPU renders)
         for idx in ids:
-            if idx not in sig_plans:
-                p = plan_sig(rs, idx, seed, cfgs[idx], sources, T, snr_range, nmic, draw_white=noise == "numpy", fs=fs)
-                if ntab:
-                    p["C"] = rirsynth.mixing_table(cfgs[idx]["mic_pos"], fs, c).astype(np.float32)
-                sig_plans[idx] = p
-
-    def write(buf, ids, infos):
-        paths = [stem(i) + ".wav" for i in ids]
-        if save_dp:
-            paths += [stem(i) + "_dp.wav" for i in ids]
-        write_wav_batch(paths, buf, fs, nthreads)
-        for i, info in zip(ids, infos):
-            np.savez(stem(i) + "_info.npz", **info)
+            for i in items(idx):
+                if i not in sig_plans:
+                    p = plan(i)
+                    if ntab:
+                        p["C"] = rirsynth.mixing_table(cfgs[idx]["mic_pos"], fs, c).astype(np.float32)
+                    sig_plans[i] = p
 
     def sink(b, acc, lab):
-        A, aids = len(acc), [b.ids[j] for j in acc]
+        rows = [j for j in acc for _ in items(b.ids[j])]
+        aids = [i for j in acc for i in items(b.ids[j])]
+        A = len(aids)
         rir_dev, dp_dev = b.rir, b.dp
-        if A < len(b.ids):
-            sel = torch.tensor(acc, device=dev)
+        if rows != list(range(len(b.ids))):
+            sel = torch.tensor(rows, device=dev)
             rir_dev, dp_dev = rir_dev.index_select(0, sel), dp_dev.index_select(0, sel)
-        up = src_snr_rows([sig_plans[i] for i in aids], ns, ntab).to(dev, non_blocking=True)           # src | snr | C of each item
+        plans = [sig_plans[i] for i in aids]
+        if load is None:
+            up = src_snr_rows(plans, ns, ntab).to(dev, non_blocking=True)                              # src | snr | C of each item
+            src, snr = up[:, :ns].contiguous(), up[:, ns].contiguous()
+        else:
+            src = load(plans)
+            snr = torch.tensor([p["snr"] for p in plans], dtype=torch.float32, device=dev)
         if noise == "numpy":
-            white = torch.from_numpy(np.stack([sig_plans[i]["white"] for i in aids]).astype(np.float32)).to(dev)
+            white = torch.from_numpy(np.stack([p["white"] for p in plans]).astype(np.float32)).to(dev)
         else:
             white = torch.empty((A, ns, nmic), dtype=torch.float32, device=dev)
-            for j, i in enumerate(aids):
-                hip.gauss_fill(white[j:j + 1], (int(seed) & 0xffffffff) | WHITE_STREAM, int(i))
-        src, snr = up[:, :ns].contiguous(), up[:, ns].contiguous()
-        rir_len = torch.tensor([b.plans[j]["n_len"] for j in acc], dtype=torch.int32, device=dev)
-        dp_len = torch.tensor([b.plans_dp[j]["n_len"] for j in acc], dtype=torch.int32, device=dev)
+            gauss_fill_items(white, aids, (int(seed) & 0xffffffff) | WHITE_STREAM)
+        rir_len = torch.tensor([b.plans[j]["n_len"] for j in rows], dtype=torch.int32, device=dev)
+        dp_len = torch.tensor([b.plans_dp[j]["n_len"] for j in rows], dtype=torch.int32, device=dev)
         gain = torch.full((A,), PCM_GAIN, dtype=torch.float32, device=dev)
         sig = torch.empty((nsig, A, ns, nmic), dtype=torch.float32, device=dev)
         out_dp = sig[1] if save_dp else None
@@ -826,14 +868,52 @@ def _signals(who, out_dir, stage, cfgs, seed, args, sources, stem, device, noise
             if ntab:
                 C = up[:, ns + 1:].reshape(A, 129, nmic, nmic).contiguous()
             else:
-                mic_pos = np.ascontiguousarray(np.stack([cfgs[i]["mic_pos"] for i in aids]), np.float64)    # (the draws leave them column-major)
+                mic_pos = np.ascontiguousarray(np.stack([cfgs[b.ids[j]]["mic_pos"] for j in rows]), np.float64)  # (the draws leave them column-major)
                 C = hip.mixing_table(torch.from_numpy(mic_pos).to(dev), float(fs), float(c))
             rirsynth.mix_simulated(src, rir_dev, rir_len, dp_dev, dp_len, white, C, snr, gain, out=sig[0], out_dp=out_dp)
         pcm = hip.pcm16_pack(sig).view(nsig * A, ns, nmic)    # dense: the A signals, then their A direct paths
-        infos = [sig_info(cfgs[i], sig_plans.pop(i), lab["t60_edc"][j], lab["drr"][j], lab["c50"][j], c) for i, j in zip(aids, acc)]
-        writer.stage(pcm, write, aids, infos)
+        emit(pcm, aids, rows, lab, [sig_plans.pop(i) for i in aids])
         return aids
 
+    return prepare, sink
+
+
+def _signals(who, out_dir, stage, cfgs, seed, args, sources, stem, device, noise, batch, T, snr_range, nmic, nthreads, log, table="host",
+             noise_type="diffuse_white", saved_cfgs=None, recorded=None, save_dp=False):
+    """The signal generators' run of ``_generate`` (see ``simulate_signals``): item idx of ``cfgs``, planned by plan_sig after seed + idx,
+    goes to ``stem(idx)`` + .wav and _info.npz.  table: where the diffuse field's mixing table is formed - "host": rirsynth.mixing_table
+    while the GPU renders, uploaded with the source; "device": hip.mixing_table of the batch's uploaded microphone positions.
+    noise_type="spatial_white": the white noise goes into hip.rir_mix as it is (no field, no division by its maximum).
+    recorded: what all_info.npz's args hold beside the ranges, T and snr_range.  save_dp: the mix also stores the direct-path signal
+    (hip.rir_mix's out_dp); it is packed and copied with the microphone signal - pipeline.StagedWriter's buffers take both, the batch's
+    signals and then their direct paths - and written as ``stem(idx)`` + _dp.wav in the same write_wav_batch call; all_info.npz's args then hold
+    save_dp=True.  The render, the mix and the pack are ``_signal_sink``'s; this is its sink that writes files."""
+    import torch
+    from .dataset import write_wav_batch
+    from .pipeline import StagedWriter
+    fs, c = args["fs"], args["c"]
+    ns = sig_samples(T, fs)
+    rs = np.random.RandomState()
+    dev = torch.device(device)
+    side = torch.cuda.Stream(dev)
+    nsig = 2 if save_dp else 1
+
+    def plan(idx):
+        return plan_sig(rs, idx, seed, cfgs[idx], sources, T, snr_range, nmic, draw_white=noise == "numpy", fs=fs)
+
+    def write(buf, ids, infos):
+        paths = [stem(i) + ".wav" for i in ids]
+        if save_dp:
+            paths += [stem(i) + "_dp.wav" for i in ids]
+        write_wav_batch(paths, buf, fs, nthreads)
+        for i, info in zip(ids, infos):
+            np.savez(stem(i) + "_info.npz", **info)
+
+    def emit(pcm, aids, rows, lab, plans):
+        infos = [sig_info(cfgs[i], p, lab["t60_edc"][j], lab["drr"][j], lab["c50"][j], c) for i, j, p in zip(aids, rows, plans)]
+        writer.stage(pcm, write, aids, infos)
+
+    prepare, sink = _signal_sink(cfgs, seed, args, dev, noise, T, nmic, plan, emit, table=table, noise_type=noise_type, save_dp=save_dp)
     with StagedWriter(nsig * batch, ns, nmic) as writer, torch.cuda.stream(side):
         return _generate(who, out_dir, stage, cfgs, seed, args, dev, noise, batch, "device", sink, log, prepare,
                          sig_lmax(args["T60_range"], fs), saved_cfgs, T=T, snr_range=tuple(snr_range), **(recorded or {}),

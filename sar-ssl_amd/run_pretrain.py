@@ -1,6 +1,7 @@
 """Pretraining entry point with the reference's command line (code/run_pretrain.py):
 
     python run_pretrain.py --pretrain --simu-exp --gpu-id 0,                      # one GPU
+    python run_pretrain.py --pretrain --simu-exp --simu-online --gpu-id 0,        # the same, every training batch rendered on the GPU (onlinesig.py)
     python run_pretrain.py --pretrain-frozen-encoder --simu-exp --gpu-id 0, --time <time of the --pretrain run>      # second stage, one GPU
     python run_pretrain.py --pretrain --simu-exp --gpu-id 0,1,2,3,4,5,6,7 [--use-amp]       # eight GPUs, the reference's own form
     torchrun --nproc-per-node 8 run_pretrain.py --pretrain --simu-exp --gpu-id 0,1,2,3,4,5,6,7 [--use-amp]     # same thing
@@ -86,6 +87,18 @@ def main(argv=None):
         dl_train = realsig.RealMixLoader(c_train, w_train, num[0], args.bs[0], T, fs, 2, device=device, nthreads=max(1, args.workers))
         dl_val = realsig.RealMixLoader(c_val, w_val, num[1], args.bs[1], T, fs, 2, device=device, nthreads=max(1, args.workers))
         native = False
+    elif args.simu_online:
+        # every training batch is drawn, rendered and packed on the GPU while the previous step runs (onlinesig.OnlineSignalLoader):
+        # MicSig/simu/pretrain need not exist; validation reads the fixed preval corpus from disk, as below
+        from sar_ssl_amd import onlinesig, rirsynth
+        nsample = int(T * fs)
+        bank = rirsynth.DeviceSourceBank(dirs["srcsig_train"], fs, device, max_bytes=int(args.simu_online_bank_gb * (1 << 30)),
+                                         workers=max(1, args.workers))
+        dl_train = onlinesig.OnlineSignalLoader(bank, (args.data_num or [data_num["train"]])[0], args.bs[0], T, args.seed, device,
+                                                reuse=args.simu_online_reuse, rank=rank, world=world)
+        f_val = at_dataset.segment_files(dirs["micsig_simu_preval"])[: data_num["val"]]
+        dl_val = at_dataset.PcmSegmentLoader(f_val, args.bs[1], nsample, 2, fs=fs, device=device, nthreads=max(1, args.workers))
+        native = True                                          # (set_epoch per epoch, as the disk loader)
     elif native:
         # threaded int16 reader -> pinned buffers -> copy stream (dataset.PcmSegmentLoader); same file listing, same
         # rank-strided shuffling as DataLoader + DistributedSampler below
